@@ -14,8 +14,17 @@ Inputs are synthetic and resident in HBM before the timed region.
         --master-port P bench.py --gpus N --steps K --warmup W
 
     python bench.py --workload retrieval --gpus N       (configs[4]: sharded exact top-25)
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full     (everything listed below)
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+A plain run sets up, warms up (the warm-up includes the second-stream choice, and at N > 1 the
+reserved-CU choice), times the K steps and prints the result line: metric, value, unit,
+ms_per_step (+ event statistics), dtype, config, switches.  --dump-outputs DIR then also writes
+what the last timed step computed (loss, embeddings, seeded samples of the updated parameters and
+of their gradients; distances and indices for retrieval) as DIR/<name>.npy; the inputs are
+seeded, so two builds can be compared output for output.
+
+Rank 0 prints ONE JSON line.  With --full, besides the contract fields it carries
   roofline     live HIP-event timing of the dominant hand-written kernel (scl_prof_* sink in
                the C library), priced on its governing roofline.  The events bracket every
                launch and cost ~6 % of a step, so they run over a few extra steps right after
@@ -33,7 +42,7 @@ Rank 0 prints ONE JSON line.  Besides the contract fields it carries
   comm         (N>1) world size as the process group reports it, per-step medians of the
                embedding all-gather and of the wait behind the last gradient all-reduce, the
                step time with 0 and 8 CUs left free by the persistent grids
-  switches     every SCL_* environment switch and A/B flag this run was started with
+  switches     (plain runs too) every SCL_* environment switch and A/B flag this run was started with
 """
 import argparse
 import json
@@ -120,6 +129,16 @@ def parse():
     ap.add_argument('--stub-cpu', action='store_true',
                     help='TEST ONLY: gloo on CPU with a trivial stand-in step; exercises the '
                          'launcher, the barriers and the max-over-ranks timing, measures nothing')
+    ap.add_argument('--full', action='store_true',
+                    help='everything besides the headline figure: per-kernel timing and rooflines, '
+                         'the sustained-MFMA calibration, telemetry, the communication diagnostics '
+                         '(N > 1), batch sweep, B = 192 loss line, retrieval, CPU baselines, and the '
+                         "retrieval workload's local-scan split.  Off (default): set up, warm up, "
+                         'time the --steps steps, print the result line')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='after the timed steps, write what the last timed step computed as '
+                         'DIR/<name>.npy (float32 / float64; fixed seeded samples of the parameters '
+                         'and gradients): same arguments, same inputs, so two builds can be compared')
     return ap.parse_args()
 
 
@@ -769,6 +788,56 @@ def _switches(args):
     return sw
 
 
+DUMP_SAMPLE = 65536     # --dump-outputs: at most this many elements of each parameter / gradient
+DUMP_ROWS_MAX = 2 << 20  # ... and of an output array (a seeded subset of its rows beyond that)
+DUMP_BUDGET = 64 << 20   # bytes of one dump, all files together
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy, float64 for float64 and integer arrays
+    (indices stay exact), float32 for the rest; at most DUMP_BUDGET bytes in all."""
+    out = {}
+    for name, a in arrays.items():
+        if isinstance(a, torch.Tensor):
+            a = a.detach()
+            a = (a.double() if a.dtype == torch.float64 or not a.is_floating_point() else a.float()).cpu().numpy()
+        a = np.asarray(a)
+        out[name] = a.astype(np.float64 if a.dtype == np.float64 or a.dtype.kind in 'iub' else np.float32)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_BUDGET:
+        raise SystemExit('bench.py: --dump-outputs would write %d bytes (budget %d)' % (total, DUMP_BUDGET))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+
+
+def sampled_rows(t, seed=0):
+    """`t` itself, or a seeded subset of its rows (kept in order) when it holds more than
+    DUMP_ROWS_MAX elements; the rows depend on the seed and the shape only."""
+    t = t.detach()
+    per_row = max(1, t[0].numel()) if t.dim() > 1 else 1
+    if t.numel() <= DUMP_ROWS_MAX:
+        return t
+    keep = max(1, DUMP_ROWS_MAX // per_row)
+    idx = np.sort(np.random.default_rng(seed).choice(t.shape[0], keep, replace=False))
+    return t[torch.from_numpy(idx).to(t.device)]
+
+
+def sampled_flat(tensors, seed=0):
+    """Up to DUMP_SAMPLE elements of every tensor at fixed seeded positions (the positions depend
+    on the seed and the shapes only), concatenated in float32."""
+    rng = np.random.default_rng(seed)
+    parts = []
+    for t in tensors:
+        flat = t.detach().reshape(-1)
+        n = flat.numel()
+        if n > DUMP_SAMPLE:
+            idx = np.sort(rng.choice(n, DUMP_SAMPLE, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        parts.append(flat.float().cpu())
+    return torch.cat(parts) if parts else torch.zeros(0)
+
+
 def retrieval_main(args, world, rank, dev, dp=False):
     """--workload retrieval: configs[4] with the REFERENCE SET SHARDED over the ranks (SURVEY
     §8e): every rank scans its rows for all (replicated) queries, the [Q, n] candidates are
@@ -815,7 +884,11 @@ def retrieval_main(args, world, rank, dev, dp=False):
     for _ in range(args.warmup):
         step()
     elapsed, (dd, ii) = timed(step, args.steps)
-    el_local, _ = timed(local_only, args.steps)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {'distances': sampled_rows(dd), 'indices': sampled_rows(ii)})
+    el_local = None
+    if args.full:
+        el_local, _ = timed(local_only, args.steps)
     if rank == 0:
         out = {
             'metric': 'retrieval queries/sec (exact L2 top-%d, %d references x %d queries x %d)' % (n, r, q, d),
@@ -830,14 +903,15 @@ def retrieval_main(args, world, rank, dev, dp=False):
                                    'all-gathered and merged' % (n, world, per),
                        'refs': r, 'queries': q, 'd': d, 'n': n, 'score': args.score,
                        'parallelism': 'ref-shard%d' % world},
-            'local_scan_ms_per_step': round(el_local / args.steps * 1e3, 3),
-            'exchange_and_merge_us_per_step': round((elapsed - el_local) / args.steps * 1e6, 1),
-            'uncertified_queries_local': stats.get('uncertified'),
             'world_seen': dist.get_world_size() if dp else 1,
             'backend': dist.get_backend() if dp else None,
             'checksum_idx': int(ii.sum()),
             'switches': _switches(args),
         }
+        if el_local is not None:
+            out.update(local_scan_ms_per_step=round(el_local / args.steps * 1e3, 3),
+                       exchange_and_merge_us_per_step=round((elapsed - el_local) / args.steps * 1e6, 1),
+                       uncertified_queries_local=stats.get('uncertified'))
         if args.n1_ref > 0:
             out['scaling_efficiency'] = round(out['value'] / (world * args.n1_ref), 4)
         print(json.dumps(out))
@@ -1054,7 +1128,7 @@ def _main_body(args, world, rank, dev, dp):
         loss.backward()
         buckets.finish()
         opt.step()
-        return loss
+        return loss, emb
 
     def fence():
         torch.cuda.synchronize()
@@ -1130,13 +1204,13 @@ def _main_body(args, world, rank, dev, dp):
             torch.cuda.synchronize()
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
-                static_loss = step()
+                static_out = step()
             graph.replay()
             torch.cuda.synchronize()
 
             def run():
                 graph.replay()
-                return static_loss
+                return static_out
         except Exception as exc:                         # noqa: BLE001 (report, then go eager)
             sys.stderr.write('bench.py: HIP graph capture failed (%s: %s); eager launches\n'
                              % (type(exc).__name__, exc))
@@ -1159,12 +1233,21 @@ def _main_body(args, world, rank, dev, dp):
         t0 = time.perf_counter()
         evs[0].record()
         for k in range(args.steps):
-            loss = run()
+            loss, emb = run()
             evs[k + 1].record()
         fence()
         elapsed = time.perf_counter() - t0
     per_step = sorted(evs[k].elapsed_time(evs[k + 1]) for k in range(args.steps))
-    if not in_region:
+    if rank == 0 and args.dump_outputs:
+        # what the caller of the last timed step receives: its loss, this rank's embeddings, and
+        # the parameters after the Adam update with the gradients that produced it (sampled)
+        dump_outputs(args.dump_outputs, {'loss': loss.detach().reshape(1), 'embeddings': sampled_rows(emb),
+                                         'params_sample': sampled_flat(params),
+                                         'grads_sample': sampled_flat([p.grad for p in params])})
+    if not args.full:
+        nets.WORK_LOG = None
+        elapsed_prof = None
+    elif not in_region:
         nets.WORK_LOG = {}    # algorithmic flops / bytes of the backbone kernels, per call site
         # one stream here: the timed steps run the weight-gradient kernels on a second stream
         # next to the backward-data kernels (nets.USE_SIDE_WRW); a duration taken while two
@@ -1186,7 +1269,7 @@ def _main_body(args, world, rank, dev, dp):
     work, nets.WORK_LOG = nets.WORK_LOG, None
     loss_val = float(loss.detach())
     global BRACKET_US
-    BRACKET_US = bracket_us(dev) if rank == 0 else 0.0
+    BRACKET_US = bracket_us(dev) if rank == 0 and args.full else 0.0
 
     def timed_steps(k):
         fence()
@@ -1207,9 +1290,10 @@ def _main_body(args, world, rank, dev, dp):
     profiled = 'rocprof' in os.environ.get('LD_PRELOAD', '').lower() or any(
         k.startswith(('ROCPROF', 'ROCPROFILER')) for k in os.environ)
     telemetry = (gpu_telemetry(step, fence)
-                 if rank == 0 and world == 1 and not args.no_telemetry and not profiled else None)
+                 if args.full and rank == 0 and world == 1 and not args.no_telemetry and not profiled
+                 else None)
     comm = None
-    if dp:
+    if dp and args.full:
         # what the first multi-GPU run must be able to explain by itself
         diag_steps = max(3, min(args.steps, 10))
         parallel.COMM_LOG = {'allgather': [], 'finish': []}
@@ -1248,61 +1332,6 @@ def _main_body(args, world, rank, dev, dp):
 
     if rank == 0:
         n_loc = (args.height // 16) * (args.width // 16)
-        models = kernel_models(b, n_loc, gb, 2 if cdt == torch.bfloat16 else 4)
-        summ = kt.summary()
-        kernels = [price(k, c, ms, models[k]) for k, (c, ms) in sorted(summ.items()) if k in models]
-        # the dominant kernel of the NetVLAD + pairwise-loss family ...
-        dom_head = max(kernels, key=lambda r: r['us'] * r['launches']) if kernels else None
-        # the backbone's own kernels (convolutions against the bf16 dense MFMA peak or HBM,
-        # whichever governs; elementwise glue against HBM), work as logged by the call sites
-        for k, (c, ms) in sorted(summ.items()):
-            if k in work and work[k][0] == c:
-                _, fl, by = work[k]
-                kernels.append(price(k, c, ms, dict(flops=fl / c, bytes=by / c,
-                                                    peak_tflops=PEAK_BF16_TFLOPS)))
-        # ... and of the whole step (a backbone convolution): `roofline` is the latter
-        dom = max(kernels, key=lambda r: r['us'] * r['launches']) if kernels else None
-
-        def roof(d):
-            peak_tf = PEAK_BF16_TFLOPS if d['kernel'] in work else PEAK_F32_TFLOPS
-            return dict(kernel=d['kernel'], bound=d['bound'],
-                        achieved=d.get('executed_tflops', d['tflops'])
-                        if d['bound'] == 'mfma' else d['gbps'],
-                        peak=d.get('mfma_peak_tflops', peak_tf)
-                        if d['bound'] == 'mfma' else PEAK_HBM_GBPS,
-                        unit='TFLOP/s' if d['bound'] == 'mfma' else 'GB/s',
-                        frac=d['frac'], traffic=None, us_per_launch=d['us'],
-                        launches_per_step=d['launches'] / max(prof_steps, 1))
-        roofline = roof(dom) if dom else None
-        roofline_head = roof(dom_head) if dom_head else None
-        if roofline:
-            # HBM bytes per launch measured offline with rocprofv3 PMC on this exact shape
-            # (profiles/pmc_traffic.json); null when the shape / dtype was not profiled
-            try:
-                with open(os.path.join(ROOT, 'profiles', 'pmc_traffic.json')) as f:
-                    pmc = json.load(f)
-                for rf in (roofline, roofline_head):
-                    ent = pmc.get(args.dtype, {}).get(rf['kernel'])
-                    if ent and pmc['shape'] == {'batch': b, 'locations': n_loc}:
-                        rf['traffic'] = ent['read'] + ent['write']
-                        alg = (work[rf['kernel']][2] / work[rf['kernel']][0]
-                               if rf['kernel'] in work else models[rf['kernel']]['bytes'])
-                        rf['traffic_algorithmic'] = int(alg)
-                        rf['traffic_source'] = ('rocprofv3 FETCH_SIZE x2 + WRITE_SIZE per launch, '
-                                                'L2 misses incl. Infinity-Cache hits '
-                                                '(profiles/pmc_traffic.json: %s)' % pmc.get('source', '?'))
-            except (OSError, ValueError, KeyError):
-                pass
-        if world == 1 and roofline and roofline['bound'] == 'mfma' and roofline['kernel'] in work:
-            try:
-                sus = sustained_mfma(dev)
-                top = max(sus['tflops_32x32x16'], sus['tflops_16x16x32'])
-                sus['frac_of_sustained'] = round(roofline['achieved'] / top, 4)
-                sus['sustained_over_peak'] = round(top / roofline['peak'], 4)
-                roofline['sustained'] = sus
-            except (RuntimeError, AttributeError) as e:
-                roofline['sustained'] = {'error': str(e)}
-        hip_ms = sum(r['us'] * r['launches'] for r in kernels) / 1e3 / max(prof_steps, 1)
         out = {
             'metric': 'train-step images/sec (VGG16-NetVLAD soft-MS, 640x480)',
             'value': round(gb * args.steps / elapsed, 2),
@@ -1329,33 +1358,91 @@ def _main_body(args, world, rank, dev, dp):
                                    % (b, args.width, args.height, args.dtype),
                        'global_batch': gb, 'locations': n_loc, 'parallelism': 'dp%d' % world,
                        'optimizer': 'adam', 'loss': float('%.6g' % loss_val)},
-            'kernel_timing': {'method': 'HIP events around every launch of the hand-written kernels '
-                                        '(scl_prof sink), on the launch stream',
-                              'steps': prof_steps,
-                              'where': 'timed region' if in_region else
-                              'extra eager steps right after the timed region (the events cost '
-                              '~6 % of a step, so the timed steps run without them)',
-                              'streams': 'one (the timed steps run the weight-gradient kernels on a '
-                                         'second stream next to the backward-data kernels; the '
-                                         'instrumented steps serialise them so that a duration '
-                                         'is one kernel alone)'
-                              if (nets.USE_SIDE_WRW or bool(nets.USE_SPLIT_FWD)) else 'one',
-                              'ms_per_step_with_events': round(elapsed_prof / prof_steps * 1e3, 3),
-                              'bracket_us': round(BRACKET_US, 2),
-                              'null_kernel_us': round(NULL_KERNEL_DEVICE_US or 0.0, 2),
-                              'bracket_how': 'event duration of the empty kernel (scl_prof_null) minus '
-                                             'its own time (null_kernel_us: 200 launches back to back '
-                                             'between one event pair), both in this process; subtracted '
-                                             'from every `us` below, at most %d %% of a duration; '
-                                             '`us_events` / `frac_events` are the raw figures'
-                                             % int(BRACKET_CAP * 100)},
-            'roofline': roofline,
-            'roofline_netvlad_loss': roofline_head,
-            'roofline_netvlad_stage': netvlad_stage(kernels, b, n_loc, 2 if cdt == torch.bfloat16 else 4,
-                                                    prof_steps),
-            'kernels': kernels,
-            'hip_path_ms_per_step': round(hip_ms, 3),
         }
+        if args.full:
+            models = kernel_models(b, n_loc, gb, 2 if cdt == torch.bfloat16 else 4)
+            summ = kt.summary()
+            kernels = [price(k, c, ms, models[k]) for k, (c, ms) in sorted(summ.items()) if k in models]
+            # the dominant kernel of the NetVLAD + pairwise-loss family ...
+            dom_head = max(kernels, key=lambda r: r['us'] * r['launches']) if kernels else None
+            # the backbone's own kernels (convolutions against the bf16 dense MFMA peak or HBM,
+            # whichever governs; elementwise glue against HBM), work as logged by the call sites
+            for k, (c, ms) in sorted(summ.items()):
+                if k in work and work[k][0] == c:
+                    _, fl, by = work[k]
+                    kernels.append(price(k, c, ms, dict(flops=fl / c, bytes=by / c,
+                                                        peak_tflops=PEAK_BF16_TFLOPS)))
+            # ... and of the whole step (a backbone convolution): `roofline` is the latter
+            dom = max(kernels, key=lambda r: r['us'] * r['launches']) if kernels else None
+
+            def roof(d):
+                peak_tf = PEAK_BF16_TFLOPS if d['kernel'] in work else PEAK_F32_TFLOPS
+                return dict(kernel=d['kernel'], bound=d['bound'],
+                            achieved=d.get('executed_tflops', d['tflops'])
+                            if d['bound'] == 'mfma' else d['gbps'],
+                            peak=d.get('mfma_peak_tflops', peak_tf)
+                            if d['bound'] == 'mfma' else PEAK_HBM_GBPS,
+                            unit='TFLOP/s' if d['bound'] == 'mfma' else 'GB/s',
+                            frac=d['frac'], traffic=None, us_per_launch=d['us'],
+                            launches_per_step=d['launches'] / max(prof_steps, 1))
+            roofline = roof(dom) if dom else None
+            roofline_head = roof(dom_head) if dom_head else None
+            if roofline:
+                # HBM bytes per launch measured offline with rocprofv3 PMC on this exact shape
+                # (profiles/pmc_traffic.json); null when the shape / dtype was not profiled
+                try:
+                    with open(os.path.join(ROOT, 'profiles', 'pmc_traffic.json')) as f:
+                        pmc = json.load(f)
+                    for rf in (roofline, roofline_head):
+                        ent = pmc.get(args.dtype, {}).get(rf['kernel'])
+                        if ent and pmc['shape'] == {'batch': b, 'locations': n_loc}:
+                            rf['traffic'] = ent['read'] + ent['write']
+                            alg = (work[rf['kernel']][2] / work[rf['kernel']][0]
+                                   if rf['kernel'] in work else models[rf['kernel']]['bytes'])
+                            rf['traffic_algorithmic'] = int(alg)
+                            rf['traffic_source'] = ('rocprofv3 FETCH_SIZE x2 + WRITE_SIZE per launch, '
+                                                    'L2 misses incl. Infinity-Cache hits '
+                                                    '(profiles/pmc_traffic.json: %s)' % pmc.get('source', '?'))
+                except (OSError, ValueError, KeyError):
+                    pass
+            if world == 1 and roofline and roofline['bound'] == 'mfma' and roofline['kernel'] in work:
+                try:
+                    sus = sustained_mfma(dev)
+                    top = max(sus['tflops_32x32x16'], sus['tflops_16x16x32'])
+                    sus['frac_of_sustained'] = round(roofline['achieved'] / top, 4)
+                    sus['sustained_over_peak'] = round(top / roofline['peak'], 4)
+                    roofline['sustained'] = sus
+                except (RuntimeError, AttributeError) as e:
+                    roofline['sustained'] = {'error': str(e)}
+            hip_ms = sum(r['us'] * r['launches'] for r in kernels) / 1e3 / max(prof_steps, 1)
+            out.update({
+                'kernel_timing': {'method': 'HIP events around every launch of the hand-written kernels '
+                                            '(scl_prof sink), on the launch stream',
+                                  'steps': prof_steps,
+                                  'where': 'timed region' if in_region else
+                                  'extra eager steps right after the timed region (the events cost '
+                                  '~6 % of a step, so the timed steps run without them)',
+                                  'streams': 'one (the timed steps run the weight-gradient kernels on a '
+                                             'second stream next to the backward-data kernels; the '
+                                             'instrumented steps serialise them so that a duration '
+                                             'is one kernel alone)'
+                                  if (nets.USE_SIDE_WRW or bool(nets.USE_SPLIT_FWD)) else 'one',
+                                  'ms_per_step_with_events': round(elapsed_prof / prof_steps * 1e3, 3),
+                                  'bracket_us': round(BRACKET_US, 2),
+                                  'null_kernel_us': round(NULL_KERNEL_DEVICE_US or 0.0, 2),
+                                  'bracket_how': 'event duration of the empty kernel (scl_prof_null) minus '
+                                                 'its own time (null_kernel_us: 200 launches back to back '
+                                                 'between one event pair), both in this process; subtracted '
+                                                 'from every `us` below, at most %d %% of a duration; '
+                                                 '`us_events` / `frac_events` are the raw figures'
+                                                 % int(BRACKET_CAP * 100)},
+                'roofline': roofline,
+                'roofline_netvlad_loss': roofline_head,
+                'roofline_netvlad_stage': netvlad_stage(kernels, b, n_loc, 2 if cdt == torch.bfloat16 else 4,
+                                                        prof_steps),
+                'kernels': kernels,
+                'hip_path_ms_per_step': round(hip_ms, 3),
+            })
         out['switches'] = _switches(args)
         out['side_stream'] = dict(mode='auto' if args.side_wrw < 0 else 'fixed',
                                   on=bool(nets.USE_SIDE_WRW), **(
@@ -1366,15 +1453,16 @@ def _main_body(args, world, rank, dev, dp):
             out['telemetry'] = telemetry
         if args.n1_ref > 0:
             out['scaling_efficiency'] = round(out['value'] / (world * args.n1_ref), 4)
-        if world == 1 and not args.no_batch_sweep:
-            out['batch_sweep'] = batch_sweep(dev)
-        if world == 1:
-            out['roofline_loss_b192'] = loss_b192_line(dev)
-            if not args.no_retrieval:
-                out['retrieval'] = retrieval_line(dev)
-        if world == 1 and not args.no_cpu_baseline:
-            out['cpu_baseline'] = cpu_baseline(args, torch.get_num_threads())
-            out['cpu_baseline_kernels'] = cpu_baseline_kernels(torch.get_num_threads())
+        if args.full:
+            if world == 1 and not args.no_batch_sweep:
+                out['batch_sweep'] = batch_sweep(dev)
+            if world == 1:
+                out['roofline_loss_b192'] = loss_b192_line(dev)
+                if not args.no_retrieval:
+                    out['retrieval'] = retrieval_line(dev)
+            if world == 1 and not args.no_cpu_baseline:
+                out['cpu_baseline'] = cpu_baseline(args, torch.get_num_threads())
+                out['cpu_baseline_kernels'] = cpu_baseline_kernels(torch.get_num_threads())
         print(json.dumps(out))
     if dp:
         dist.destroy_process_group()

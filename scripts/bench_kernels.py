@@ -1,3 +1,5 @@
+"""Top kernels of a saved `bench.py --full` result line (the plain line has no `kernels`):
+`python scripts/bench_kernels.py line.json`."""
 import json,sys
 d=json.loads(open(sys.argv[1]).readline())
 print(d['ms_per_step'], d['value'])

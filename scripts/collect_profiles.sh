@@ -4,16 +4,16 @@ set -x
 RN=${1:-r06}
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$RN; mkdir -p $O
 cd /tmp; export TMPDIR=/tmp
-python3 $R/bench.py --steps 20 --warmup 5 > $O/bench_n1_default_run.json 2> $O/bench.err
-python3 $R/bench.py --steps 20 --warmup 5 --side-wrw 0 --no-cpu-baseline > $O/bench_n1_one_stream.json 2>> $O/bench.err
+python3 $R/bench.py --full --steps 20 --warmup 5 > $O/bench_n1_default_run.json 2> $O/bench.err
+python3 $R/bench.py --full --steps 20 --warmup 5 --side-wrw 0 --no-cpu-baseline > $O/bench_n1_one_stream.json 2>> $O/bench.err
 # kernel trace of the default command, and of the one-stream run (the durations of `roofline`
 # are taken with the weight-gradient kernels serialised: compare with the second table)
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-batch-sweep --no-retrieval --no-telemetry > $O/bench_under_rocprof.json 2>/dev/null
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace1 -- python3 $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-batch-sweep --no-retrieval --no-telemetry --side-wrw 0 > $O/bench_under_rocprof_one_stream.json 2>/dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 $R/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-batch-sweep --no-retrieval --no-telemetry > $O/bench_under_rocprof.json 2>/dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace1 -- python3 $R/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-batch-sweep --no-retrieval --no-telemetry --side-wrw 0 > $O/bench_under_rocprof_one_stream.json 2>/dev/null
 # HBM traffic of the backbone kernels (separate passes per counter, no tracing)
-rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_bb/fetch -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-batch-sweep --no-retrieval --no-telemetry --side-wrw 0 > /dev/null 2>&1
-rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_bb/write -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-batch-sweep --no-retrieval --no-telemetry --side-wrw 0 > /dev/null 2>&1
-rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY --output-format csv -d $O/pmc_bb/sq -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-batch-sweep --no-retrieval --no-telemetry --side-wrw 0 > /dev/null 2>&1
+rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_bb/fetch -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-batch-sweep --no-retrieval --no-telemetry --side-wrw 0 > /dev/null 2>&1
+rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_bb/write -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-batch-sweep --no-retrieval --no-telemetry --side-wrw 0 > /dev/null 2>&1
+rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY --output-format csv -d $O/pmc_bb/sq -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-batch-sweep --no-retrieval --no-telemetry --side-wrw 0 > /dev/null 2>&1
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY --output-format csv -d $O/pmc_nv/sq -- python3 $R/scripts/microbench.py --what netvlad,loss --iters 3 --loss-batches 24,192 > /dev/null 2>&1
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_nv/fetch -- python3 $R/scripts/microbench.py --what netvlad,loss --iters 3 --loss-batches 24,192 > /dev/null 2>&1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_nv/write -- python3 $R/scripts/microbench.py --what netvlad,loss --iters 3 --loss-batches 24,192 > /dev/null 2>&1
@@ -24,8 +24,8 @@ cp $(ls $O/trace_nv/*/*kernel_stats.csv | head -1) $O/microbench_netvlad_loss_ke
 python3 scripts/pmc_summary.py $O/pmc_tn --only kernel --out $O/pmc_topn_sq_counters.csv > /dev/null 2>&1
 python3 scripts/microbench.py --iters 20 --topn-score f32,bf16x3 --json $O/microbench_netvlad_loss_topn.json > $O/microbench.log 2>&1
 python3 tests/tools/parity_report.py --json $O/parity_report.json > $O/parity.log 2>&1
-python3 bench.py --workload retrieval --steps 5 --warmup 2 > $O/bench_retrieval_n1_f32.json 2>> $O/bench.err
-python3 bench.py --workload retrieval --steps 5 --warmup 2 --score bf16x3 > $O/bench_retrieval_n1_bf16x3.json 2>> $O/bench.err
+python3 bench.py --full --workload retrieval --steps 5 --warmup 2 > $O/bench_retrieval_n1_f32.json 2>> $O/bench.err
+python3 bench.py --full --workload retrieval --steps 5 --warmup 2 --score bf16x3 > $O/bench_retrieval_n1_bf16x3.json 2>> $O/bench.err
 python3 scripts/vlad_stamps.py --kernel fwd > $O/vlad_stamps_fwd.txt 2>/dev/null
 python3 scripts/vlad_stamps.py --kernel fwd8 > $O/vlad_stamps_fwd8.txt 2>/dev/null
 python3 scripts/vlad_stamps.py --kernel dx > $O/vlad_stamps_dx.txt 2>/dev/null
@@ -39,7 +39,7 @@ python3 scripts/wrw_ab.py --variants 0,2200 --rounds 2 > $O/wrw64_buffer_path_vs
 python3 scripts/first_wrw_fused_ablate.py --stamps > $O/first_wrw_fused_ablations_and_stamps.txt 2>/dev/null
 bash scripts/env_ab.sh SCL_FUSED_FIRST_WRW 2 > $O/fused_first_wrw_step_ab.txt 2>/dev/null
 # round 6: the one-rank RCCL step, the loss forward forms + stamps, NetVLAD inference sweep, retrieval forms
-python3 bench.py --steps 20 --warmup 5 --force-dist --no-cpu-baseline --no-retrieval --no-batch-sweep > $O/bench_n1_force_dist_rccl.json 2>> $O/bench.err
+python3 bench.py --full --steps 20 --warmup 5 --force-dist --no-cpu-baseline --no-retrieval --no-batch-sweep > $O/bench_n1_force_dist_rccl.json 2>> $O/bench.err
 python3 scripts/force_dist_ab.py 2>/dev/null | grep -v "^RCCL\|^HIP\|^ROCm\|^Hostname\|^Librccl" > $O/force_dist_same_process_ab.txt
 python3 scripts/loss_fwd_ab.py 2>/dev/null | grep "^{" > $O/loss_fwd_forms_ab.jsonl
 python3 scripts/loss_stamps.py --batch 192 2>/dev/null > $O/loss_stamps_b192.txt

@@ -202,7 +202,7 @@ def test_bench_two_ranks_on_one_gpu():
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '2',
-                        '--warmup', '1', '--no-cpu-baseline'], env=env, capture_output=True,
+                        '--warmup', '1', '--full', '--no-cpu-baseline'], env=env, capture_output=True,
                        text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
@@ -239,7 +239,7 @@ def test_bench_eight_ranks_on_one_gpu_reduced_images():
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '8', '--steps', '2',
                         '--warmup', '1', '--batch', '4', '--height', '128', '--width', '160',
-                        '--no-cpu-baseline'], env=env, capture_output=True, text=True, timeout=1500)
+                        '--full', '--no-cpu-baseline'], env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1
@@ -268,7 +268,7 @@ def test_bench_retrieval_workload_two_ranks_on_one_gpu():
     for gpus in (1, 2):
         r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--workload', 'retrieval',
                             '--gpus', str(gpus), '--steps', '2', '--warmup', '1', '--refs', '20000',
-                            '--queries', '1000', '--n1-ref', '1000.0'], env=env, capture_output=True,
+                            '--queries', '1000', '--n1-ref', '1000.0', '--full'], env=env, capture_output=True,
                            text=True, timeout=900)
         assert r.returncode == 0, r.stderr[-2000:]
         lines = [l for l in r.stdout.splitlines() if l.startswith('{')]

@@ -248,7 +248,7 @@ def _bench(extra, timeout=1500):
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT', 'SCL_BENCH_ONE_GPU_GLOO'):
         env.pop(k, None)
     env.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--no-cpu-baseline',
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--full', '--no-cpu-baseline',
                         '--no-retrieval', '--no-batch-sweep', '--no-telemetry'] + extra, env=env,
                        capture_output=True, text=True, timeout=timeout)
     assert r.returncode == 0, r.stderr[-3000:]
