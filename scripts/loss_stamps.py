@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Where the one-launch pairwise-loss forward (csrc/gram_loss.hip: gram16x6_persist_kernel /
+"""Where the one-launch pairwise-loss forward (csrc/gram_loss_diag.hip: gram16x6_persist_kernel /
 gram16_persist_kernel) spends its time: scl_debug_set_variant(40) makes thread 0 of every workgroup
 write shader-clock stamps into the tail of the workspace; prints, per phase, the median and the
 maximum over workgroups in microseconds (s_memtime ticks at 100 MHz).  DIAGNOSTIC ONLY.

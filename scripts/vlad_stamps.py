@@ -1,8 +1,8 @@
 #!/usr/bin/env python
-"""Where the fused NetVLAD kernels (csrc/netvlad.hip: vlad_fwd_kernel, vlad_dx_kernel) spend their
-cycles: runs them with scl_debug_set_variant(916 / 917) — wave 0 of every workgroup writes
-shader-clock stamps into the tail of the workspace — and prints the median over workgroups of
-every phase, in cycles.  DIAGNOSTIC ONLY (the stamps perturb the kernel)."""
+"""Where the fused NetVLAD kernels (csrc/netvlad_diag.hip: vlad_fwd_kernel; csrc/netvlad.hip:
+vlad_dx_kernel) spend their cycles: runs them with scl_debug_set_variant(916 / 917) — wave 0 of
+every workgroup writes shader-clock stamps into the tail of the workspace — and prints the median
+over workgroups of every phase, in cycles.  DIAGNOSTIC ONLY (the stamps perturb the kernel)."""
 import argparse
 import os
 

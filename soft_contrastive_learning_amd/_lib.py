@@ -6,7 +6,8 @@ HIP device, the call raises.  PyTorch is used only for device memory and streams
 Two builds of the same sources exist (csrc/Makefile): the PRODUCT library ``libscl_hip.so`` — what
 ``load()`` returns — has no diagnostic kernel variants compiled in and rejects
 ``scl_debug_set_variant(v != 0)``; ``libscl_hip_diag.so`` (``-DSCL_DIAG``) carries the A/B,
-ablation and clock-stamp variants.  ``with variant(v):`` runs the enclosed calls on the
+ablation and clock-stamp variants (the kernels only a variant launches are in
+``csrc/*_diag.hip``, which that build alone compiles).  ``with variant(v):`` runs the enclosed calls on the
 diagnostic build under variant ``v`` (equality tests, scripts/); ``SCL_DIAG=1`` in the
 environment or ``use_diag()`` makes it the process's library (scripts/).
 """

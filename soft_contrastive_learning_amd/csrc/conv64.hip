@@ -1862,23 +1862,17 @@ __global__ __launch_bounds__(64) void conv_first_davg_kernel(
 
 static int conv64_cus();
 
-// conv1_2 with two 4-wave workgroups per CU (ConvCfg GEO 1) — DIAGNOSTIC BUILD, SCL_CONV64_TWO_WG=1.
-// Round 6 measured it (scripts/conv12_geo_ab.py, profiles/r06/conv12_two_workgroups_per_cu.txt):
-// bit-identical, forward 488 -> 478 us, backward-data with the un-pooling window 555 -> 686 us,
-// bias + ReLU forward 510 -> 510.  Taking the tile barrier out from between the two waves of a
-// SIMD does not speed the K loop up: the 8,100 cycles per tile are not the phase lock DESIGN.md
-// section 7 suspected, so the product keeps the one 8-wave workgroup.
-static bool conv64_two_wg() {
 #ifdef SCL_DIAG
-  static const bool on = [] {
-    const char* e = getenv("SCL_CONV64_TWO_WG");
-    return e && e[0] == '1';
-  }();
-  return on;
-#else
-  return false;
+// the diagnostic variants (conv64_diag.hip): true when the variant owns the call, its status in *rc
+static bool conv3x3_diag(const void* x, const void* w, int64_t sk, int64_t sc, int64_t sh, int64_t sw,
+                         int transposed, int B, int H, int W, int cin, int kout, void* out, const float* bias,
+                         int relu, void* pooled, const void* mask, void* pidx, const void* uidx, void* workspace,
+                         hipStream_t st, int* rc);
+static bool wrw3x3_diag(const void* x, const void* gz, const unsigned char* pidx, int B, int H, int W, int cin,
+                        int kout, void* gw, int64_t w_stride_k, int64_t w_stride_c, int64_t w_stride_h,
+                        int64_t w_stride_w, int gw_f32, float* grad_bias, void* workspace, size_t need,
+                        void* stream, int* rc);
 #endif
-}
 
 template <int CIN, int KOUT, int GEO = 0>
 int launch_conv3x3(const void* x, const void* w, int64_t sk, int64_t sc, int64_t sh, int64_t sw,
@@ -1973,9 +1967,12 @@ static int conv3x3_dispatch(const void* x, const void* w, int64_t w_stride_k, in
                                   transposed, B, H, W, out, bias, relu ? 1 : 0, pooled,        \
                                   mask, pidx, uidx, workspace, st);
 #ifdef SCL_DIAG
-  if (cin == 64 && kout == 64 && conv64_two_wg())
-    return launch_conv3x3<64, 64, 1>(x, w, w_stride_k, w_stride_c, w_stride_h, w_stride_w, transposed, B, H,
-                                     W, out, bias, relu ? 1 : 0, pooled, mask, pidx, uidx, workspace, st);
+  {
+    int rc;
+    if (conv3x3_diag(x, w, w_stride_k, w_stride_c, w_stride_h, w_stride_w, transposed, B, H, W, cin, kout, out,
+                     bias, relu, pooled, mask, pidx, uidx, workspace, st, &rc))
+      return rc;
+  }
 #endif
   SCL_CONV_CASE(64, 64)
   SCL_CONV_CASE(64, 128)
@@ -2099,27 +2096,26 @@ static int wrw3x3_run(const void* x, const void* gz, const unsigned char* pidx, 
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wrw64_kernel<D, T, N, PL>),         \
                             hipFuncAttributeMaxDynamicSharedMemorySize,                        \
                             (int)WrwCfg<T, N>::LDS);
-    SCL_WRW_ATTR(0, 32, 1, 0) SCL_WRW_ATTR(2, 32, 1, 0)
-    SCL_WRW_ATTR(0, 8, 1, 0) SCL_WRW_ATTR(0, 32, 2, 0) SCL_WRW_ATTR(0, 8, 2, 0)
+    SCL_WRW_ATTR(0, 32, 1, 0) SCL_WRW_ATTR(0, 8, 1, 0) SCL_WRW_ATTR(0, 32, 2, 0) SCL_WRW_ATTR(0, 8, 2, 0)
     SCL_WRW_ATTR(0, 32, 1, 1) SCL_WRW_ATTR(0, 8, 1, 1) SCL_WRW_ATTR(0, 32, 2, 1) SCL_WRW_ATTR(0, 8, 2, 1)
-    SCL_WRW_ATTR(4, 32, 2, 0) SCL_WRW_ATTR(4, 8, 2, 0) SCL_WRW_ATTR(4, 32, 2, 1) SCL_WRW_ATTR(4, 8, 2, 1)
-    SCL_WRW_ATTR(6, 32, 2, 0) SCL_WRW_ATTR(6, 8, 2, 0)
-#ifdef SCL_DIAG
-    SCL_WRW_ATTR(8, 32, 2, 0) SCL_WRW_ATTR(8, 8, 2, 0) SCL_WRW_ATTR(8, 32, 2, 1) SCL_WRW_ATTR(8, 8, 2, 1)
-    SCL_WRW_ATTR(16, 32, 2, 0) SCL_WRW_ATTR(16, 8, 2, 0) SCL_WRW_ATTR(16, 32, 2, 1) SCL_WRW_ATTR(16, 8, 2, 1)
-#endif
 #undef SCL_WRW_ATTR
   });
+#ifdef SCL_DIAG
+  {
+    int rc;
+    if (wrw3x3_diag(x, gz, pidx, B, H, W, cin, kout, gw, w_stride_k, w_stride_c, w_stride_h, w_stride_w, gw_f32,
+                    grad_bias, workspace, need, stream, &rc))
+      return rc;
+  }
+#endif
   const int cus = conv64_cus();
   // [64 c] x [128 k] blocks wherever the output channels allow (scl_debug_set_variant(2100)
   // pins the 64 x 64 variant); tile shape: wide, or tall where that pads the map less
-  const int dbg = scl_variant() / 1000 == 2 ? scl_variant() & 3 : 0;
-  const bool stamps = (scl_variant() == 2004 || scl_variant() == 2006) && kout % 128 == 0;   // (needs >= 64 KB of bias slabs)
-  const int nkb = (kout % 128 == 0 && dbg == 0 && scl_variant() != 2100) ? 2 : 1;
+  const int nkb = (kout % 128 == 0 && scl_variant() != 2100) ? 2 : 1;
   const int th_w = nkb == 1 ? 8 : 4, th_t = nkb == 1 ? 32 : 16;
   const int tiles_wide = B * ((H + th_w - 1) / th_w) * ((W + 31) / 32);
   const int tiles_tall = B * ((H + th_t - 1) / th_t) * ((W + 7) / 8);
-  const bool tall = tiles_tall < tiles_wide && dbg == 0;
+  const bool tall = tiles_tall < tiles_wide;
   const int tiles = tall ? tiles_tall : tiles_wide;
   const int P = wrw_splits(cin, kout, tiles, cus);
   hipStream_t st = (hipStream_t)stream;
@@ -2130,37 +2126,6 @@ static int wrw3x3_run(const void* x, const void* gz, const unsigned char* pidx, 
              (float*)workspace, bslabs, pidx)
   float* bslabs = grad_bias ? (float*)((char*)workspace + wrw_bias_slab_offset(cin, kout)) : nullptr;
   int PP = P;
-  if (stamps) {
-    PP = wrw_splits(cin, kout / 2, tiles, cus);
-    bslabs = (float*)((char*)workspace + wrw_bias_slab_offset(cin, kout));
-    if ((size_t)PP * (cin / 64) * (kout / 128) * 256 > need - wrw_bias_slab_offset(cin, kout))
-      return SCL_E_WORKSPACE;
-    if (scl_variant() == 2006) {        // ... without staging after the first tile
-      if (tall) SCL_WRW_LAUNCH(6, 8, 2, 0); else SCL_WRW_LAUNCH(6, 32, 2, 0);
-    } else if (pidx) {
-      if (tall) SCL_WRW_LAUNCH(4, 8, 2, 1); else SCL_WRW_LAUNCH(4, 32, 2, 1);
-    } else {
-      if (tall) SCL_WRW_LAUNCH(4, 8, 2, 0); else SCL_WRW_LAUNCH(4, 32, 2, 0);
-    }
-    return scl_launch_status();
-  }
-#ifdef SCL_DIAG
-  if (nkb == 2 && scl_variant() == 2200) {     // round 4's staging (no buffer path): A/B partner, CORRECT results
-    PP = wrw_splits(cin, kout / 2, tiles, cus);
-    if (pidx) {
-      if (tall) SCL_WRW_LAUNCH(8, 8, 2, 1); else SCL_WRW_LAUNCH(8, 32, 2, 1);
-    } else {
-      if (tall) SCL_WRW_LAUNCH(8, 8, 2, 0); else SCL_WRW_LAUNCH(8, 32, 2, 0);
-    }
-  } else if (nkb == 2 && scl_variant() == 2300) {   // 16x16x32 timing ablation: RESULTS MEANINGLESS
-    PP = wrw_splits(cin, kout / 2, tiles, cus);
-    if (pidx) {
-      if (tall) SCL_WRW_LAUNCH(16, 8, 2, 1); else SCL_WRW_LAUNCH(16, 32, 2, 1);
-    } else {
-      if (tall) SCL_WRW_LAUNCH(16, 8, 2, 0); else SCL_WRW_LAUNCH(16, 32, 2, 0);
-    }
-  } else
-#endif
   if (nkb == 2) {
     PP = wrw_splits(cin, kout / 2, tiles, cus);
     if (pidx) {
@@ -2171,8 +2136,7 @@ static int wrw3x3_run(const void* x, const void* gz, const unsigned char* pidx, 
   } else if (pidx) {
     if (tall) SCL_WRW_LAUNCH(0, 8, 1, 1); else SCL_WRW_LAUNCH(0, 32, 1, 1);
   } else if (tall) SCL_WRW_LAUNCH(0, 8, 1, 0);
-  else if (dbg == 0) SCL_WRW_LAUNCH(0, 32, 1, 0);
-  else SCL_WRW_LAUNCH(2, 32, 1, 0);
+  else SCL_WRW_LAUNCH(0, 32, 1, 0);
 #undef SCL_WRW_LAUNCH
   const int nslab = nkb == 1 ? 2 * PP : PP, nblk = (cin / 64) * (kout / 64);
 #define SCL_WRW_REDUCE(RG)                                                                     \

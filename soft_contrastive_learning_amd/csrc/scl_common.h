@@ -272,7 +272,10 @@ extern SclProfSink* volatile scl_prof_sink;
 // tests select with scl_debug_set_variant).  The product library (libscl_hip.so) is compiled
 // without it: scl_variant() is the constant 0 there, every variant branch of the dispatch code
 // and every `dbg` test inside a kernel folds away, and scl_debug_set_variant rejects anything
-// but 0 — the shipped library has no process-wide switch that changes a result.
+// but 0 — the shipped library has no process-wide switch that changes a result.  Kernels and
+// launch structures that only a variant reaches live in netvlad_diag.hip, gram_loss_diag.hip and
+// conv64_diag.hip, which the diagnostic build compiles in place of their product sources; what
+// stays here are hooks that fold to 0 and one-line knobs between kernels the product launches.
 #ifdef SCL_DIAG
 extern volatile int scl_debug_variant;
 static inline int scl_variant() { return scl_debug_variant; }

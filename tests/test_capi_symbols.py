@@ -63,6 +63,17 @@ def test_product_library_has_no_variants_and_the_diagnostic_build_does(lib):
     assert 'scl_debug_variant' not in syms.replace('scl_debug_set_variant', '')
     syms = subprocess.run(['nm', '-D', so.replace('.so', '_diag.so')], capture_output=True, text=True).stdout
     assert 'scl_debug_variant' in syms.replace('scl_debug_set_variant', '')
+    # nor any kernel that only a variant launches: those live in csrc/*_diag.hip, which the
+    # diagnostic library alone compiles (the device code is stored uncompressed in both)
+    product, diagnostic = open(so, 'rb').read(), open(so.replace('.so', '_diag.so'), 'rb').read()
+    for name in (b'rowtile16_kernelIfLi0ELi1E', b'rowtile16_kernelItLi0ELi7E', b'wrw64_kernelILi2E',
+                 b'wrw64_kernelILi4E', b'wrw64_kernelILi6E', b'wrw64_kernelILi8E', b'wrw64_kernelILi16E',
+                 b'vlad_split_w_kernel', b'vlad_fwd_kernelILb1E', b'vlad_bwd_kernel', b'vlad_finish_sum_kernel',
+                 b'vlad_wgrad_partial_kernel', b'bwd_dots_kernel', b'bwd_du_kernel', b'persist_kernel',
+                 b'gram16x6_kernelILi9ELi2ELb1E', b'gram16x6_kernelILi20ELi2ELb1E',
+                 b'conv3x3_kernelILi64ELi64ELi0ELi0ELi0ELi1E'):
+        assert name not in product, name
+        assert name in diagnostic, name
 
 
 def test_abi_version_and_error_strings(lib):
