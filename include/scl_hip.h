@@ -635,6 +635,33 @@ int scl_prof_end(float* ms, const char** names, int capacity);
 int scl_prof_null(void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Dense reduction heads (csrc/dense.hip): the `tf.layers.dense` stack of --reduction 1fc|2fc|3fc
+ * (reference train/train.py:631-644, evaluation/inference.py:97-109).  Float32 in and out, exact
+ * float32 products (v_mfma_f32_32x32x2_f32), fixed-order sums only: bitwise reproducible, and the
+ * K / N split is chosen from (K, N) alone, so row m of the result does not depend on M or on the
+ * other rows.  1 <= M <= 256, K >= 1, N >= 1; row strides in elements (ld >= row width).
+ *
+ *   scl_dense_fwd       y[M,N] = x[M,K] w[K,N] (+ bias[N]; bias may be NULL), then
+ *                       max(y, 0) when relu != 0.  w in TF kernel layout [in, units].
+ *   scl_dense_bwd_data  gx[M,K] = g'[M,N] w^T, g' = gy where y > 0 (y = the layer's saved
+ *                       post-ReLU output), g' = gy when y is NULL (no activation).
+ *   scl_dense_wgrad     gw[K,N] = x^T g', gb[N] = sum_m g' (gb may be NULL).  Overwrites gw and
+ *                       gb; needs no workspace.
+ * Workspaces: scl_dense_*_workspace_bytes (0 = none needed; 0 also for a shape outside the range).
+ * ------------------------------------------------------------------------- */
+size_t scl_dense_fwd_workspace_bytes(int M, int K, int N);
+int scl_dense_fwd(const float* x, int64_t ld_x, const float* w, int64_t ld_w, const float* bias,
+                  int M, int K, int N, int relu, float* y, int64_t ld_y, void* workspace,
+                  size_t workspace_bytes, void* stream);
+size_t scl_dense_bwd_data_workspace_bytes(int M, int K, int N);
+int scl_dense_bwd_data(const float* gy, int64_t ld_gy, const float* y, int64_t ld_y,
+                       const float* w, int64_t ld_w, int M, int K, int N, float* gx, int64_t ld_gx,
+                       void* workspace, size_t workspace_bytes, void* stream);
+int scl_dense_wgrad(const float* x, int64_t ld_x, const float* gy, int64_t ld_gy, const float* y,
+                    int64_t ld_y, int M, int K, int N, float* gw, int64_t ld_gw, float* gb,
+                    void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Host utility for the checkpoint bundle reader / writer (tf_bundle.py; the reference
  * restores and saves through tf.train.Saver, train/train.py:882-905, 984, 1079, 1102):
  * CRC-32C (Castagnoli, reflected 0x82F63B78) of n bytes continued from `crc` (0 to start),

@@ -134,6 +134,11 @@ SIGNATURES = {
     "scl_prof_end": (_i, [_p, _p, _i]),
     "scl_prof_null": (_i, [_p]),
     "scl_crc32c": (ctypes.c_uint, [ctypes.c_uint, _p, _z]),
+    "scl_dense_fwd_workspace_bytes": (_z, [_i, _i, _i]),
+    "scl_dense_fwd": (_i, [_p, _l, _p, _l, _p, _i, _i, _i, _i, _p, _l, _p, _z, _p]),
+    "scl_dense_bwd_data_workspace_bytes": (_z, [_i, _i, _i]),
+    "scl_dense_bwd_data": (_i, [_p, _l, _p, _l, _p, _l, _i, _i, _i, _p, _l, _p, _z, _p]),
+    "scl_dense_wgrad": (_i, [_p, _l, _p, _l, _p, _l, _i, _i, _i, _p, _l, _p, _p]),
 }
 
 _libs = {}

@@ -39,6 +39,9 @@ def _param_table(model):
     if getattr(model, 'vlad_cores', 64) == 64:     # the vgg16() graph has no head variables
         rows.append((SCOPE + '/assignment/kernel', model.assignment_kernel, False))
         rows.append((SCOPE + '/cluster_centers', model.cluster_centers, False))
+    head = getattr(model, 'reduction_head', None)
+    if head is not None:                           # dense head: TF layout already, no prefix
+        rows.extend((name, p, False) for name, p in head.tf_variables())
     return rows
 
 
@@ -170,13 +173,15 @@ def read_variables(path):
     return sd
 
 
-def load(model, path, strict=True, optimizer=None):
+def load(model, path, strict=True, optimizer=None, head=True):
     """Restore by variable name (scope filter like restore_weights); returns global_step.
-    ``path`` is what the reference's --checkpoint flag takes: the bundle prefix (or an .npz)."""
+    ``path`` is what the reference's --checkpoint flag takes: the bundle prefix (or an .npz).
+    ``head``: also restore (and require) a dense reduction head; False leaves it as initialised."""
     sd = read_variables(path)
     step = int(np.asarray(sd.get(GLOBAL_STEP_VAR, 0)))
     model.load_state_dict_tf({k: torch.from_numpy(np.ascontiguousarray(v))
-                              for k, v in sd.items() if v.dtype.kind == 'f'}, strict=strict)
+                              for k, v in sd.items() if v.dtype.kind == 'f'}, strict=strict,
+                             head=head)
     if optimizer is not None:
         restore_optimizer(model, optimizer, sd)
     return step

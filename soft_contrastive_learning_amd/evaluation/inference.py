@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from .. import checkpoint
-from ..model import nets
+from ..model import nets, reduction
 
 
 def pad_indices(num, images_per_pass):
@@ -34,7 +34,8 @@ def pad_indices(num, images_per_pass):
 
 def extract_features(model, loader, num, images_per_pass=4, device=None, loader_threads=6):
     """Returns ``list`` of ``num`` float32 vectors (length 32768 with the NetVLAD head, H' W' 512
-    without: ``ops['full_out']``, evaluation/inference.py:89-92), in index order.  ``loader`` is
+    without: ``ops['full_out']``, evaluation/inference.py:89-92; ``out_dim`` with a dense reduction
+    head: ``ops['output']``, :97-109), in index order.  ``loader`` is
     called from ``loader_threads`` threads (cpu_thread, :28-38), one batch ahead of the device."""
     from concurrent.futures import ThreadPoolExecutor
     device = device or next(model.parameters()).device
@@ -52,7 +53,7 @@ def extract_features(model, loader, num, images_per_pass=4, device=None, loader_
             batch = pending.pop(0).result()
             if k + ahead < len(starts):
                 pending.append(pool.submit(load_batch, starts[k + ahead]))
-            out = nets.full_out(torch.from_numpy(batch).to(device), model=model)
+            out = nets.output(torch.from_numpy(batch).to(device), model=model)
             out = out.float().cpu().numpy()
             for slot, f in zip(range(s, s + len(out)), out):
                 feats[slot] = f
@@ -105,7 +106,8 @@ def main(argv=None):
     p.add_argument('--set', default='synthetic')
     p.add_argument('--checkpoint', default='')
     p.add_argument('--out_name', default='scl_amd')
-    p.add_argument('--reduction', default='none')
+    p.add_argument('--out_dim', default=512, type=int)
+    p.add_argument('--reduction', default='none', help='none, 1fc, 2fc, 3fc, pca')
     p.add_argument('--vlad_cores', default=64, type=int)
     p.add_argument('--out_root', default='./scl_lv')
     p.add_argument('--images_per_pass', type=int, default=4)
@@ -114,12 +116,17 @@ def main(argv=None):
     # --reduction pca writes the RAW descriptors, like the reference: "Don't actually do PCA
     # here - doing it after" (evaluation/inference.py:94-95; its projection branch at :111-116
     # is unreachable).  The whitening runs in evaluation/top_n.py.
-    if flags.vlad_cores not in (0, 64) or flags.reduction not in ('none', 'pca'):
-        raise SystemExit('only --vlad_cores 64 | 0 with --reduction none|pca is on the hot path')
+    if flags.vlad_cores not in (0, 64) or flags.reduction not in ('none', 'pca') + reduction.KINDS:
+        raise SystemExit('only --vlad_cores 64 | 0 with --reduction none|pca|1fc|2fc|3fc is on the hot path')
     np.random.seed(42)                                       # inference.py:270-271
     model = nets.VGG16NetVLAD(vlad_cores=flags.vlad_cores).cuda()
+    if flags.reduction in reduction.KINDS:
+        # :97-109; the input of the head without NetVLAD is the fixed small_side x large_side frame
+        # (:78-86)
+        reduction.attach(model, flags.reduction, flags.out_dim, height=flags.small_side,
+                         width=flags.large_side)
     if flags.checkpoint:
-        checkpoint.load(model, flags.checkpoint)
+        checkpoint.load(model, flags.checkpoint)     # every variable, the head included (:122-131)
     if flags.set == 'synthetic' and not flags.csv_root:
         loader, num = synthetic_loader(flags.small_side, flags.large_side), flags.num_images
     else:

@@ -1398,23 +1398,37 @@ class VGG16NetVLAD(torch.nn.Module):
         if self.vlad_cores == 64:      # the vgg16() graph creates no head variables (nets.py:72-131)
             sd[SCOPE + '/assignment/kernel'] = self.assignment_kernel.detach()
             sd[SCOPE + '/cluster_centers'] = self.cluster_centers.detach()
+        head = getattr(self, 'reduction_head', None)
+        if head is not None:           # --reduction 1fc|2fc|3fc: unscoped names (model/reduction.py)
+            for key, p in head.tf_variables():
+                sd[key] = p.detach()
         return sd
 
-    def load_state_dict_tf(self, sd, strict=True):
+    def load_state_dict_tf(self, sd, strict=True, head=True):
         """Restore by TF variable name like restore_weights (train/train.py:882-905):
-        only names containing the scope are taken."""
+        only names containing the scope are taken.  A dense reduction head (model/reduction.py)
+        is restored too when ``head`` (inference, evaluation/inference.py:122-131, and the
+        trainer's --resume); ``head=False`` leaves it as initialised, like the reference trainer's
+        --checkpoint restore."""
         own = self.state_dict_tf()
+        head_vars = dict(self.reduction_head.tf_variables()) \
+            if getattr(self, 'reduction_head', None) is not None else {}
+        if not head:
+            own = {k: v for k, v in own.items() if k not in head_vars}
         missing = [k for k in own if k not in sd]
         if strict and missing:
             raise KeyError("checkpoint lacks %s" % missing)
         with torch.no_grad():
             for key, val in sd.items():
-                if SCOPE not in key or key not in own:
+                if key not in own or (SCOPE not in key and key not in head_vars):
                     continue
                 val = torch.as_tensor(val, dtype=torch.float32)
                 if tuple(val.shape) != tuple(own[key].shape):
                     raise ValueError("%s: shape %s != %s" % (key, tuple(val.shape),
                                                              tuple(own[key].shape)))
+                if key in head_vars:
+                    head_vars[key].copy_(val)
+                    continue
                 short = key[len(SCOPE) + 1:]
                 if short == 'average_rgb':
                     self.average_rgb.copy_(val)
@@ -1472,6 +1486,16 @@ def full_out(image_batch, model=None):
         return model(image_batch)
     x = model.forward_vgg16(image_batch)
     return x.reshape(x.shape[0], -1)
+
+
+def output(image_batch, model=None):
+    """``ops['output']`` (train/train.py:615-644, evaluation/inference.py:94-109): ``full_out``, or
+    what the model's dense reduction head (``--reduction 1fc|2fc|3fc``, model/reduction.py) makes
+    of it.  What the loss, the mining features and the localisation check read."""
+    model = model or default_model()
+    out = full_out(image_batch, model)
+    head = getattr(model, 'reduction_head', None)
+    return out if head is None else head(out)
 
 
 def trainable_parameters(model):

@@ -36,7 +36,7 @@ import torch
 import torch.distributed as dist
 
 from .. import checkpoint, parallel, pointnetvlad_cls
-from ..model import losses, nets
+from ..model import losses, nets, reduction
 from .optim import make_optimizer
 
 
@@ -77,8 +77,10 @@ def make_parser():
     p.add_argument('--lr_down_frequency', type=float, default=1)
     p.add_argument('--momentum', type=float, default=0.9)
     p.add_argument('--optimizer', default='adam', help='adam, momentum')
-    # head (:1284-1289); only the NetVLAD / no-reduction path is on the hot path
-    p.add_argument('--reduction', default='none')
+    # head (:1283-1289): none, or a dense reduction head 1fc|2fc|3fc of --out_dim units
+    # (model/reduction.py); spp and the training-time pca need reference modules that do not exist
+    p.add_argument('--out_dim', default=512, type=int)
+    p.add_argument('--reduction', default='none', help='none, 1fc, 2fc, 3fc')
     p.add_argument('--vlad_cores', default=64, type=int)
     # hard negative mining (:1288-1293)
     p.add_argument('--mining_step', type=int, default=250)
@@ -161,6 +163,9 @@ def get_learning_rate(epoch, flags):
     lr = flags.base_lr * (flags.lr_down_factor ** (epoch // flags.lr_down_frequency))
     return max(lr, flags.minimal_lr)
 
+
+# reduction modes of the reference whose modules are absent from it
+UNAVAILABLE_REDUCTIONS = {'spp': 'learnlarge.model.mac', 'pca': 'learnlarge.model.incremental_skl'}
 
 SUPPORTED_LOSSES = ('triplet', 'lazy_triplet', 'evil_triplet', 'quadruplet', 'lazy_quadruplet',
                     'evil_quadruplet', 'ms_loss', 'wms', 'logratio',
@@ -396,11 +401,11 @@ def train_dataset_epoch(flags, epoch, state, log):
 
     def loss_of(distances, images):
         """Single-process loss (the evaluation on the other region: every rank alike)."""
-        out = nets.full_out(images)
+        out = nets.output(images)
         return compute_loss(flags, tuple_shape, out, batch_distances(flags, distances, dev))
 
     def train_loss(distances, images, indices):
-        out = nets.full_out(images)
+        out = nets.output(images)
         if group is None:
             return compute_loss(flags, tuple_shape, out, batch_distances(flags, distances, dev))
         if flags.loss == 'wms':
@@ -539,10 +544,29 @@ def train_dataset_epoch(flags, epoch, state, log):
         saver.save_epoch(model, epoch, state['step'], opt)           # :984
 
 
+def restore(flags, model, opt, verbose=True):
+    """--checkpoint: restore_weights (train/train.py:882-905) takes the variables of the
+    ``vgg16_netvlad_pca`` scope only, so a dense reduction head starts from its initialiser (logged
+    as 'Newly initialized: <var>', :889); --resume also restores the head and every Adam slot and
+    returns the global step.  Returns the step to continue from."""
+    if not flags.checkpoint:
+        return 0
+    got = checkpoint.load(model, flags.checkpoint, optimizer=opt if flags.resume else None,
+                          head=flags.resume)
+    head = reduction.head_of(model)
+    if not flags.resume and head is not None and verbose:
+        for name, _ in head.tf_variables():
+            print('Newly initialized: {}'.format(name))
+    return got if flags.resume else 0
+
+
 def main(argv=None):
     flags = make_parser().parse_args(argv)
-    if flags.vlad_cores not in (0, 64) or flags.reduction != 'none':
-        raise SystemExit('only --vlad_cores 64 | 0 with --reduction none is on the hot path')
+    if flags.reduction in UNAVAILABLE_REDUCTIONS:
+        raise SystemExit('--reduction %s needs %s, which the reference does not contain'
+                         % (flags.reduction, UNAVAILABLE_REDUCTIONS[flags.reduction]))
+    if flags.vlad_cores not in (0, 64) or flags.reduction not in ('none',) + reduction.KINDS:
+        raise SystemExit('only --vlad_cores 64 | 0 with --reduction none|1fc|2fc|3fc is on the hot path')
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
     local_rank = int(os.environ.get('LOCAL_RANK', '0'))
@@ -569,6 +593,8 @@ def main(argv=None):
     cdt = torch.bfloat16 if flags.dtype == 'bf16' else torch.float32
     model = nets.set_default_model(nets.VGG16NetVLAD(compute_dtype=cdt,
                                                      vlad_cores=flags.vlad_cores).to(dev))
+    if flags.reduction in reduction.KINDS:             # :631-644, float32 under --dtype bf16 too
+        reduction.attach(model, flags.reduction, flags.out_dim, height=flags.height, width=flags.width)
     params = nets.trainable_parameters(model)       # train/train.py:606-611: the head decides
     buckets = parallel.GradBuckets(params, group, force_collectives=bool(flags.force_dist))
     nets.GRAD_SINK = buckets       # conv weight / bias gradients go straight into the flat buffer
@@ -576,10 +602,7 @@ def main(argv=None):
     # correction), not torch's: train/optim.py
     opt = make_optimizer(flags.optimizer, params, flags.base_lr, flags.momentum)
     # restore_weights (:882-905) + the slot variables a tf.train.Saver checkpoint carries
-    step = 0
-    if flags.checkpoint:
-        got = checkpoint.load(model, flags.checkpoint, optimizer=opt if flags.resume else None)
-        step = got if flags.resume else 0
+    step = restore(flags, model, opt, verbose=rank == 0)
     out_dir = os.path.join(flags.out_root, flags.out_folder or flags.loss)
     saver = checkpoint.Saver(out_dir, flags.max_to_keep)
     data = SyntheticTuples(flags, tuple_shape, dev, rank, world)
@@ -638,7 +661,7 @@ def main(argv=None):
             t0 = time.time()
             distances, img = data.batch()
             buckets.zero()
-            output = nets.full_out(img)                           # ops['output'] (:606-629)
+            output = nets.output(img)                             # ops['output'] (:606-644)
             loss = compute_loss(flags, tuple_shape, output, distances, group=group)
             loss.backward()
             buckets.finish()
