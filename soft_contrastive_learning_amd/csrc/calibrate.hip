@@ -12,9 +12,6 @@
 // (random in [-1, 1): all-zero operands draw less power and over-state the ceiling).
 #include "scl_common.h"
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 namespace {
 
 template <int SHAPE>
@@ -46,9 +43,7 @@ __global__ __launch_bounds__(512, 1) void mfma_bf16_loop_kernel(const unsigned* 
         for (int j = 0; j < 4; ++j)
 #pragma unroll
           for (int n = 0; n < 2; ++n)
-            acc[2 * j + n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-                __builtin_bit_cast(bf16x8, a[j]), __builtin_bit_cast(bf16x8, b[n]),
-                acc[2 * j + n], 0, 0, 0);
+            acc[2 * j + n] = mfma32b(a[j], b[n], acc[2 * j + n]);
       }
     }
 #pragma unroll
@@ -70,9 +65,7 @@ __global__ __launch_bounds__(512, 1) void mfma_bf16_loop_kernel(const unsigned* 
       for (int j = 0; j < 8; ++j)
 #pragma unroll
         for (int n = 0; n < 4; ++n)
-          acc[4 * j + n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              __builtin_bit_cast(bf16x8, a[j]), __builtin_bit_cast(bf16x8, b[n]), acc[4 * j + n],
-              0, 0, 0);
+          acc[4 * j + n] = mfma16b(a[j], b[n], acc[4 * j + n]);
     }
 #pragma unroll
     for (int j = 0; j < 32; ++j)

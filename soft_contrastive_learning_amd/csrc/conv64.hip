@@ -18,12 +18,10 @@
 //   * epilogue: f32 accumulators -> bf16 through a per-wave LDS transpose -> 16-byte stores.
 #include <mutex>
 
+#include "conv_pack_layout.h"
 #include "scl_common.h"
 
 namespace {
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int C64 = 64;
 constexpr int TH = 8, TW = 32;                       // output tile
@@ -31,81 +29,9 @@ constexpr int WR = TH + 2, WC = TW + 2;              // halo window
 constexpr int SCR_LD = 40;                           // bf16 per scratch row (32 ch + 8 pad)
 constexpr int SCR = 32 * SCR_LD;                     // per-wave epilogue scratch (one tile row)
 
-__device__ __forceinline__ f32x16 mfma32b(u32x4 a, u32x4 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a),
-                                                 __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
+// (u32x4, mfma32b / mfma16b, the LDS-DMA forms glds16 / glds16_s / blds16 + image_rsrc, zero_block,
+// lds_byte_of and the transposed reads tr_pair / lds_tr16: scl_cdna4.h)
 
-typedef float f32x4_ __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ f32x4_ mfma16b(u32x4 a, u32x4 b, f32x4_ c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a),
-                                                 __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-typedef short s16x4_ __attribute__((ext_vector_type(4)));
-// two transposed reads (ds_read_b64_tr_b16), `step4` elements apart: 8 consecutive rows of one column
-__device__ __forceinline__ u32x4 tr_pair_early(const unsigned short* a0, int step4) {
-  const s16x4_ lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (s16x4_ __attribute__((address_space(3)))*)(a0));
-  const s16x4_ hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (s16x4_ __attribute__((address_space(3)))*)(a0 + step4));
-  const uint2 l2 = __builtin_bit_cast(uint2, lo), h2 = __builtin_bit_cast(uint2, hi);
-  return u32x4{l2.x, l2.y, h2.x, h2.y};
-}
-
-// LDS-DMA staging (global_load_lds_dwordx4): one wave-instruction copies 64 x 16 bytes from
-// per-lane global addresses to 1 KB of CONSECUTIVE LDS — no staging registers, no ds_write
-// pass, many more bytes in flight per CU.  Out-of-image halo pixels read a zero block.
-__device__ uint4 zero_block[4];                      // never written: zeros
-
-// Issued as inline asm so that hipcc does not order it against the LDS reads of the OTHER
-// buffer (with the builtin it waits vmcnt(0) before the next ds_read: no overlap at all);
-// the kernel waits vmcnt(0) itself before the barrier that hands the buffer over.
-// lds_byte: wave-uniform LDS byte address of the 1-KB chunk; src: this lane's 16 bytes.
-__device__ __forceinline__ void glds16(const unsigned short* src, unsigned lds_byte) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(src), "s"(lds_byte)
-      : "memory");
-}
-__device__ __forceinline__ unsigned lds_byte_of(const unsigned short* p) {
-  return (unsigned)(size_t)(const __attribute__((address_space(3))) unsigned short*)p;
-}
-// ... with a wave-uniform base pointer and a 32-bit byte offset per lane: no vector instruction
-// for the address at all
-__device__ __forceinline__ void glds16_s(const unsigned short* base, unsigned off_bytes,
-                                         unsigned lds_byte) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(off_bytes), "s"(base), "s"(lds_byte)
-      : "memory");
-}
-// LDS-DMA through a BUFFER RESOURCE (buffer_load_dwordx4 ... offen lds): the same 1-KB copy, with
-// the hardware's bounds check on every lane's byte offset — an offset at or beyond num_records,
-// or a negative one (it wraps to > 2^31), delivers ZEROS (scripts/buffer_lds_probe.hip).  With one
-// resource per image the rows of a halo window that lie above or below the image need no per-lane
-// test, no zero block and no select: one v_add per chunk instead of ~11 vector instructions.
-// rsrc: {base lo, base hi (stride 0), num_records in bytes, 0x00020000}, wave-uniform.
-__device__ __forceinline__ void blds16(u32x4 rsrc, unsigned voff_bytes, unsigned lds_byte) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(voff_bytes), "s"(rsrc), "s"(lds_byte)
-      : "memory");
-}
-__device__ __forceinline__ u32x4 image_rsrc(const unsigned short* base, int64_t first_elem, unsigned bytes) {
-  const unsigned long long a = (unsigned long long)(base + first_elem);
-  return u32x4{(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)a),
-               (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)(a >> 32) & 0xffffu)),
-               (unsigned)__builtin_amdgcn_readfirstlane((int)bytes), 0x00020000u};
-}
 // Round 5: wrw64_kernel takes the buffer path for tiles whose window columns lie inside the image
 // (DBG & 8 = the round-4 staging, for A/B in the diagnostic build).
 constexpr bool kWrwBufPath = true;
@@ -147,9 +73,7 @@ struct ConvCfg {
       (2 * (size_t)WIN_ + WAVES * (size_t)SCR) * sizeof(unsigned short);
 };
 
-// Weights -> register image [nt][ks][lane 64][8 bf16].
-//   transposed = 0 (forward):       B[c][k] = w[k][c][kh][kw]
-//   transposed = 1 (backward-data): B[k][c] = w[k][c][2-kh][2-kw]  (contraction over k)
+// Weights -> register image (pack_reg_coord, conv_pack_layout.h; forward / transposed: pack_src_offset).
 // w is addressed through its element strides (OIHW logical, any memory format); flags =
 // SCL_CONV_TRANSPOSED | SCL_W_F32 (include/scl_hip.h).
 template <int CIN, int KOUT>
@@ -161,16 +85,7 @@ __global__ __launch_bounds__(256) void conv3x3_pack_kernel(const void* __restric
   const int transposed = flags & 1, wf32 = flags & 2;
   const int idx = blockIdx.x * 256 + threadIdx.x;      // over NT * KS * 64 * 8
   if (idx >= Cfg::NT * Cfg::KS * 512) return;
-  const int e = idx & 7, lane = (idx >> 3) & 63, ks = (idx >> 9) % Cfg::KS, nt = idx / (Cfg::KS * 512);
-  const int j = lane & 31, h = lane >> 5;
-  const int tap = ks / Cfg::SPT, kh = tap / 3, kw = tap % 3;
-  const int cin = 16 * (ks % Cfg::SPT) + 8 * h + e;    // contraction index
-  const int cout = 32 * nt + j;                        // output channel of this pass
-  int64_t off;
-  if (!transposed)
-    off = cout * sk + cin * sc + kh * sh + kw * sw;
-  else
-    off = cin * sk + cout * sc + (2 - kh) * sh + (2 - kw) * sw;
+  const int64_t off = pack_src_offset(pack_reg_coord(idx, CIN), sk, sc, sh, sw, transposed);
   packed[idx] = weight_bf16(w, off, wf32);
 }
 
@@ -380,7 +295,7 @@ __global__ __launch_bounds__((ConvCfg<CIN, KOUT, GEO>::NTHR), (GEO ? 2 : 1)) voi
   if (FW) {
 #pragma unroll
     for (int v = 0; v < 4; ++v)
-      *reinterpret_cast<f32x4_*>(dwl + wid * 1024 + v * 256 + lane * 4) = f32x4_{0.f, 0.f, 0.f, 0.f};
+      *reinterpret_cast<f32x4*>(dwl + wid * 1024 + v * 256 + lane * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
     if (tile < ntiles) {
       xwin_load(tile);
       xwin_store(0);
@@ -596,21 +511,21 @@ __global__ __launch_bounds__((ConvCfg<CIN, KOUT, GEO>::NTHR), (GEO ? 2 : 1)) voi
       f32x16 dacc;
 #pragma unroll
       for (int v = 0; v < 4; ++v) {
-        const f32x4_ t = *reinterpret_cast<const f32x4_*>(dwl + wid2 * 1024 + v * 256 + lane2 * 4);
+        const f32x4 t = *reinterpret_cast<const f32x4*>(dwl + wid2 * 1024 + v * 256 + lane2 * 4);
 #pragma unroll
         for (int j = 0; j < 4; ++j) dacc[4 * v + j] = t[j];
       }
 #pragma unroll
       for (int u = 0; u < ((dbg & 16) ? 0 : 4); ++u) {
         const int s_ = 4 * pq + u;                                   // 16 pixels: row s_ / 2, half s_ & 1
-        const u32x4 a = tr_pair_early(ga + s_ * 16 * FWPL, 4 * FWPL);
+        const u32x4 a = tr_pair(ga + s_ * 16 * FWPL, 4 * FWPL);
         const u32x4 bfr = *reinterpret_cast<const u32x4*>(imc + (s_ * 32 + r2) * 16 + 8 * h2);
         dacc = mfma32b(a, bfr, dacc);
       }
 #pragma unroll
       for (int v = 0; v < 4; ++v)
-        *reinterpret_cast<f32x4_*>(dwl + wid2 * 1024 + v * 256 + lane2 * 4) =
-            f32x4_{dacc[4 * v], dacc[4 * v + 1], dacc[4 * v + 2], dacc[4 * v + 3]};
+        *reinterpret_cast<f32x4*>(dwl + wid2 * 1024 + v * 256 + lane2 * 4) =
+            f32x4{dacc[4 * v], dacc[4 * v + 1], dacc[4 * v + 2], dacc[4 * v + 3]};
       if (next < ntiles) xwin_store(xpar ^ 1);
       xpar ^= 1;
       FW_STAMP(8);
@@ -673,7 +588,7 @@ __global__ __launch_bounds__((ConvCfg<CIN, KOUT, GEO>::NTHR), (GEO ? 2 : 1)) voi
     const int mt_ = wid & 1, pq = wid >> 1;
 #pragma unroll
     for (int v = 0; v < 4; ++v) {
-      const f32x4_ t = *reinterpret_cast<const f32x4_*>(dwl + wid * 1024 + v * 256 + lane * 4);
+      const f32x4 t = *reinterpret_cast<const f32x4*>(dwl + wid * 1024 + v * 256 + lane * 4);
 #pragma unroll
       for (int j = 0; j < 4; ++j) red[(pq * 64 + 32 * mt_ + acc_row(4 * v + j, h)) * 32 + r] = t[j];
     }
@@ -711,18 +626,6 @@ __global__ __launch_bounds__((ConvCfg<CIN, KOUT, GEO>::NTHR), (GEO ? 2 : 1)) voi
 constexpr int WPL = 32;                              // bf16 per pixel and plane
 constexpr int GPLANE = TH * TW * WPL;                // one 32-channel plane of a 256-pixel gz tile
                                                      // (conv_first_wrw_kernel; wrw64: WrwCfg)
-
-
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ u32x4 tr_pair(const unsigned short* a0, int step4) {
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (s16x4 __attribute__((address_space(3)))*)(a0));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (s16x4 __attribute__((address_space(3)))*)(a0 + step4));
-  const uint2 l2 = __builtin_bit_cast(uint2, lo), h2 = __builtin_bit_cast(uint2, hi);
-  return u32x4{l2.x, l2.y, h2.x, h2.y};
-}
 
 // grid (pixel splits P, C / 64, K / 64): workgroup (p, cb, kb) accumulates the [9][64][64]
 // block (input channels 64 cb .., output channels 64 kb ..) over the tiles p, p + P, ...
@@ -983,12 +886,9 @@ __global__ __launch_bounds__(512, 1) void wrw64_kernel(const unsigned short* __r
     auto x_frag = [&](int wrow, int cx) {
       const unsigned short* p = xl + (wrow * WCv + cx) * WPL;
       XFrag f;
-      f.lo = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                                           (s16x4 __attribute__((address_space(3)))*)(p)));
-      f.hi = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                                           (s16x4 __attribute__((address_space(3)))*)(p + 4 * WPL)));
-      f.ex = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                                           (s16x4 __attribute__((address_space(3)))*)(p + 8 * WPL)));
+      f.lo = __builtin_bit_cast(uint2, lds_tr16(p));
+      f.hi = __builtin_bit_cast(uint2, lds_tr16(p + 4 * WPL));
+      f.ex = __builtin_bit_cast(uint2, lds_tr16(p + 8 * WPL));
       return f;
     };
     // window row (relative to the wave's first) and column slot of step s_, tap row kh
@@ -1039,8 +939,8 @@ __global__ __launch_bounds__(512, 1) void wrw64_kernel(const unsigned short* __r
         // registers on v_mfma_f32_16x16x32_bf16 — what would the other MFMA shape be worth here?
         f32x16& c_ = acc[i % 9];
         const int o_ = 8 * (i & 1);
-        f32x4_ q0 = {c_[o_], c_[o_ + 1], c_[o_ + 2], c_[o_ + 3]};
-        f32x4_ q1 = {c_[o_ + 4], c_[o_ + 5], c_[o_ + 6], c_[o_ + 7]};
+        f32x4 q0 = {c_[o_], c_[o_ + 1], c_[o_ + 2], c_[o_ + 3]};
+        f32x4 q1 = {c_[o_ + 4], c_[o_ + 5], c_[o_ + 6], c_[o_ + 7]};
         q0 = mfma16b(a, bf[s_ & 1], q0);
         q1 = mfma16b(a, bf[s_ & 1], q1);
         c_[o_] = q0[0]; c_[o_ + 1] = q0[1]; c_[o_ + 2] = q0[2]; c_[o_ + 3] = q0[3];
@@ -1880,6 +1780,7 @@ int launch_conv3x3(const void* x, const void* w, int64_t sk, int64_t sc, int64_t
                    void* pooled, const void* mask, void* pidx, const void* uidx, void* workspace,
                    hipStream_t st) {
   using Cfg = ConvCfg<CIN, KOUT, GEO>;
+  static_assert(pack_reg_shape(CIN, KOUT), "the shapes that scl_conv_pack_batch gives the register image");
   static SclDeviceOnce once;
   scl_call_once(once, [] {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_kernel<CIN, KOUT, 0, 0, 0, GEO>),

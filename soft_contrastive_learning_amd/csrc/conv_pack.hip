@@ -5,15 +5,16 @@
 // convh.hip): 24 launches of 4-10 us per training step, each with a kernel boundary on either
 // side, on the critical path.  The weights change once per step, so the caller can have all the
 // images written up front by scl_conv_pack_batch — one launch — and hand them to the
-// convolutions with SCL_W_PACKED.  The two layouts are restated here; the parity tests compare
-// a convolution fed this way with the same convolution packing for itself, bit for bit.
+// convolutions with SCL_W_PACKED.  Both layouts come from conv_pack_layout.h, the same index maps
+// those packers write through; the parity tests compare a convolution fed this way with the same
+// convolution packing for itself, bit for bit.
+#include "conv_pack_layout.h"
 #include "scl_common.h"
 #include "vlad_planes.h"
 
 namespace {
 
 constexpr int kMaxJobs = 32;
-typedef unsigned u32x4s __attribute__((ext_vector_type(4)));
 
 struct PackJobs {
   const void* w[kMaxJobs];
@@ -39,34 +40,9 @@ __global__ __launch_bounds__(256) void conv_pack_batch_kernel(const PackJobs job
   const int transposed = flags & 1, wf32 = flags & 2;
   const int64_t total = (int64_t)9 * cin * kout;
   if (idx >= total) return;
-  int ci, co, kh, kw;
-  if (flags & 8) {
-    // conv64.hip: [n-tile kout / 32][k-step 9 * cin / 16][lane 64][8]; lane (j, h): output
-    // channel 32 nt + j, contraction index 16 (ks % SPT) + 8 h + e of tap ks / SPT
-    const int spt = cin / 16, ks_n = 9 * spt;
-    const int e = idx & 7, lane = (idx >> 3) & 63, ks = (int)((idx >> 9) % ks_n);
-    const int nt = (int)(idx / ((int64_t)ks_n * 512));
-    const int tap = ks / spt;
-    kh = tap / 3;
-    kw = tap % 3;
-    ci = 16 * (ks % spt) + 8 * (lane >> 5) + e;
-    co = 32 * nt + (lane & 31);
-  } else {
-    // convh.hip: [n-block kout / 128][chunk cin / 32][tap 9][piece 4][k 128][8]
-    const int e = idx & 7, k = (idx >> 3) & 127, g = (idx >> 10) & 3;
-    const int64_t rest = idx >> 12;
-    const int tap = rest % 9, cc_n = cin / 32;
-    const int cc = (rest / 9) % cc_n, nb = rest / 9 / cc_n;
-    kh = tap / 3;
-    kw = tap % 3;
-    ci = 32 * cc + 8 * g + e;
-    co = 128 * nb + k;
-  }
-  int64_t off;
-  if (!transposed)
-    off = co * jobs.sk[job] + ci * jobs.sc[job] + kh * jobs.sh[job] + kw * jobs.sw[job];
-  else
-    off = ci * jobs.sk[job] + co * jobs.sc[job] + (2 - kh) * jobs.sh[job] + (2 - kw) * jobs.sw[job];
+  const PackCoord c = (flags & 8) ? pack_reg_coord(idx, cin) : pack_lds_coord(idx, cin);
+  const int64_t off =
+      pack_src_offset(c, jobs.sk[job], jobs.sc[job], jobs.sh[job], jobs.sw[job], transposed);
   jobs.packed[job][idx] = weight_bf16(jobs.w[job], off, wf32);
 }
 
@@ -89,8 +65,7 @@ __global__ __launch_bounds__(256) void conv_pack_tiled_kernel(const PackJobs job
     return;
   }
   const int transposed = flags & 1, wf32 = flags & 2;
-  const int cibn = cin / 32;
-  const int cob = t / cibn, cib = t % cibn;
+  const int cob = t / (cin / 32), cib = t % (cin / 32);
   // source rows: forward: output channel co (row stride sk), 288 = (ci, tap) contiguous from
   // ci0 * 9; transposed: contraction channel ci = source k (row stride sk), 288 = (co, tap)
   const int64_t sk = jobs.sk[job];
@@ -99,7 +74,7 @@ __global__ __launch_bounds__(256) void conv_pack_tiled_kernel(const PackJobs job
     const int row = e / 288, col = e - row * 288;
     const unsigned short v = weight_bf16(jobs.w[job], (row0 + row) * sk + col0 + col, wf32);
     const int inner = col / 9, tap = col - inner * 9;
-    if (!transposed)
+    if (!transposed)                                  // pack_src_offset, read off a contiguous row:
       tile[tap][row][inner] = v;                      // row = co, inner = ci
     else
       tile[8 - tap][inner][row] = v;                  // row = ci, inner = co; taps flipped
@@ -108,29 +83,18 @@ __global__ __launch_bounds__(256) void conv_pack_tiled_kernel(const PackJobs job
   unsigned short* packed = jobs.packed[job];
   for (int u = threadIdx.x; u < 9 * 4 * 32; u += 256) {
     const int kl = u & 31, g = (u >> 5) & 3, tap = u >> 7;       // co_local, 8-channel piece
-    const u32x4s v = *reinterpret_cast<const u32x4s*>(&tile[tap][kl][8 * g]);
-    int64_t idx;
-    if (flags & 8) {
-      // conv64.hip: ((nt * KS + ks) * 64 + lane) * 8, ks = tap * SPT + ci / 16, lane = co % 32 + 32 h
-      const int spt = cin / 16, ks = tap * spt + 2 * cib + (g >> 1);
-      idx = (((int64_t)cob * 9 * spt + ks) * 64 + kl + 32 * (g & 1)) * 8;
-    } else {
-      // convh.hip: ((nb * CC + cc) * 9 + tap) * 4096 + (g * 128 + k) * 8
-      const int co = 32 * cob + kl;
-      idx = (((int64_t)(co >> 7) * cibn + cib) * 9 + tap) * 4096 + (g * 128 + (co & 127)) * 8;
-    }
-    *reinterpret_cast<u32x4s*>(packed + idx) = v;
+    const u32x4 v = *reinterpret_cast<const u32x4*>(&tile[tap][kl][8 * g]);
+    const int co = 32 * cob + kl, piece = 4 * cib + g;
+    const int64_t idx = (flags & 8) ? pack_reg_index(co, piece, tap, cin)
+                                    : pack_lds_index(co, piece, tap, cin);
+    *reinterpret_cast<u32x4*>(packed + idx) = v;
   }
-}
-
-inline bool reg_shape(int cin, int kout) {
-  return (cin == 64 || cin == 128) && (kout == 64 || kout == 128);
 }
 
 }  // namespace
 
 extern "C" size_t scl_conv_packed_bytes(int cin, int kout) {
-  if (reg_shape(cin, kout)) return scl_round256((size_t)9 * cin * kout * sizeof(unsigned short));
+  if (pack_reg_shape(cin, kout)) return scl_round256((size_t)9 * cin * kout * sizeof(unsigned short));
   if (cin < 64 || kout < 128 || cin % 64 || kout % 128 || cin > 1024 || kout > 1024) return 0;
   return scl_round256((size_t)9 * cin * kout * sizeof(unsigned short));
 }
@@ -160,7 +124,7 @@ extern "C" int scl_conv_pack_batch(const SclPackJob* jobs, int njobs, void* stre
       pj.sc[i] = j.w_stride_c;
       pj.sh[i] = j.w_stride_h;
       pj.sw[i] = j.w_stride_w;
-      pj.flags[i] = vlad ? j.flags : (j.flags | (reg_shape(j.cin, j.kout) ? 8 : 0));
+      pj.flags[i] = vlad ? j.flags : (j.flags | (pack_reg_shape(j.cin, j.kout) ? 8 : 0));
       pj.cin[i] = j.cin;
       pj.kout[i] = j.kout;
       pj.first_block[i] = blocks;

@@ -18,12 +18,10 @@
 //   * epilogue as conv64.hip: bf16 through a per-wave LDS transpose, optional bias (+ ReLU).
 #include <mutex>
 
+#include "conv_pack_layout.h"
 #include "scl_common.h"
 
 namespace {
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int BW = 40;                              // output block width (block height: GCfg)
 constexpr int GWC = BW + 4;                         // halo window: 42 columns used, 44 staged —
@@ -71,14 +69,9 @@ __device__ __forceinline__ int tile_col(int l) {
   return l < 4 ? l : l < 12 ? l - 4 : l < 16 ? l - 8 : l < 20 ? l - 16 : l < 28 ? l - 20 : l - 24;
 }
 
-__device__ __forceinline__ f32x16 mfma32b(u32x4 a, u32x4 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a),
-                                                 __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-
 // Weights -> [n-block][chunk][tap][k 128][c 32 + 8 pad] bf16: the exact LDS image of a step
 // (10 KB slices in the order the kernel stages them, copied by LDS-DMA as they are).
-// transposed as in conv64.hip.
+// Forward / transposed: pack_src_offset (conv_pack_layout.h).
 __global__ __launch_bounds__(256) void convg_pack_kernel(const void* __restrict__ w,
                                                          int64_t sk, int64_t sc, int64_t sh,
                                                          int64_t sw, int flags, int cin,
@@ -92,37 +85,15 @@ __global__ __launch_bounds__(256) void convg_pack_kernel(const void* __restrict_
   const int64_t rest = idx / (GPIX * 128);           // (nb * CC + cc) * 9 + tap
   const int tap = rest % 9;
   const int cc = (rest / 9) % (cin / CCH), nb = rest / 9 / (cin / CCH);
-  const int kh = tap / 3, kw = tap % 3;
-  const int ci = CCH * cc + c, co = NB * nb + k;
   if (c >= CCH) {
     packed[idx] = 0;
     return;
   }
-  int64_t off;
-  if (!transposed)
-    off = co * sk + ci * sc + kh * sh + kw * sw;
-  else
-    off = ci * sk + co * sc + (2 - kh) * sh + (2 - kw) * sw;
+  const int64_t off = pack_src_offset(PackCoord{NB * nb + k, CCH * cc + c, tap}, sk, sc, sh, sw, transposed);
   packed[idx] = weight_bf16(w, off, wf32);
 }
 
-__device__ uint4 zero_block[4];                      // never written: zeros
-
-// LDS-DMA (see conv64.hip): 64 lanes x 16 bytes from per-lane global addresses into 1 KB of
-// consecutive LDS at the wave-uniform byte address lds_byte.  Inline asm, so hipcc does not
-// order it against LDS reads of the other buffer; the kernel counts vmcnt itself.
-__device__ __forceinline__ void glds16(const unsigned short* src, unsigned lds_byte) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(src), "s"(lds_byte)
-      : "memory");
-}
-__device__ __forceinline__ unsigned lds_byte_of(const unsigned short* p) {
-  return (unsigned)(size_t)(const __attribute__((address_space(3))) unsigned short*)p;
-}
+// Staging is LDS-DMA (glds16, scl_cdna4.h); the kernel counts vmcnt itself.
 constexpr int WCHK = TPB * GWT * 2 / 1024;           // chunks per weight step group (30)
 
 // grid (pixel blocks, kout / 128); block 512.  EPI: 0 plain, 1 + bias (+ ReLU),

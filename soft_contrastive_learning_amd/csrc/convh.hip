@@ -30,12 +30,10 @@
 //   * LDS: 2 x 40 KB windows + 3 x 24 KB weights = 152 KB (12-row blocks).
 #include <mutex>
 
+#include "conv_pack_layout.h"
 #include "scl_common.h"
 
 namespace {
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int HBW = 40;                      // output block width
 constexpr int HWC = HBW + 2;                 // window columns
@@ -81,13 +79,8 @@ struct HConst {
 __device__ __forceinline__ int ht_row(int i) { return (i >= 4 && i < 12) ? 1 : 0; }
 __device__ __forceinline__ int ht_col(int i) { return i < 4 ? i : i < 8 ? i - 4 : i < 12 ? i - 4 : i - 8; }
 
-__device__ __forceinline__ f32x4 mfma16h(u32x4 a, u32x4 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a),
-                                                 __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-
-// Weights -> [n-block][chunk][tap][piece g][k 128][8 channels] bf16: the LDS image of a step
-// (8 KB), three consecutive steps = one group, copied by LDS-DMA as they lie.
+// Weights -> LDS image (pack_lds_coord, conv_pack_layout.h): [n-block][chunk][tap][piece g][k 128]
+// [8 channels] bf16, 8 KB per step, three consecutive steps = one group, copied by LDS-DMA as they lie.
 __global__ __launch_bounds__(256) void convh_pack_kernel(const void* __restrict__ w, int64_t sk,
                                                          int64_t sc, int64_t sh, int64_t sw,
                                                          int flags, int cin, int kout,
@@ -96,33 +89,8 @@ __global__ __launch_bounds__(256) void convh_pack_kernel(const void* __restrict_
   const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t total = (int64_t)9 * (cin / HCCH) * kout * HCCH;
   if (idx >= total) return;
-  const int e = idx & 7, k = (idx >> 3) & 127, g = (idx >> 10) & 3;
-  const int64_t rest = idx >> 12;                      // (nb * CC + cc) * 9 + tap
-  const int tap = rest % 9;
-  const int cc = (rest / 9) % (cin / HCCH), nb = rest / 9 / (cin / HCCH);
-  const int kh = tap / 3, kw = tap % 3;
-  const int ci = HCCH * cc + 8 * g + e, co = HNB * nb + k;
-  int64_t off;
-  if (!transposed)
-    off = co * sk + ci * sc + kh * sh + kw * sw;
-  else
-    off = ci * sk + co * sc + (2 - kh) * sh + (2 - kw) * sw;
+  const int64_t off = pack_src_offset(pack_lds_coord(idx, cin), sk, sc, sh, sw, transposed);
   packed[idx] = weight_bf16(w, off, wf32);
-}
-
-__device__ uint4 h_zero_block[4];                      // never written: zeros
-
-__device__ __forceinline__ void hglds16(const unsigned short* src, unsigned lds_byte) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(src), "s"(lds_byte)
-      : "memory");
-}
-__device__ __forceinline__ unsigned h_lds_byte_of(const unsigned short* p) {
-  return (unsigned)(size_t)(const __attribute__((address_space(3))) unsigned short*)p;
 }
 
 // grid: persistent workgroups over `vblocks` virtual blocks; block 512.  EPI as convg_kernel:
@@ -167,7 +135,7 @@ __global__ __launch_bounds__(HTHR, 1) void convh_kernel(const unsigned short* __
   const int kb = kout / HNB;
   const int blocks_x = (W + HBW - 1) / HBW, blocks_y = (H + BH - 1) / BH;
   const int CC = cin / HCCH, S = 9 * CC;                 // CC is even (host check)
-  const unsigned short* zeros = reinterpret_cast<const unsigned short*>(h_zero_block);
+  const unsigned short* zeros = reinterpret_cast<const unsigned short*>(zero_block);
   int nb = 0, b = 0, y0 = 0, x0 = 0;
   // LDS slot 64 (wid + 8 n) + lane of a window = piece `slot & 3` of pixel `slot >> 2`, filled
   // with the pixel's piece (slot & 3) ^ f(row, col).  One packed register per chunk —
@@ -203,26 +171,26 @@ __global__ __launch_bounds__(HTHR, 1) void convh_kernel(const unsigned short* __
     return true;
   };
   auto issue_win = [&](int cc, int buf, int n0, int n1) {
-    const unsigned base = h_lds_byte_of(win) + buf * WIN * 2;
+    const unsigned base = lds_byte_of(win) + buf * WIN * 2;
 #pragma unroll
     for (int n = 0; n < NI; ++n)
       if (n >= n0 && n < n1)
-        hglds16(woff[n] >= 0 ? x + woff[n] + HCCH * cc : zeros, base + (wid + 8 * n) * 1024);
+        glds16(woff[n] >= 0 ? x + woff[n] + HCCH * cc : zeros, base + (wid + 8 * n) * 1024);
   };
   auto issue_wts = [&](int grp, int buf) {              // three steps = 24 chunks, 3 per wave
     const unsigned short* src = packed + ((int64_t)nb * S + HTPB * grp) * HWT + lane * 8;
-    const unsigned base = h_lds_byte_of(wts) + buf * HTPB * HWT * 2;
+    const unsigned base = lds_byte_of(wts) + buf * HTPB * HWT * 2;
 #pragma unroll
     for (int n = 0; n < 3; ++n) {
       const int j = wid + 8 * n;
-      hglds16(src + j * 512, base + j * 1024);
+      glds16(src + j * 512, base + j * 1024);
     }
   };
   auto issue_wts_one = [&](int grp, int buf, int n) {   // one of a wave's three chunks of a group
     const unsigned short* src = packed + ((int64_t)nb * S + HTPB * grp) * HWT + lane * 8;
-    const unsigned base = h_lds_byte_of(wts) + buf * HTPB * HWT * 2;
+    const unsigned base = lds_byte_of(wts) + buf * HTPB * HWT * 2;
     const int j = wid + 8 * n;
-    hglds16(src + j * 512, base + j * 1024);
+    glds16(src + j * 512, base + j * 1024);
   };
   auto stage_first = [&]() {                            // a tile's first two groups and window
     issue_wts(0, 0);
@@ -347,8 +315,8 @@ __global__ __launch_bounds__(HTHR, 1) void convh_kernel(const unsigned short* __
 #pragma unroll
           for (int n = 0; n < NT; ++n)
             acc[MH * mh + j][n] =
-                EPI == 3 ? mfma16h(af[(h + APAR) & 1][j], bf[(t + PAR) & 1][n], acc[MH * mh + j][n])
-                         : mfma16h(bf[(t + PAR) & 1][n], af[(h + APAR) & 1][j], acc[MH * mh + j][n]);
+                EPI == 3 ? mfma16b(af[(h + APAR) & 1][j], bf[(t + PAR) & 1][n], acc[MH * mh + j][n])
+                         : mfma16b(bf[(t + PAR) & 1][n], af[(h + APAR) & 1][j], acc[MH * mh + j][n]);
           if (after_barrier) {
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -543,7 +511,6 @@ __global__ __launch_bounds__(HTHR, 1) void convh_kernel(const unsigned short* __
         __builtin_amdgcn_wave_barrier();
       }
     } else {
-      typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
       unsigned short* out_tile = out + tile_off;
 #pragma unroll
       for (int j = 0; j < MT; ++j) {

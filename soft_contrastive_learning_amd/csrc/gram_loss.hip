@@ -596,10 +596,6 @@ __global__ __launch_bounds__(256) void sqdist_finish_kernel(const float* __restr
 constexpr int kFastB = 256;
 constexpr int kG16 = 16;
 
-__device__ __forceinline__ f32x4 mfma16f(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
 struct Gram16Plan {
   int T;        // 16-row tiles
   int P;        // tile pairs (upper triangle)
@@ -796,7 +792,7 @@ __device__ __forceinline__ void gram16_body(const float* __restrict__ emb, int64
         const f32x4 a_n = *reinterpret_cast<const f32x4*>(cn + 16 * ti_n * LD);
         const f32x4 b_n = *reinterpret_cast<const f32x4*>(cn + 16 * tj_n * LD);
 #pragma unroll
-        for (int c = 0; c < 4; ++c) acc[lp] = mfma16f(a[c], b[c], acc[lp]);
+        for (int c = 0; c < 4; ++c) acc[lp] = mfma16(a[c], b[c], acc[lp]);
         a = a_n;
         b = b_n;
         ti = ti_n;
@@ -931,13 +927,6 @@ __device__ __forceinline__ void split3_bf16x(float x, unsigned& h1, unsigned& h2
   h2 = b;
   h3 = f32_to_bf16(r1 - bf16_to_f32(b));
 }
-typedef unsigned gx_u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 gx_bf16x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ f32x4 mfma16bf(gx_u32x4 a, gx_u32x4 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(gx_bf16x8, a),
-                                                 __builtin_bit_cast(gx_bf16x8, b), c, 0, 0, 0);
-}
-
 // DUAL: two accumulation chains per pair (needs 2 x 4 x PWMAX accumulator registers)
 template <int PWMAX, int NSUB, bool DUAL>   // pairs per wave (max), 64-column passes per workgroup
 __global__ __launch_bounds__(256) void gram16x6_kernel(const float* __restrict__ emb, int64_t ld,
@@ -974,7 +963,7 @@ __global__ __launch_bounds__(256) void gram16x6_kernel(const float* __restrict__
   for (int lp = 0; lp < PWMAX; ++lp) acc[lp] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int lp = 0; lp < (DUAL ? PWMAX : 1); ++lp) acc2[lp] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const gx_u32x4* img = reinterpret_cast<const gx_u32x4*>(x6_lds);
+  const u32x4* img = reinterpret_cast<const u32x4*>(x6_lds);
 
 #pragma unroll
   for (int sb = 0; sb < NSUB; ++sb) {
@@ -1003,9 +992,9 @@ __global__ __launch_bounds__(256) void gram16x6_kernel(const float* __restrict__
     __syncthreads();
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-      const gx_u32x4* fb = img + (4 * ks + g) * (Bp + 1) + i;   // + plane * 8 * (Bp + 1) + 16 * tile
+      const u32x4* fb = img + (4 * ks + g) * (Bp + 1) + i;   // + plane * 8 * (Bp + 1) + 16 * tile
       int ti = ti0, tj = tj0;
-      gx_u32x4 a[3], b[3];
+      u32x4 a[3], b[3];
 #pragma unroll
       for (int pl = 0; pl < 3; ++pl) {
         a[pl] = fb[pl * 8 * (Bp + 1) + 16 * ti];
@@ -1019,7 +1008,7 @@ __global__ __launch_bounds__(256) void gram16x6_kernel(const float* __restrict__
             ti_n = ti + 1 < T ? ti + 1 : ti;
             tj_n = ti_n;
           }
-          gx_u32x4 a_n[3], b_n[3];
+          u32x4 a_n[3], b_n[3];
 #pragma unroll
           for (int pl = 0; pl < 3; ++pl) {
             b_n[pl] = fb[pl * 8 * (Bp + 1) + 16 * tj_n];
@@ -1028,22 +1017,22 @@ __global__ __launch_bounds__(256) void gram16x6_kernel(const float* __restrict__
           __builtin_amdgcn_sched_barrier(0);     // next pair's reads fly under these MFMAs
           if constexpr (DUAL) {
             f32x4 c = acc[lp], c2 = acc2[lp];
-            c2 = mfma16bf(a[2], b[0], c2);         // chain 2: the small terms
-            c = mfma16bf(a[1], b[0], c);
-            c2 = mfma16bf(a[0], b[2], c2);
-            c = mfma16bf(a[0], b[1], c);
-            c2 = mfma16bf(a[1], b[1], c2);
-            c = mfma16bf(a[0], b[0], c);
+            c2 = mfma16b(a[2], b[0], c2);         // chain 2: the small terms
+            c = mfma16b(a[1], b[0], c);
+            c2 = mfma16b(a[0], b[2], c2);
+            c = mfma16b(a[0], b[1], c);
+            c2 = mfma16b(a[1], b[1], c2);
+            c = mfma16b(a[0], b[0], c);
             acc[lp] = c;
             acc2[lp] = c2;
           } else {
             f32x4 c = acc[lp];
-            c = mfma16bf(a[2], b[0], c);
-            c = mfma16bf(a[0], b[2], c);
-            c = mfma16bf(a[1], b[1], c);
-            c = mfma16bf(a[1], b[0], c);
-            c = mfma16bf(a[0], b[1], c);
-            c = mfma16bf(a[0], b[0], c);
+            c = mfma16b(a[2], b[0], c);
+            c = mfma16b(a[0], b[2], c);
+            c = mfma16b(a[1], b[1], c);
+            c = mfma16b(a[1], b[0], c);
+            c = mfma16b(a[0], b[1], c);
+            c = mfma16b(a[0], b[0], c);
             acc[lp] = c;
           }
 #pragma unroll
@@ -1614,22 +1603,22 @@ __global__ __launch_bounds__(256) void gram_bwd32_kernel(const float* __restrict
 // DUAL as gram16x6_kernel (two accumulation chains per pair; the host picks it by the same rule).
 // SMAX: steps per wave (T <= 12: 11; T = 13: 13).  SC1: write-through slab stores.
 template <bool DUAL>
-__device__ __forceinline__ void x6_pair_mfmas(const gx_u32x4 (&A)[3], const gx_u32x4 (&Bf)[3], f32x4& c,
+__device__ __forceinline__ void x6_pair_mfmas(const u32x4 (&A)[3], const u32x4 (&Bf)[3], f32x4& c,
                                               f32x4& c2) {
   if constexpr (DUAL) {
-    c2 = mfma16bf(A[2], Bf[0], c2);         // chain 2: the small terms
-    c = mfma16bf(A[1], Bf[0], c);
-    c2 = mfma16bf(A[0], Bf[2], c2);
-    c = mfma16bf(A[0], Bf[1], c);
-    c2 = mfma16bf(A[1], Bf[1], c2);
-    c = mfma16bf(A[0], Bf[0], c);
+    c2 = mfma16b(A[2], Bf[0], c2);         // chain 2: the small terms
+    c = mfma16b(A[1], Bf[0], c);
+    c2 = mfma16b(A[0], Bf[2], c2);
+    c = mfma16b(A[0], Bf[1], c);
+    c2 = mfma16b(A[1], Bf[1], c2);
+    c = mfma16b(A[0], Bf[0], c);
   } else {
-    c = mfma16bf(A[2], Bf[0], c);
-    c = mfma16bf(A[0], Bf[2], c);
-    c = mfma16bf(A[1], Bf[1], c);
-    c = mfma16bf(A[1], Bf[0], c);
-    c = mfma16bf(A[0], Bf[1], c);
-    c = mfma16bf(A[0], Bf[0], c);
+    c = mfma16b(A[2], Bf[0], c);
+    c = mfma16b(A[0], Bf[2], c);
+    c = mfma16b(A[1], Bf[1], c);
+    c = mfma16b(A[1], Bf[0], c);
+    c = mfma16b(A[0], Bf[1], c);
+    c = mfma16b(A[0], Bf[0], c);
   }
 }
 
@@ -1698,9 +1687,9 @@ __device__ __forceinline__ void gram16x6p_body(const float* __restrict__ emb, in
       }
     }
   };
-  const gx_u32x4* img = reinterpret_cast<const gx_u32x4*>(x6p_lds) + g * (Bp + 1) + i;
+  const u32x4* img = reinterpret_cast<const u32x4*>(x6p_lds) + g * (Bp + 1) + i;
   // fragment (pass sb, k-step ks, plane pl, tile t) = img[sb * IMG + (pl * 8 + 4 * ks) * (Bp + 1) + 16 * t]
-  auto frag3 = [&](gx_u32x4 (&f)[3], int sb, int ks, int tile) {
+  auto frag3 = [&](u32x4 (&f)[3], int sb, int ks, int tile) {
 #pragma unroll
     for (int pl = 0; pl < 3; ++pl) f[pl] = img[sb * IMG + (pl * 8 + 4 * ks) * (Bp + 1) + 16 * tile];
   };
@@ -1726,7 +1715,7 @@ __device__ __forceinline__ void gram16x6p_body(const float* __restrict__ emb, in
 #pragma unroll
   for (int ks = 0; ks < 2; ++ks) {
     int st = s_first, tj = tj_first;
-    gx_u32x4 a0[3], a1[3], b[3];
+    u32x4 a0[3], a1[3], b[3];
     frag3(a0, 0, ks, 2 * st);
     frag3(a1, 0, ks, 2 * st + 1 < T ? 2 * st + 1 : 2 * st);
     frag3(b, 0, ks, tj);
@@ -1735,7 +1724,7 @@ __device__ __forceinline__ void gram16x6p_body(const float* __restrict__ emb, in
       if (ls < nsteps) {
         int st_n, tj_n;
         next_step(st, tj, st_n, tj_n);
-        gx_u32x4 b_n[3];
+        u32x4 b_n[3];
         frag3(b_n, 0, ks, tj_n);
         __builtin_amdgcn_sched_barrier(0);       // the next step's reads fly under these MFMAs
         x6_pair_mfmas<DUAL>(a0, b, acc[2 * ls], acc2[DUAL ? 2 * ls : 0]);
@@ -1760,7 +1749,7 @@ __device__ __forceinline__ void gram16x6p_body(const float* __restrict__ emb, in
   float* slab = slabs + (int64_t)blockIdx.x * P * 256;
   {
     int st = s_first, tj = tj_first;
-    gx_u32x4 a0[2][3], a1[2][3], b[2][3];
+    u32x4 a0[2][3], a1[2][3], b[2][3];
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
       frag3(a0[ks], 1, ks, 2 * st);
@@ -1772,7 +1761,7 @@ __device__ __forceinline__ void gram16x6p_body(const float* __restrict__ emb, in
       if (ls < nsteps) {
         int st_n, tj_n;
         next_step(st, tj, st_n, tj_n);
-        gx_u32x4 b_n[2][3];
+        u32x4 b_n[2][3];
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) frag3(b_n[ks], 1, ks, tj_n);
         __builtin_amdgcn_sched_barrier(0);
@@ -2168,7 +2157,6 @@ __global__ __launch_bounds__(512) void gram_bwd_planes_kernel(const float* __res
   f32x4 acc0[NRT], acc1[NRT];
 #pragma unroll
   for (int t = 0; t < NRT; ++t) acc0[t] = acc1[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-  typedef short gbp_s16x4 __attribute__((ext_vector_type(4)));
   for (int ks = 0; ks < KS; ++ks) {
     __syncthreads();                                   // the previous k-step's fragments are read
     publish();
@@ -2177,28 +2165,24 @@ __global__ __launch_bounds__(512) void gram_bwd_planes_kernel(const float* __res
     // E^T fragments of the wave's 16 columns: lane (group g, 4 q + p) addresses slab row
     // 8 g + 4 half + q, columns 16 w + 4 p .. + 3; lane (g, i) receives column i of the four rows —
     // k index 8 g + 4 half + q, the natural order of the A fragment's 16 bytes
-    gx_u32x4 bfr[3];
+    u32x4 bfr[3];
 #pragma unroll
     for (int pl = 0; pl < 3; ++pl) {
       const unsigned short* pb = ep + (pl * 32 + 8 * g_ + q_) * GBP_LDE + 16 * wid + 4 * p_;
-      const uint2 lo = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                                                     (gbp_s16x4 __attribute__((address_space(3)))*)(pb)));
-      const uint2 hi = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                                                     (gbp_s16x4 __attribute__((address_space(3)))*)(pb + 4 * GBP_LDE)));
-      bfr[pl] = gx_u32x4{lo.x, lo.y, hi.x, hi.y};
+      bfr[pl] = tr_pair(pb, 4 * GBP_LDE);
     }
 #pragma unroll
     for (int t = 0; t < NRT; ++t) {
-      gx_u32x4 a[3];
+      u32x4 a[3];
 #pragma unroll
       for (int pl = 0; pl < 3; ++pl)
-        a[pl] = *reinterpret_cast<const gx_u32x4*>(mp + (pl * Rp + 16 * t + ii) * GBP_LDM + 8 * g_);
-      acc0[t] = mfma16bf(a[1], bfr[1], acc0[t]);       // small terms first, two chains
-      acc1[t] = mfma16bf(a[0], bfr[2], acc1[t]);
-      acc0[t] = mfma16bf(a[2], bfr[0], acc0[t]);
-      acc1[t] = mfma16bf(a[0], bfr[1], acc1[t]);
-      acc0[t] = mfma16bf(a[1], bfr[0], acc0[t]);
-      acc1[t] = mfma16bf(a[0], bfr[0], acc1[t]);
+        a[pl] = *reinterpret_cast<const u32x4*>(mp + (pl * Rp + 16 * t + ii) * GBP_LDM + 8 * g_);
+      acc0[t] = mfma16b(a[1], bfr[1], acc0[t]);       // small terms first, two chains
+      acc1[t] = mfma16b(a[0], bfr[2], acc1[t]);
+      acc0[t] = mfma16b(a[2], bfr[0], acc0[t]);
+      acc1[t] = mfma16b(a[0], bfr[1], acc1[t]);
+      acc0[t] = mfma16b(a[1], bfr[0], acc0[t]);
+      acc1[t] = mfma16b(a[0], bfr[0], acc1[t]);
     }
   }
   // register q of lane (column i, group g) = row 16 t + 4 g + q.  The tile leaves through LDS so

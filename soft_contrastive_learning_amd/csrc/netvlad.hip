@@ -88,9 +88,6 @@ constexpr int RT_PLANE = K * RT_LD;             // 2304 floats (= 36 x 64)
 constexpr int RT_CHUNK = 4 * RT_PLANE;          // 9216 floats per buffer
 constexpr size_t kRowTile16Lds = 2 * (size_t)RT_CHUNK * sizeof(float);   // 73,728 B
 
-__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
 __device__ __forceinline__ float q16_sum(float v) {
 #pragma unroll
   for (int m = 1; m < 16; m <<= 1) v += __shfl_xor(v, m, 64);
@@ -347,26 +344,10 @@ __global__ __launch_bounds__(256, 2) void rowtile16_kernel(RowTileArgs p) {
 // x.o = x.o1 + x.o2 + x.o3 differs from the float32 contraction only by accumulation order —
 // at 3 x 16 cycles per 16x16x32 step instead of 8 x 32 cycles of 16x16x4 float32 steps, and
 // with no bf16 -> f32 conversion of x at all.  Row norms by float32 FMAs on the same registers.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
-__device__ __forceinline__ f32x4 mfma16b(u32x4 a, u32x4 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a),
-                                                 __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-
-// LDS-DMA: 64 lanes x 16 bytes from per-lane global addresses into 1 KB of consecutive LDS at
-// the wave-uniform byte address lds_byte.  Inline asm, so hipcc does not order it against LDS
-// reads of the other buffer; the kernel waits for it itself (s_waitcnt vmcnt).
-__device__ __forceinline__ void nv_glds16(const unsigned short* src, unsigned lds_byte) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(src), "s"(lds_byte)
-      : "memory");
-}
-// The same with a wave-uniform 64-bit base (SGPR pair) and a 32-bit per-lane byte offset: the
+// LDS-DMA is glds16 (scl_cdna4.h); the kernels wait for it themselves (s_waitcnt vmcnt).
+// nv_glds16s is that header's glds16_s (wave-uniform 64-bit base in an SGPR pair, 32-bit per-lane
+// byte offset) with the lane's offset formed inside the asm block, for this file's reason: the
 // eight-wave kernels have no registers to spare for per-lane 64-bit row addresses (hipcc hoisted
 // four of them out of the step loop, spilled two, and put the reload — an s_waitcnt vmcnt(0) —
 // between two DMA instructions: every stage then waited out a full memory latency twice).
@@ -381,9 +362,6 @@ __device__ __forceinline__ void nv_glds16s(const unsigned short* sbase, unsigned
       : "=&s"(keep), "=&v"(voff)
       : "v"(lane), "s"(cx), "s"(sbase), "s"(lds_byte)
       : "memory");
-}
-__device__ __forceinline__ unsigned nv_lds_byte_of(const void* p) {
-  return (unsigned)(size_t)(const __attribute__((address_space(3))) char*)p;
 }
 
 // V_part[b, half, d, k] = sum_{n in half} x[b,n,d] * (coefn[b,n,k] * rn[b,n])
@@ -518,8 +496,6 @@ __global__ __launch_bounds__(256) void aggregate_kernel(const void* __restrict__
   }
 }
 
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-
 // =======================================================================================
 // Fused kernels for bf16 feature maps (round 3): ONE pass over x per direction.
 //
@@ -580,7 +556,6 @@ __host__ __device__ constexpr int vf_pi(int g, int e) {
 constexpr int VF_WREP = 1;
 constexpr int VF_WIMG = VF_NPL * D * K;           // bf16 elements per copy
 
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 // v + (v of the lane 16 / 32 away): one register swap between 16-lane rows / 32-lane halves
 // (v_permlane16_swap_b32 / v_permlane32_swap_b32) and one add — no trip through the LDS crossbar
 // like ds_bpermute (what __shfl_xor compiles to for these distances).
@@ -601,13 +576,8 @@ __device__ __forceinline__ float vf_gsum(float v) { return vf_pair32(vf_pair16(v
 __device__ __forceinline__ float vf_gmax(float v) { return vf_pair32(vf_pair16(v, true), true); }
 
 typedef __attribute__((address_space(3))) u32x4 lds_u32x4;
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 typedef __attribute__((address_space(3))) u32x2 lds_u32x2;
 __device__ __forceinline__ u32x4 vf_ldsr128(unsigned byte) { return *(const lds_u32x4*)(size_t)byte; }
-__device__ __forceinline__ uint2 vf_ldsr_tr(unsigned byte) {
-  const s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(size_t)byte);
-  return __builtin_bit_cast(uint2, v);
-}
 __device__ __forceinline__ void vf_ldsw64(unsigned byte, unsigned lo, unsigned hi) {
   *(lds_u32x2*)(size_t)byte = u32x2{lo, hi};
 }
@@ -743,7 +713,7 @@ __global__ __launch_bounds__(512) void vlad_fwd8_kernel(VladFwdArgs p) {
   const int st_lo = sl * p.steps_per_slice;
   const int st_hi = st_lo + p.steps_per_slice < nsteps_img ? st_lo + p.steps_per_slice : nsteps_img;
   const int nst = st_hi - st_lo;                           // >= 1 by the host's choice of S
-  const unsigned lds0 = nv_lds_byte_of(vf_lds);
+  const unsigned lds0 = lds_byte_of(vf_lds);
   const unsigned cf0 = lds0 + VF_NST * VF_STAGE + w * VF_CF;
   unsigned char* xl = vf_lds + VF_NST * VF_STAGE + 4 * VF_CF;
   float* pn = reinterpret_cast<float*>(xl + V8_XL);
@@ -944,8 +914,8 @@ __global__ __launch_bounds__(512) void vlad_fwd8_kernel(VladFwdArgs p) {
     u32x4 bfr[VF_NPL];
 #pragma unroll
     for (int pl = 0; pl < VF_NPL; ++pl) {
-      const uint2 lo = vf_ldsr_tr(cf0 + pl * VF_CFPL + cfoff[0]);
-      const uint2 hi = vf_ldsr_tr(cf0 + pl * VF_CFPL + cfoff[1]);
+      const uint2 lo = lds_tr16_at(cf0 + pl * VF_CFPL + cfoff[0]);
+      const uint2 hi = lds_tr16_at(cf0 + pl * VF_CFPL + cfoff[1]);
       bfr[pl] = u32x4{lo.x, lo.y, hi.x, hi.y};
     }
     // address of the transposed fragment of channel tile ct = 16 h + c: (stage + troff[hh]) ^ 32 (c & 7)
@@ -954,16 +924,16 @@ __global__ __launch_bounds__(512) void vlad_fwd8_kernel(VladFwdArgs p) {
     u32x4 af[8];
 #pragma unroll
     for (int c = 0; c < V8_AHEAD; ++c) {
-      const uint2 lo = vf_ldsr_tr((tb0 ^ (32u * (c & 7))) + 32u * (c & 8)),
-                  hi = vf_ldsr_tr((tb1 ^ (32u * (c & 7))) + 32u * (c & 8));
+      const uint2 lo = lds_tr16_at((tb0 ^ (32u * (c & 7))) + 32u * (c & 8)),
+                  hi = lds_tr16_at((tb1 ^ (32u * (c & 7))) + 32u * (c & 8));
       af[c] = u32x4{lo.x, lo.y, hi.x, hi.y};
     }
 #pragma unroll
     for (int c = 0; c < 16; ++c) {
       if (c + V8_AHEAD < 16) {
         const int cn = c + V8_AHEAD;
-        const uint2 lo = vf_ldsr_tr((tb0 ^ (32u * (cn & 7))) + 32u * (cn & 8)),
-                    hi = vf_ldsr_tr((tb1 ^ (32u * (cn & 7))) + 32u * (cn & 8));
+        const uint2 lo = lds_tr16_at((tb0 ^ (32u * (cn & 7))) + 32u * (cn & 8)),
+                    hi = lds_tr16_at((tb1 ^ (32u * (cn & 7))) + 32u * (cn & 8));
         af[cn & 7] = u32x4{lo.x, lo.y, hi.x, hi.y};
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -1060,7 +1030,7 @@ __global__ __launch_bounds__(512) void vlad_bwd8_kernel(VladBwdArgs p) {
   const int st_lo = sl * p.steps_per_slice;
   const int st_hi = st_lo + p.steps_per_slice < nsteps_img ? st_lo + p.steps_per_slice : nsteps_img;
   const int nst = st_hi - st_lo;
-  const unsigned lds0 = nv_lds_byte_of(vf_lds);
+  const unsigned lds0 = lds_byte_of(vf_lds);
   const unsigned cf0 = lds0 + VF_NST * VF_STAGE + w * VF_CF;
   unsigned char* xl = vf_lds + VF_NST * VF_STAGE + 4 * VF_CF;
   float* exch = reinterpret_cast<float*>(xl + V8_XL + V8_PN);     // [tile][cluster group][loc][4]
@@ -1211,24 +1181,24 @@ __global__ __launch_bounds__(512) void vlad_bwd8_kernel(VladBwdArgs p) {
     u32x4 bfr[VF_NPL];
 #pragma unroll
     for (int pl = 0; pl < VF_NPL; ++pl) {
-      const uint2 lo = vf_ldsr_tr(cf0 + pl * VF_CFPL + cfoff[0]);
-      const uint2 hi = vf_ldsr_tr(cf0 + pl * VF_CFPL + cfoff[1]);
+      const uint2 lo = lds_tr16_at(cf0 + pl * VF_CFPL + cfoff[0]);
+      const uint2 hi = lds_tr16_at(cf0 + pl * VF_CFPL + cfoff[1]);
       bfr[pl] = u32x4{lo.x, lo.y, hi.x, hi.y};
     }
     const unsigned tb0 = sb + troff[0], tb1 = sb + troff[1];
     u32x4 af[8];
 #pragma unroll
     for (int c = 0; c < V8_AHEAD; ++c) {
-      const uint2 lo = vf_ldsr_tr((tb0 ^ (32u * (c & 7))) + 32u * (c & 8)),
-                  hi = vf_ldsr_tr((tb1 ^ (32u * (c & 7))) + 32u * (c & 8));
+      const uint2 lo = lds_tr16_at((tb0 ^ (32u * (c & 7))) + 32u * (c & 8)),
+                  hi = lds_tr16_at((tb1 ^ (32u * (c & 7))) + 32u * (c & 8));
       af[c] = u32x4{lo.x, lo.y, hi.x, hi.y};
     }
 #pragma unroll
     for (int c = 0; c < 16; ++c) {
       if (c + V8_AHEAD < 16) {
         const int cn = c + V8_AHEAD;
-        const uint2 lo = vf_ldsr_tr((tb0 ^ (32u * (cn & 7))) + 32u * (cn & 8)),
-                    hi = vf_ldsr_tr((tb1 ^ (32u * (cn & 7))) + 32u * (cn & 8));
+        const uint2 lo = lds_tr16_at((tb0 ^ (32u * (cn & 7))) + 32u * (cn & 8)),
+                    hi = lds_tr16_at((tb1 ^ (32u * (cn & 7))) + 32u * (cn & 8));
         af[cn & 7] = u32x4{lo.x, lo.y, hi.x, hi.y};
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -1716,7 +1686,6 @@ struct Elem8<float> {
 };
 template <>
 struct Elem8<unsigned short> {
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
   typedef u32x4 raw;
   static __device__ __forceinline__ raw ldraw(const unsigned short* p) {
     return *reinterpret_cast<const u32x4*>(p);
@@ -1921,7 +1890,7 @@ __global__ __launch_bounds__(256, 1) void vlad_dx_kernel(VladDxArgs p) {
   const int n_lo = VF_STEP * st_lo;
   const int n_hi = VF_STEP * st_hi < p.N ? VF_STEP * st_hi : p.N;
   const int ntile = (n_hi - n_lo + 15) / 16;
-  const unsigned lds0 = nv_lds_byte_of(dxv_lds);
+  const unsigned lds0 = lds_byte_of(dxv_lds);
   const unsigned scr0 = lds0 + 2 * DXV_ABUF + wid * DXV_SCR;
   unsigned long long* stp =
       SCL_DIAG_ONLY(p.dbg) && threadIdx.x == 0 ? p.stamps + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 32 : nullptr;

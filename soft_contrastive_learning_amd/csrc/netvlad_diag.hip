@@ -46,7 +46,7 @@ __global__ __launch_bounds__(256, 1) void vlad_fwd_kernel(VladFwdArgs p) {
   const int st_lo = sl * p.steps_per_slice;
   const int st_hi = st_lo + p.steps_per_slice < nsteps_img ? st_lo + p.steps_per_slice : nsteps_img;
   const int nst = st_hi - st_lo;                           // >= 1 by the host's choice of S
-  const unsigned lds0 = nv_lds_byte_of(vf_lds);
+  const unsigned lds0 = lds_byte_of(vf_lds);
   const unsigned cf0 = lds0 + VF_NST * VF_STAGE + wid * VF_CF;
   float* exch = reinterpret_cast<float*>(vf_lds + VF_NST * VF_STAGE + 4 * VF_CF);
   const unsigned short* xb = p.x + (int64_t)b * p.N * D;
@@ -73,7 +73,7 @@ __global__ __launch_bounds__(256, 1) void vlad_fwd_kernel(VladFwdArgs p) {
       const int r = wid + 4 * v;
       int n = VF_STEP * step + r;
       n = n < p.N ? n : p.N - 1;
-      nv_glds16(xb + (int64_t)n * D + ((lane ^ (r & 15)) << 3), base + r * 1024);
+      glds16(xb + (int64_t)n * D + ((lane ^ (r & 15)) << 3), base + r * 1024);
     }
   };
   stage(st_lo);
@@ -241,8 +241,8 @@ __global__ __launch_bounds__(256, 1) void vlad_fwd_kernel(VladFwdArgs p) {
     u32x4 bfr[VF_NPL];
 #pragma unroll
     for (int pl = 0; pl < VF_NPL; ++pl) {
-      const uint2 lo = vf_ldsr_tr(cf0 + pl * VF_CFPL + cfoff[0]);
-      const uint2 hi = vf_ldsr_tr(cf0 + pl * VF_CFPL + cfoff[1]);
+      const uint2 lo = lds_tr16_at(cf0 + pl * VF_CFPL + cfoff[0]);
+      const uint2 hi = lds_tr16_at(cf0 + pl * VF_CFPL + cfoff[1]);
       bfr[pl] = u32x4{lo.x, lo.y, hi.x, hi.y};
     }
     // address of the transposed fragment of channel tile ct: (stage + troff[h]) ^ 32 ct touches
@@ -258,15 +258,15 @@ __global__ __launch_bounds__(256, 1) void vlad_fwd_kernel(VladFwdArgs p) {
     u32x4 af[8];
 #pragma unroll
     for (int ct = 0; ct < VF_AHEAD; ++ct) {
-      const uint2 lo = vf_ldsr_tr(ta[0][ct & 7] + 32u * (ct & 24)), hi = vf_ldsr_tr(ta[1][ct & 7] + 32u * (ct & 24));
+      const uint2 lo = lds_tr16_at(ta[0][ct & 7] + 32u * (ct & 24)), hi = lds_tr16_at(ta[1][ct & 7] + 32u * (ct & 24));
       af[ct] = u32x4{lo.x, lo.y, hi.x, hi.y};
     }
 #pragma unroll
     for (int ct = 0; ct < 32; ++ct) {
       if (ct + VF_AHEAD < 32) {
         const int cn = ct + VF_AHEAD;
-        const uint2 lo = vf_ldsr_tr(ta[0][cn & 7] + 32u * (cn & 24)),
-                    hi = vf_ldsr_tr(ta[1][cn & 7] + 32u * (cn & 24));
+        const uint2 lo = lds_tr16_at(ta[0][cn & 7] + 32u * (cn & 24)),
+                    hi = lds_tr16_at(ta[1][cn & 7] + 32u * (cn & 24));
         af[cn & 7] = u32x4{lo.x, lo.y, hi.x, hi.y};
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -355,7 +355,7 @@ __global__ __launch_bounds__(256, 1) void vlad_bwd_kernel(VladBwdArgs p) {
   const int st_lo = sl * p.steps_per_slice;
   const int st_hi = st_lo + p.steps_per_slice < nsteps_img ? st_lo + p.steps_per_slice : nsteps_img;
   const int nst = st_hi - st_lo;
-  const unsigned lds0 = nv_lds_byte_of(vf_lds);
+  const unsigned lds0 = lds_byte_of(vf_lds);
   const unsigned cf0 = lds0 + VF_NST * VF_STAGE + wid * VF_CF;
   float* exch = reinterpret_cast<float*>(vf_lds + VF_NST * VF_STAGE + 4 * VF_CF);   // [wave][loc][4]
   const unsigned short* xb = p.x + (int64_t)b * p.N * D;
@@ -367,7 +367,7 @@ __global__ __launch_bounds__(256, 1) void vlad_bwd_kernel(VladBwdArgs p) {
       const int r = wid + 4 * v;
       int n = VF_STEP * step + r;
       n = n < p.N ? n : p.N - 1;
-      nv_glds16(xb + (int64_t)n * D + ((lane ^ (r & 15)) << 3), base + r * 1024);
+      glds16(xb + (int64_t)n * D + ((lane ^ (r & 15)) << 3), base + r * 1024);
     }
   };
   stage(st_lo);
@@ -506,8 +506,8 @@ __global__ __launch_bounds__(256, 1) void vlad_bwd_kernel(VladBwdArgs p) {
     u32x4 bfr[VF_NPL];
 #pragma unroll
     for (int pl = 0; pl < VF_NPL; ++pl) {
-      const uint2 lo = vf_ldsr_tr(cf0 + pl * VF_CFPL + cfoff[0]);
-      const uint2 hi = vf_ldsr_tr(cf0 + pl * VF_CFPL + cfoff[1]);
+      const uint2 lo = lds_tr16_at(cf0 + pl * VF_CFPL + cfoff[0]);
+      const uint2 hi = lds_tr16_at(cf0 + pl * VF_CFPL + cfoff[1]);
       bfr[pl] = u32x4{lo.x, lo.y, hi.x, hi.y};
     }
     // address of the transposed fragment of channel tile ct: (stage + troff[h]) ^ 32 ct touches
@@ -523,15 +523,15 @@ __global__ __launch_bounds__(256, 1) void vlad_bwd_kernel(VladBwdArgs p) {
     u32x4 af[8];
 #pragma unroll
     for (int ct = 0; ct < VF_AHEAD; ++ct) {
-      const uint2 lo = vf_ldsr_tr(ta[0][ct & 7] + 32u * (ct & 24)), hi = vf_ldsr_tr(ta[1][ct & 7] + 32u * (ct & 24));
+      const uint2 lo = lds_tr16_at(ta[0][ct & 7] + 32u * (ct & 24)), hi = lds_tr16_at(ta[1][ct & 7] + 32u * (ct & 24));
       af[ct] = u32x4{lo.x, lo.y, hi.x, hi.y};
     }
 #pragma unroll
     for (int ct = 0; ct < 32; ++ct) {
       if (ct + VF_AHEAD < 32) {
         const int cn = ct + VF_AHEAD;
-        const uint2 lo = vf_ldsr_tr(ta[0][cn & 7] + 32u * (cn & 24)),
-                    hi = vf_ldsr_tr(ta[1][cn & 7] + 32u * (cn & 24));
+        const uint2 lo = lds_tr16_at(ta[0][cn & 7] + 32u * (cn & 24)),
+                    hi = lds_tr16_at(ta[1][cn & 7] + 32u * (cn & 24));
         af[cn & 7] = u32x4{lo.x, lo.y, hi.x, hi.y};
       }
       __builtin_amdgcn_sched_barrier(0);

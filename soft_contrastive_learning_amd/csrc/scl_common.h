@@ -7,23 +7,9 @@
 #include <mutex>
 
 #include "scl_hip.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
+#include "scl_cdna4.h"   // vector types, MFMA wrappers, LDS-DMA, transposed LDS reads
 
 #define SCL_WAVE 64
-
-// v_mfma_f32_32x32x2_f32: D[32x32] += A[32x2] * B[2x32], exact f32 (a k-ordered
-// fmaf chain).  Lane l supplies A[i = l & 31][k = l >> 5] and B[k = l >> 5][j = l & 31].
-// Accumulator register r of lane l is D[row = (r & 3) + 8 * (r >> 2) + 4 * (l >> 5)][col = l & 31].
-__device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ int acc_row(int reg, int half) {
-  return (reg & 3) + 8 * (reg >> 2) + 4 * half;
-}
 
 __device__ __forceinline__ f32x16 zero16() {
   f32x16 z;
@@ -84,7 +70,7 @@ __device__ __forceinline__ unsigned relu_mask_word(unsigned g, unsigned y) {
   asm("v_pk_mul_lo_u16 %0, %1, %2" : "=v"(out) : "v"(g), "v"(keep));
   return out;
 }
-template <typename V4>   // four packed words (the translation units' own u32x4)
+template <typename V4>   // four packed words (u32x4)
 __device__ __forceinline__ V4 relu_mask(V4 g, V4 y) {
   return V4{relu_mask_word(g.x, y.x), relu_mask_word(g.y, y.y), relu_mask_word(g.z, y.z),
                relu_mask_word(g.w, y.w)};

@@ -61,13 +61,6 @@ __global__ __launch_bounds__(256) void refnorm_kernel(const float* __restrict__ 
     atomicMax(rmax_bits, __float_as_uint(fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]))));
 }
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ f32x16 mfma_bf16(u32x4 a, u32x4 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a),
-                                                 __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
 // x = hi + lo + O(2^-17 |x|): hi = bf16(x), lo = bf16(x - hi), both round-to-nearest-even.
 __device__ __forceinline__ void split_bf16(float x, unsigned& hi, unsigned& lo) {
   const unsigned short h = f32_to_bf16(x);
@@ -102,23 +95,6 @@ __global__ __launch_bounds__(256) void ref_split_kernel(const float* __restrict_
   split8(a, b, h, l);
   hi[i] = h;
   lo[i] = l;
-}
-
-// LDS-DMA (global_load_lds_dwordx4): one wave instruction copies 64 x 16 bytes from a wave-uniform base
-// + per-lane byte offsets straight into 1 KB of consecutive LDS — no staging registers, no ds_write pass.
-// Inline asm so that hipcc does not order it against the reads of the other buffer; the kernel waits
-// vmcnt(0) itself before the barrier that hands the buffer over (csrc/conv64.hip has the same helper).
-__device__ __forceinline__ void tn_glds16(const void* base, unsigned off_bytes, unsigned lds_byte) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(off_bytes), "s"(base), "s"(lds_byte)
-      : "memory");
-}
-__device__ __forceinline__ unsigned tn_lds_byte_of(const void* p) {
-  return (unsigned)(size_t)(const __attribute__((address_space(3))) char*)p;
 }
 
 // Rank-count sort of one query's KEEP-entry list by one wave (entry e = lane & 31):
@@ -298,7 +274,7 @@ __global__ __launch_bounds__(256, 2) void topn_scan_kernel(const void* __restric
   auto dma_issue = [&](int t) {
     const int rb = r_begin + t * 32 * tile_stride;
     const int last = r_end - 1 - rb < 31 ? r_end - 1 - rb : 31;       // last valid row of the tile
-    const unsigned dst0 = tn_lds_byte_of(lds) + (unsigned)(t & 1) * (BUF_DW * 4);
+    const unsigned dst0 = lds_byte_of(lds) + (unsigned)(t & 1) * (BUF_DW * 4);
 #pragma unroll
     for (int k = 0; k < (NCHT + QW - 1) / QW; ++k) {
       const int c = wid_s + QW * k;                                   // (wave-uniform)
@@ -310,7 +286,7 @@ __global__ __launch_bounds__(256, 2) void topn_scan_kernel(const void* __restric
         const int logical = phys ^ (row & (SLOTS - 1));
         row = row < last ? row : last;
         const char* base = reinterpret_cast<const char*>(BF && pl ? ref_lov : refv) + (int64_t)rb * ROWB;
-        tn_glds16(base, (unsigned)(row * ROWB + logical * 16), dst0 + (unsigned)(pl * PLANE_B + 1024 * cc));
+        glds16_s(base, (unsigned)(row * ROWB + logical * 16), dst0 + (unsigned)(pl * PLANE_B + 1024 * cc));
       }
     }
     if (threadIdx.x < 32) {
@@ -383,9 +359,9 @@ __global__ __launch_bounds__(256, 2) void topn_scan_kernel(const void* __restric
             vl[(u + 1) & 1] = rd_l(u + 1);
           }
           __builtin_amdgcn_sched_barrier(0);
-          acc = mfma_bf16(qh[u], vh[u & 1], acc);
-          acc = mfma_bf16(qh[u], vl[u & 1], acc);
-          acc = mfma_bf16(ql[u], vh[u & 1], acc);
+          acc = mfma32b(qh[u], vh[u & 1], acc);
+          acc = mfma32b(qh[u], vl[u & 1], acc);
+          acc = mfma32b(ql[u], vh[u & 1], acc);
         }
       }
     } else {

@@ -23,8 +23,6 @@
 
 namespace {
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 template <typename T>
 struct Vec8;
 template <>

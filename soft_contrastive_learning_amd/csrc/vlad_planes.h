@@ -7,8 +7,6 @@
 #pragma once
 #include "scl_common.h"
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 // x = h1 + h2 + h3 exactly (up to the float32 subnormal range): three bf16 roundings.
 __device__ __forceinline__ void split3_bf16(float x, unsigned short& h1, unsigned short& h2,
                                             unsigned short& h3) {
