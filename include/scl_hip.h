@@ -662,6 +662,38 @@ int scl_dense_wgrad(const float* x, int64_t ld_x, const float* gy, int64_t ld_gy
                     void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Spectral losses (csrc/spectral_loss.hip): wrd_loss, prodwrd_loss and sumwrd_loss of the
+ * reference (model/losses.py:373-437; wrd is its trainer's default --loss).  Per tuple the loss
+ * takes the `dimensions` largest singular values of the weighted residual rows
+ * diag(w) (x_j - a) on a positive and a negative side:
+ *   loss = mean_t(prod_pos[t] - prod_neg[t]) + margin.
+ *
+ *   kind        0 wrd: w = the payload;  1 prodwrd: w = payload * f;  2 sumwrd: w = payload + f,
+ *               f = 1 / (1 + exp(f_alpha_p (sim - f_lamb))) on the positive side and
+ *               1 / (1 + exp(f_alpha_n (f_lamb - sim))) on the negative one, sim = a . x_j
+ *   z           [T, S+1, E] f32, contiguous; row 0 of a tuple is the anchor, then the positives
+ *               and the negatives (S = P + N <= 32)
+ *   pos_w, neg_w  [T, S] f32 payload weights of the two sides (no gradient)
+ *   dimensions  1 <= dimensions <= S
+ *   loss_out    device scalar f32
+ *   prods_out   [T, 2] f64: prod_pos, prod_neg of every tuple.  The loss is margin plus a
+ *               difference of products that are often 1e-5 and smaller; compare these.
+ *   coef_out    [T, S+1, S+1] f32 or NULL: per tuple the matrix C with d loss / d z[t] = C z[t]
+ *               (the 1/T of the mean included), consumed by scl_gram_loss_bwd tuple by tuple
+ * The Gram of z is accumulated in float64 and W R W is solved by a cyclic Jacobi iteration in
+ * float64 with a fixed maximum sweep count; every sum has a fixed order (bit-reproducible).
+ * A singular value that is exactly 0 among the `dimensions` largest contributes no gradient term
+ * (d prod / d s_i divided by s_i; the reference's SVD gradient gives inf or NaN there).
+ * Returns SCL_E_NULL for a missing pointer, SCL_E_SHAPE for T, S, E or dimensions out of range,
+ * SCL_E_KIND for an unknown kind, SCL_E_WORKSPACE; nothing is launched then.
+ * ------------------------------------------------------------------------- */
+size_t scl_spectral_loss_workspace_bytes(int T, int S, int E);
+int scl_spectral_loss_fwd(int kind, const float* z, const float* pos_w, const float* neg_w, int T,
+                          int S, int E, float margin, int dimensions, float f_alpha_p,
+                          float f_alpha_n, float f_lamb, float* loss_out, double* prods_out,
+                          float* coef_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Host utility for the checkpoint bundle reader / writer (tf_bundle.py; the reference
  * restores and saves through tf.train.Saver, train/train.py:882-905, 984, 1079, 1102):
  * CRC-32C (Castagnoli, reflected 0x82F63B78) of n bytes continued from `crc` (0 to start),

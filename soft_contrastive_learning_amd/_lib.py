@@ -31,6 +31,8 @@ TUPLE_QUADRUPLET, TUPLE_LAZY_QUADRUPLET, TUPLE_EVIL_QUADRUPLET = 3, 4, 5
 VLAD_D, VLAD_K = 512, 64
 VLAD_SAVE_ROWS = 514      # save_vlad rows per image: U, asum, sync words of the backward pass
 TOPN_SCORE_F32, TOPN_SCORE_BF16X3 = 0, 1
+SPECTRAL_WRD, SPECTRAL_PRODWRD, SPECTRAL_SUMWRD = 0, 1, 2
+SPECTRAL_MAX_S = 32        # others (positives + negatives) per tuple of scl_spectral_loss_fwd
 CONV_TRANSPOSED, W_F32, W_PACKED = 1, 2, 4   # flag word of the convolution entry points
 PACK_VLAD_W = 16           # SclPackJob.flags: the job writes the NetVLAD plane images of assign_w
 
@@ -139,6 +141,9 @@ SIGNATURES = {
     "scl_dense_bwd_data_workspace_bytes": (_z, [_i, _i, _i]),
     "scl_dense_bwd_data": (_i, [_p, _l, _p, _l, _p, _l, _i, _i, _i, _p, _l, _p, _z, _p]),
     "scl_dense_wgrad": (_i, [_p, _l, _p, _l, _p, _l, _i, _i, _i, _p, _l, _p, _p]),
+    "scl_spectral_loss_workspace_bytes": (_z, [_i, _i, _i]),
+    "scl_spectral_loss_fwd": (_i, [_i, _p, _p, _p, _i, _i, _i, _f, _i, _f, _f, _f, _p, _p, _p, _p, _z,
+                                   _p]),
 }
 
 _libs = {}

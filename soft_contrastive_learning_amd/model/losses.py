@@ -15,6 +15,7 @@ and backward are the hand-written gfx950 kernels behind ``include/scl_hip.h``.
   distance_triplet_loss / distance_quadruplet_loss   model/losses.py:239-307
   _pairwise_squared_distances  model/losses.py:656-661
   pairwise_distance_loss       model/losses.py:627-646
+  wrd_loss / prodwrd_loss / sumwrd_loss       model/losses.py:373-437
 The pointnetvlad_cls losses the trainer imports beside them (train/train.py:25)
 live in ``soft_contrastive_learning_amd.pointnetvlad_cls``.
 """
@@ -25,7 +26,8 @@ from .. import _lib as L
 __all__ = ['wms_loss', 'ms_loss', 'ms_det', 'logratio_loss', 'evil_triplet_loss',
            'evil_quadruplet_loss', 'worst_pos_distance', '_pairwise_squared_distances',
            'distance_loss', 'huber_distance_loss', 'distance_triplet_loss',
-           'distance_quadruplet_loss', 'pairwise_distance_loss']
+           'distance_quadruplet_loss', 'pairwise_distance_loss', 'wrd_loss', 'prodwrd_loss',
+           'sumwrd_loss']
 
 
 def _as_f32(t):
@@ -481,3 +483,105 @@ def pairwise_distance_loss(anchor, positives, pairwise_squared_d_dists, d_max_sq
     feats = torch.cat([_as_f32(anchor), _as_f32(positives)], dim=1)
     return _PairwiseDistanceLoss.apply(feats, pairwise_squared_d_dists, float(d_max_squared),
                                        float(f_max_squared), 'huber' in distance_loss_name)
+
+
+# ------------------------------------------------------------------- spectral losses
+def _side_weights(wt, t, s, name):
+    """[T,S,1] (the reference's broadcast shape) or [T,S] -> contiguous f32 [T,S], detached."""
+    if not isinstance(wt, torch.Tensor) or tuple(wt.shape) not in ((t, s, 1), (t, s)):
+        raise ValueError("%s must be [T,S,1] or [T,S] = [%d,%d(,1)], got %s"
+                         % (name, t, s, tuple(getattr(wt, 'shape', ()))))
+    return _as_f32(wt.detach()).reshape(t, s).contiguous()
+
+
+class _SpectralLoss(torch.autograd.Function):
+    """wrd / prodwrd / sumwrd on Z = [anchor; positives; negatives]; see csrc/spectral_loss.hip.
+    Returns (loss, prods [T,2] float64); the backward is ``scl_gram_loss_bwd`` per tuple on the
+    coefficient matrices the forward leaves."""
+
+    @staticmethod
+    def forward(ctx, z, pos_w, neg_w, kind, margin, dimensions, f_alpha_p, f_alpha_n, f_lamb):
+        lib = L.load()
+        t, s1, e = z.shape
+        s = s1 - 1
+        need_grad = ctx.needs_input_grad[0]
+        loss = torch.empty((), dtype=torch.float32, device=z.device)
+        prods = torch.empty((t, 2), dtype=torch.float64, device=z.device)
+        coef = torch.empty((t, s1, s1), dtype=torch.float32, device=z.device) if need_grad else None
+        nbytes = lib.scl_spectral_loss_workspace_bytes(t, s, e)
+        if nbytes == 0:
+            raise ValueError("unsupported tuple shape T=%d S=%d E=%d" % (t, s, e))
+        ws = L.workspace(nbytes, z.device)
+        L.check(lib.scl_spectral_loss_fwd(
+            kind, L.ptr(z), L.ptr(pos_w), L.ptr(neg_w), t, s, e, float(margin), int(dimensions),
+            float(f_alpha_p), float(f_alpha_n), float(f_lamb), L.ptr(loss), L.ptr(prods),
+            L.ptr(coef), L.ptr(ws), ws.numel(), L.stream_of(z)))
+        if need_grad:
+            ctx.save_for_backward(z, coef)
+        ctx.mark_non_differentiable(prods)
+        return loss, prods
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_prods):
+        lib = L.load()
+        z, coef = ctx.saved_tensors
+        t, s1, e = z.shape
+        g = _as_f32(grad_loss).contiguous()
+        grad = torch.empty_like(z)
+        for k in range(t):
+            L.check(lib.scl_gram_loss_bwd(L.ptr(z[k]), e, s1, e, L.ptr(coef[k]), L.ptr(g), 0, s1,
+                                          L.ptr(grad[k]), e, L.stream_of(z)))
+        return (grad,) + (None,) * 8
+
+
+def _spectral(kind, anchor, positives, negatives, pos_weights, neg_weights, margin, dimensions,
+              f_alpha_p, f_alpha_n, f_lamb, return_products):
+    for name, x in (('anchor', anchor), ('positives', positives), ('negatives', negatives)):
+        if not isinstance(x, torch.Tensor) or x.dim() != 3:
+            raise ValueError("%s must be rank 3 [T,R,E]" % name)
+    t, p, e = positives.shape
+    n = negatives.shape[1]
+    if tuple(anchor.shape) != (t, 1, e) or negatives.shape[0] != t or negatives.shape[2] != e:
+        raise ValueError("inconsistent tuple shapes anchor%s positives%s negatives%s" % (
+            tuple(anchor.shape), tuple(positives.shape), tuple(negatives.shape)))
+    s = p + n
+    if s > L.SPECTRAL_MAX_S:
+        raise ValueError("positives + negatives = %d above the kernel's cap of %d"
+                         % (s, L.SPECTRAL_MAX_S))
+    dimensions = int(dimensions)
+    if dimensions < 1 or dimensions > s:
+        raise ValueError("dimensions must be in 1..positives + negatives = %d, got %d"
+                         % (s, dimensions))
+    pw = _side_weights(pos_weights, t, s, 'pos_weights')
+    nw = _side_weights(neg_weights, t, s, 'neg_weights')
+    L.require_device(anchor, positives, negatives, pw, nw)
+    z = torch.cat([_as_f32(anchor), _as_f32(positives), _as_f32(negatives)], dim=1)
+    loss, prods = _SpectralLoss.apply(z, pw, nw, kind, margin, dimensions, f_alpha_p, f_alpha_n,
+                                      f_lamb)
+    return (loss, prods) if return_products else loss
+
+
+def wrd_loss(anchor, positives, negatives, pos_weights, neg_weights, margin, dimensions=10,
+             return_products=False):
+    """Weighted residual determinant, model/losses.py:373-389: per tuple the product of the
+    ``dimensions`` largest singular values of the residual rows ``x_j - anchor`` weighted by
+    ``pos_weights`` minus the same under ``neg_weights``, plus ``margin``; mean over tuples.
+    The weights ([T,P+N,1] or [T,P+N]) carry no gradient.  ``return_products=True`` also returns
+    the [T,2] float64 products (the loss alone hides them behind the margin)."""
+    return _spectral(L.SPECTRAL_WRD, anchor, positives, negatives, pos_weights, neg_weights,
+                     margin, dimensions, 0.0, 0.0, 0.0, return_products)
+
+
+def prodwrd_loss(anchor, positives, negatives, pos_weights, neg_weights, margin, dimensions=10,
+                 f_alpha_p=2.0, f_alpha_n=50.0, f_lamb=1.0, return_products=False):
+    """model/losses.py:392-413: wrd with every row weight multiplied by a sigmoid of the
+    anchor similarity (which carries gradient)."""
+    return _spectral(L.SPECTRAL_PRODWRD, anchor, positives, negatives, pos_weights, neg_weights,
+                     margin, dimensions, f_alpha_p, f_alpha_n, f_lamb, return_products)
+
+
+def sumwrd_loss(anchor, positives, negatives, pos_weights, neg_weights, margin, dimensions=10,
+                f_alpha_p=2.0, f_alpha_n=50.0, f_lamb=1.0, return_products=False):
+    """model/losses.py:416-437: wrd with that sigmoid added to every row weight."""
+    return _spectral(L.SPECTRAL_SUMWRD, anchor, positives, negatives, pos_weights, neg_weights,
+                     margin, dimensions, f_alpha_p, f_alpha_n, f_lamb, return_products)

@@ -9,7 +9,9 @@ add one "other negative" far from all of them (:503-519).  With a mining cache t
 the anchor's cached neighbours supplies hard negatives from the front of the list and hard
 positives from its back (:446-453, :459-466, :472-484).  The per-loss ``distances`` payload
 is built exactly as :525-571 (squared / plain Euclidean, anchor / pairwise / all-pairs /
-pos|neg layouts).
+pos|neg layouts, and the 'wrd' weights of :538-556: ``1/(1+e^(alpha(d-beta)))`` then
+``1/(1+e^(alpha(beta-d)))`` over the Euclidean anchor distances of positives then negatives,
+2(P+N) values).
 
 Deliberate differences, all on paths where the reference misbehaves:
   * an anchor without cached neighbours has no hard candidates (the reference would reuse
@@ -21,8 +23,7 @@ Deliberate differences, all on paths where the reference misbehaves:
   * the candidate scan uses a boolean mask instead of a Python list comprehension over the
     whole dataset per negative (same ascending candidate order, so the same RandomState
     reproduces the same draws).
-The weighted-ratio payloads ('wrd', 'swrd') belong to losses outside the hot path and are
-refused.
+The 'swrd' payload belongs to a loss outside the hot path (swrd_loss) and is refused.
 
 ``InputPipeline`` is the CPU_IN -> GPU_IN queue pair of train_cpu_thread (:226-260): a
 worker thread samples tuples and loads their images while the device trains.
@@ -38,7 +39,7 @@ class TupleSampler:
     def __init__(self, xy, yaw, positives_per_tuple=12, negatives_per_tuple=12,
                  max_pos_radius=15.0, min_neg_radius=15.0, hard_positives_per_tuple=6,
                  hard_negatives_per_tuple=6, mutually_exclusive_negs=True, distance_type='none',
-                 cache=None, mining_cache_size=1000, rng=None):
+                 cache=None, mining_cache_size=1000, rng=None, alpha=0.8, beta=15.0):
         from sklearn.neighbors import KDTree
         self.xy = np.asarray(xy, dtype=float)
         self.yaw = np.asarray(yaw, dtype=float)
@@ -47,12 +48,13 @@ class TupleSampler:
         self.max_pos_radius, self.min_neg_radius = max_pos_radius, min_neg_radius
         self.hard_p, self.hard_n = hard_positives_per_tuple, hard_negatives_per_tuple
         self.exclusive = mutually_exclusive_negs
-        if distance_type in ('wrd', 'swrd'):
-            raise ValueError("distance type %r belongs to losses outside the hot path"
+        if distance_type == 'swrd':
+            raise ValueError("distance type %r belongs to a loss outside the hot path"
                              % (distance_type,))
-        if distance_type not in ('none', 'anchor', 'pairwise', 'wms', 'logratio'):
+        if distance_type not in ('none', 'anchor', 'pairwise', 'wms', 'logratio', 'wrd'):
             raise ValueError("unknown distance type %r" % (distance_type,))
         self.distance_type = distance_type
+        self.alpha, self.beta = alpha, beta                       # ALPHA, BETA of the 'wrd' weights
         self.cache = cache
         self.cache_k = mining_cache_size
         self.rng = rng if rng is not None else np.random.RandomState(42)   # np.random.seed(42)
@@ -143,6 +145,14 @@ class TupleSampler:
             neg_loc = np.array([self.xy[int(i), :] for i in negatives], dtype=float)
             every = np.concatenate((pos_loc, neg_loc), 0)
             return pairwise_distances(every, every, metric='euclidean')
+        if dt == 'wrd':
+            neg_loc = np.array([self.xy[int(i), :] for i in negatives], dtype=float)
+            pos_d = np.squeeze(pairwise_distances(pos_loc[1:], anchor, metric='euclidean'))
+            neg_d = np.squeeze(pairwise_distances(neg_loc, anchor, metric='euclidean'))
+            d = np.concatenate((np.atleast_1d(pos_d), np.atleast_1d(neg_d)))
+            pos_w = 1 / (1 + math.e ** (self.alpha * (d - self.beta)))
+            neg_w = 1 / (1 + math.e ** (self.alpha * (self.beta - d)))
+            return np.array(np.concatenate((pos_w, neg_w)), dtype=float)
         neg_loc = np.array([self.xy[int(i), :] for i in negatives], dtype=float)      # logratio
         pos_d = np.squeeze(pairwise_distances(pos_loc[1:], anchor, metric='sqeuclidean'))
         neg_d = np.squeeze(pairwise_distances(neg_loc, anchor, metric='sqeuclidean'))

@@ -18,7 +18,9 @@ schedule (:118-121), the optimisers (:865-878) and the three checkpoint cadences
 * default: ``SyntheticTuples`` — random images with the per-loss ``distances`` payload the GPU
   thread receives (:263-275); what bench.py's workload looks like.
 
-The PCA threads and the eigenvalue / incremental-PCA losses stay out.
+The PCA threads and the eigenvalue / incremental-PCA losses stay out; of the
+residual-determinant family wrd, prodwrd and sumwrd are in (model/losses.py), swrd and
+residual_det are not.
 
     python -m soft_contrastive_learning_amd.train.train --loss wms --vlad_cores 64 \
         --reduction none --tuples_per_batch 1 --steps 20
@@ -172,7 +174,7 @@ SUPPORTED_LOSSES = ('triplet', 'lazy_triplet', 'evil_triplet', 'quadruplet', 'la
                     'distance_triplet', 'distance_lazy_triplet', 'distance_quadruplet',
                     'distance_lazy_quadruplet', 'huber_distance_triplet',
                     'huber_distance_lazy_triplet', 'huber_distance_quadruplet',
-                    'huber_distance_lazy_quadruplet')
+                    'huber_distance_lazy_quadruplet', 'wrd', 'prodwrd', 'sumwrd')
 
 
 def compute_loss(flags, tuple_shape, output, distances, local_rows=None, group=None):
@@ -222,6 +224,14 @@ def compute_loss(flags, tuple_shape, output, distances, local_rows=None, group=N
         # only d_alpha, d_beta, wfunction, sumfunction are forwarded (:851-852)
         return losses.wms_loss(distances, output, d_alpha=flags.alpha, d_beta=flags.beta,
                                wfunction=flags.wfunction, sumfunction=flags.sumfunction)
+    if loss in ('wrd', 'prodwrd', 'sumwrd'):
+        # distances [T, 2(P+N)]: the positive-side weights of all rows, then the negative-side
+        # ones (:677-681); only margin_1 is forwarded (:842-849)
+        others = flags.positives_per_tuple + flags.negatives_per_tuple
+        pos_w, neg_w = torch.split(distances.reshape(t, 2 * others, -1), [others, others], 1)
+        fn = {'wrd': losses.wrd_loss, 'prodwrd': losses.prodwrd_loss,
+              'sumwrd': losses.sumwrd_loss}[loss]
+        return fn(outs[0], outs[1], outs[2], pos_w, neg_w, flags.margin_1)
     if loss == 'logratio':
         p = flags.positives_per_tuple
         pos_d, neg_d = torch.split(distances.reshape(t, -1, 1), [p, flags.negatives_per_tuple], 1)
@@ -259,6 +269,13 @@ class SyntheticTuples:
             d = np.concatenate([self.rng.uniform(1, 15 ** 2, (t * self.world, p)),
                                 self.rng.uniform(15 ** 2, 200 ** 2, (t * self.world, n))],
                                1).astype(np.float32)[mine]
+        elif dtype == 'wrd':
+            # weights of the metres anchor -> positives, negatives (:538-556), [T, 2(P+N)]
+            p, n = f.positives_per_tuple, f.negatives_per_tuple
+            m = np.concatenate([self.rng.uniform(0.5, f.max_pos_radius, (t * self.world, p)),
+                                self.rng.uniform(f.min_neg_radius, 200.0, (t * self.world, n))], 1)
+            d = np.concatenate([1 / (1 + np.exp(f.alpha * (m - f.beta))),
+                                1 / (1 + np.exp(f.alpha * (f.beta - m)))], 1).astype(np.float32)[mine]
         elif f.loss == 'ms_loss':
             # labels built in build_model (:822-826), globally unique across ranks
             p = f.positives_per_tuple
@@ -362,7 +379,7 @@ def train_dataset_epoch(flags, epoch, state, log):
     t, s_img = flags.tuples_per_batch, flags.tuples_per_batch * sum(state['tuple_shape'])
     local_ref, local_query, other_ref, other_query = open_sets(flags, epoch)
     dtype = distance_type(flags.loss)
-    dtype = dtype if dtype in ('anchor', 'pairwise', 'wms', 'logratio') else 'none'
+    dtype = dtype if dtype in ('anchor', 'pairwise', 'wms', 'logratio', 'wrd') else 'none'
     cache = mining.MiningCache()
 
     def make_sampler(image_set, use_cache):
@@ -371,7 +388,8 @@ def train_dataset_epoch(flags, epoch, state, log):
                             flags.hard_positives_per_tuple, flags.hard_negatives_per_tuple,
                             flags.mutually_exclusive_negs, dtype, cache if use_cache else None,
                             flags.mining_cache_size,
-                            np.random.RandomState(42 + epoch if world == 1 else [42 + epoch, rank]))
+                            np.random.RandomState(42 + epoch if world == 1 else [42 + epoch, rank]),
+                            alpha=flags.alpha, beta=flags.beta)
     sampler = make_sampler(local_ref, True)
     other_sampler = make_sampler(other_ref, False)
     pipe = InputPipeline(sampler, local_ref.load_images, tuple_shape, use_hard_negatives=True,
