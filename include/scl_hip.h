@@ -694,6 +694,46 @@ int scl_spectral_loss_fwd(int kind, const float* z, const float* pos_w, const fl
                           float* coef_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Eigenvalue and residual losses (csrc/spectral_loss.hip) on the same float64 Gram and Jacobi
+ * solve as the spectral losses above, with a side-sized matrix per (tuple, side): the residual
+ * rows of that side alone (P x P, N x N) or the plain Gram of [anchor; side] ((P+1)^2, (N+1)^2).
+ * s(.) = singular values, largest first; k = dimensions; a = the anchor row.
+ *
+ *   kind  SCL_EIGEN_RESIDUAL_DET    term = prod of the k largest s(P - a) | s(N - a)
+ *                                   loss = mean_t(term_pos - term_neg) + margin   (model/losses.py:345-356)
+ *         SCL_EIGEN_RESIDUAL_TRACE  the same with the sum of the k largest          (:613-624)
+ *         SCL_EIGEN_SWRD            residual_det on diag(pos_w)(P - a), diag(neg_w)(N - a)  (:359-370)
+ *         SCL_EIGEN_NTUPLET_EVMM    term_pos = lambda_min(G[a;P]), term_neg = lambda_max(G[a;N]),
+ *                                   loss = mean_t max(margin + term_pos - term_neg, 0)  (:317-327)
+ *         SCL_EIGEN_NTUPLET_TRACE   the same with term = trace G[a;side]; no solve  (:331-341)
+ *         SCL_EIGEN_NEG_EIGENVALUE  term_neg = lambda_min(G[a;N]), term_pos = 0,
+ *                                   loss = -mean_t term_neg; margin is ignored      (:310-313)
+ *   z           [T, P+N+1, E] f32, contiguous: anchor, positives, negatives (P, N >= 1, P+N <= 32;
+ *               NEG_EIGENVALUE also takes P = 0, z = [anchor; negatives], with N <= 31)
+ *   pos_w       [T, P] f32, neg_w [T, N] f32: the row weights of SWRD (no gradient); may be NULL
+ *               for every other kind, which ignores them
+ *   dimensions  1 <= dimensions <= min(P, N) for the three residual kinds; ignored otherwise
+ *   loss_out    device scalar f32
+ *   terms_out   [T, 2] f64: term_pos, term_neg of every tuple
+ *   coef_out    [T, P+N+1, P+N+1] f32 or NULL: C with d loss / d z[t] = C z[t] (1/T included; a
+ *               tuple whose hinge is inactive gets zeros), consumed by scl_gram_loss_bwd
+ * A hinge argument of exactly 0 counts as active (TensorFlow's maximum sends the gradient to its
+ * first argument where x >= y).  Every sum has a fixed order (bit-reproducible).
+ * Returns SCL_E_NULL for a missing pointer (the weights for SWRD), SCL_E_KIND for an unknown kind,
+ * SCL_E_SHAPE for T, P, N, E or dimensions out of range, SCL_E_WORKSPACE; nothing is launched then.
+ * ------------------------------------------------------------------------- */
+#define SCL_EIGEN_RESIDUAL_DET 0
+#define SCL_EIGEN_RESIDUAL_TRACE 1
+#define SCL_EIGEN_SWRD 2
+#define SCL_EIGEN_NTUPLET_EVMM 3
+#define SCL_EIGEN_NTUPLET_TRACE 4
+#define SCL_EIGEN_NEG_EIGENVALUE 5
+size_t scl_eigen_loss_workspace_bytes(int T, int P, int N, int E);
+int scl_eigen_loss_fwd(int kind, const float* z, const float* pos_w, const float* neg_w, int T, int P,
+                       int N, int E, float margin, int dimensions, float* loss_out, double* terms_out,
+                       float* coef_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Host utility for the checkpoint bundle reader / writer (tf_bundle.py; the reference
  * restores and saves through tf.train.Saver, train/train.py:882-905, 984, 1079, 1102):
  * CRC-32C (Castagnoli, reflected 0x82F63B78) of n bytes continued from `crc` (0 to start),

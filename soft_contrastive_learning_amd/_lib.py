@@ -33,6 +33,8 @@ VLAD_SAVE_ROWS = 514      # save_vlad rows per image: U, asum, sync words of the
 TOPN_SCORE_F32, TOPN_SCORE_BF16X3 = 0, 1
 SPECTRAL_WRD, SPECTRAL_PRODWRD, SPECTRAL_SUMWRD = 0, 1, 2
 SPECTRAL_MAX_S = 32        # others (positives + negatives) per tuple of scl_spectral_loss_fwd
+EIGEN_RESIDUAL_DET, EIGEN_RESIDUAL_TRACE, EIGEN_SWRD = 0, 1, 2
+EIGEN_NTUPLET_EVMM, EIGEN_NTUPLET_TRACE, EIGEN_NEG_EIGENVALUE = 3, 4, 5
 CONV_TRANSPOSED, W_F32, W_PACKED = 1, 2, 4   # flag word of the convolution entry points
 PACK_VLAD_W = 16           # SclPackJob.flags: the job writes the NetVLAD plane images of assign_w
 
@@ -144,6 +146,8 @@ SIGNATURES = {
     "scl_spectral_loss_workspace_bytes": (_z, [_i, _i, _i]),
     "scl_spectral_loss_fwd": (_i, [_i, _p, _p, _p, _i, _i, _i, _f, _i, _f, _f, _f, _p, _p, _p, _p, _z,
                                    _p]),
+    "scl_eigen_loss_workspace_bytes": (_z, [_i, _i, _i, _i]),
+    "scl_eigen_loss_fwd": (_i, [_i, _p, _p, _p, _i, _i, _i, _i, _f, _i, _p, _p, _p, _p, _z, _p]),
 }
 
 _libs = {}

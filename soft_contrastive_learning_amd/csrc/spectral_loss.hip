@@ -28,6 +28,10 @@
 //   3. spectral_finish_kernel  coef = (C_pos - C_neg) / T in float32, loss = sum over tuples in
 //                              tuple order / T + margin.
 // Every sum has a fixed order: two calls on the same input return the same bits.
+//
+// The eigenvalue and residual losses (residual_det, residual_trace, swrd, ntuplet_evmm,
+// ntuplet_trace, neg_eigenvalue; model/losses.py:310-370, 613-624) take the same Gram pass and the
+// same Jacobi solve on a side-sized matrix: eigen_solve_kernel and eigen_finish_kernel below.
 #include "scl_common.h"
 
 namespace {
@@ -139,24 +143,9 @@ __device__ __forceinline__ void tournament_pair(int n2, int step, int k, int* p,
   *q = a < b ? b : a;
 }
 
-__global__ __launch_bounds__(kSolveThreads) void spectral_solve_kernel(
-    int kind, const double* __restrict__ part, int nslice, const float* __restrict__ pos_w,
-    const float* __restrict__ neg_w, int S, int T, int dimensions, float f_alpha_p, float f_alpha_n,
-    float f_lamb, double* __restrict__ prods_out, double* __restrict__ side_coef) {
-  __shared__ double Gs[kMaxRows * kLd];         // Gram of Z, full symmetric
-  __shared__ double A[kMaxS * kLd];             // W R W, then M0
-  __shared__ double V[kMaxS * kLd];             // eigenvectors in columns
-  __shared__ double w[kMaxS], dw[kMaxS], lam[kMaxS], dcoef[kMaxS], qv[kMaxS], rsum[kMaxS];
-  __shared__ double rot_c[kMaxS / 2], rot_s[kMaxS / 2];
-  __shared__ int rot_p[kMaxS / 2], rot_q[kMaxS / 2];
-  __shared__ int order[kMaxS];
-  __shared__ int rotated;
-
-  const int tid = threadIdx.x, side = blockIdx.x, t = blockIdx.y;
-  const int S1 = S + 1;
-  const int n2 = S + (S & 1), npairs = n2 / 2;
-
-  // ---- Gram: slice partials in slice order ----
+// Gs = the Gram of tuple t, full symmetric: the slice partials summed in slice order
+__device__ __forceinline__ void load_gram(const double* __restrict__ part, int t, int nslice, int S1,
+                                          double* Gs, int tid) {
   const double* pt = part + (int64_t)t * nslice * kPartial;
   for (int i = tid; i < S1 * S1; i += kSolveThreads) {
     const int r = i / S1, c = i - r * S1;
@@ -168,49 +157,19 @@ __global__ __launch_bounds__(kSolveThreads) void spectral_solve_kernel(
     Gs[r * kLd + c] = v;
     Gs[c * kLd + r] = v;
   }
+  __syncthreads();
+}
+
+// Cyclic Jacobi on the symmetric n2 x n2 matrix A (n2 even, row stride kLd) with V = I on entry:
+// on return A's diagonal holds the eigenvalues and V's columns the eigenvectors.  At most
+// kMaxSweeps sweeps; every thread of the workgroup calls it.
+__device__ __forceinline__ void jacobi_solve(double* A, double* V, int n2, int tid) {
+  __shared__ double rot_c[kMaxS / 2], rot_s[kMaxS / 2];
+  __shared__ int rot_p[kMaxS / 2], rot_q[kMaxS / 2];
+  __shared__ int rotated;
+  const int npairs = n2 / 2;
   if (tid == 0) rotated = 0;
   __syncthreads();
-
-  // ---- row weights of this side ----
-  if (tid < kMaxS) {
-    double wj = 0.0, dwj = 0.0;
-    if (tid < S) {
-      const double w0 = (double)(side == 0 ? pos_w : neg_w)[(int64_t)t * S + tid];
-      if (kind == 0) {
-        wj = w0;
-      } else {
-        const double sim = Gs[tid + 1];
-        const double slope = side == 0 ? (double)f_alpha_p : -(double)f_alpha_n;
-        const double f = 1.0 / (1.0 + exp(slope * (sim - (double)f_lamb)));
-        const double df = -f * (1.0 - f) * slope;
-        if (kind == 1) {
-          wj = w0 * f;
-          dwj = w0 * df;
-        } else {
-          wj = w0 + f;
-          dwj = df;
-        }
-      }
-    }
-    w[tid] = wj;
-    dw[tid] = dwj;
-  }
-  __syncthreads();
-
-  // ---- A = W R W (zero in the padding row of an odd S), V = I ----
-  for (int i = tid; i < n2 * n2; i += kSolveThreads) {
-    const int r = i / n2, c = i - r * n2;
-    double a = 0.0;
-    if (r < S && c < S) {
-      const double res = Gs[(r + 1) * kLd + c + 1] - Gs[(r + 1) * kLd] - Gs[c + 1] + Gs[0];
-      a = w[r] * res * w[c];
-    }
-    A[r * kLd + c] = a;
-    V[r * kLd + c] = r == c ? 1.0 : 0.0;
-  }
-  __syncthreads();
-
-  // ---- cyclic Jacobi, at most kMaxSweeps sweeps ----
   for (int sweep = 0; sweep < kMaxSweeps; ++sweep) {
     for (int step = 0; step < n2 - 1; ++step) {
       if (tid < npairs) {
@@ -264,6 +223,78 @@ __global__ __launch_bounds__(kSolveThreads) void spectral_solve_kernel(
     __syncthreads();
     if (!any) break;
   }
+}
+
+// order[r] = the index of the r-th largest of lam[0 .. n) (ties: the lower index first)
+__device__ __forceinline__ void rank_descending(const double* lam, int* order, int n, int tid) {
+  if (tid < n) {
+    const double li = lam[tid];
+    int rank = 0;
+    for (int j = 0; j < n; ++j) {
+      const double lj = lam[j];
+      rank += (lj > li || (lj == li && j < tid)) ? 1 : 0;
+    }
+    order[rank] = tid;
+  }
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(kSolveThreads) void spectral_solve_kernel(
+    int kind, const double* __restrict__ part, int nslice, const float* __restrict__ pos_w,
+    const float* __restrict__ neg_w, int S, int T, int dimensions, float f_alpha_p, float f_alpha_n,
+    float f_lamb, double* __restrict__ prods_out, double* __restrict__ side_coef) {
+  __shared__ double Gs[kMaxRows * kLd];         // Gram of Z, full symmetric
+  __shared__ double A[kMaxS * kLd];             // W R W, then M0
+  __shared__ double V[kMaxS * kLd];             // eigenvectors in columns
+  __shared__ double w[kMaxS], dw[kMaxS], lam[kMaxS], dcoef[kMaxS], qv[kMaxS], rsum[kMaxS];
+  __shared__ int order[kMaxS];
+
+  const int tid = threadIdx.x, side = blockIdx.x, t = blockIdx.y;
+  const int S1 = S + 1;
+  const int n2 = S + (S & 1);
+
+  load_gram(part, t, nslice, S1, Gs, tid);
+
+  // ---- row weights of this side ----
+  if (tid < kMaxS) {
+    double wj = 0.0, dwj = 0.0;
+    if (tid < S) {
+      const double w0 = (double)(side == 0 ? pos_w : neg_w)[(int64_t)t * S + tid];
+      if (kind == 0) {
+        wj = w0;
+      } else {
+        const double sim = Gs[tid + 1];
+        const double slope = side == 0 ? (double)f_alpha_p : -(double)f_alpha_n;
+        const double f = 1.0 / (1.0 + exp(slope * (sim - (double)f_lamb)));
+        const double df = -f * (1.0 - f) * slope;
+        if (kind == 1) {
+          wj = w0 * f;
+          dwj = w0 * df;
+        } else {
+          wj = w0 + f;
+          dwj = df;
+        }
+      }
+    }
+    w[tid] = wj;
+    dw[tid] = dwj;
+  }
+  __syncthreads();
+
+  // ---- A = W R W (zero in the padding row of an odd S), V = I ----
+  for (int i = tid; i < n2 * n2; i += kSolveThreads) {
+    const int r = i / n2, c = i - r * n2;
+    double a = 0.0;
+    if (r < S && c < S) {
+      const double res = Gs[(r + 1) * kLd + c + 1] - Gs[(r + 1) * kLd] - Gs[c + 1] + Gs[0];
+      a = w[r] * res * w[c];
+    }
+    A[r * kLd + c] = a;
+    V[r * kLd + c] = r == c ? 1.0 : 0.0;
+  }
+  __syncthreads();
+
+  jacobi_solve(A, V, n2, tid);
 
   // ---- the k largest eigenvalues, their product, d prod / d s_i / s_i ----
   if (tid < kMaxS) {
@@ -271,16 +302,7 @@ __global__ __launch_bounds__(kSolveThreads) void spectral_solve_kernel(
     order[tid] = 0;                             // (stays in range whatever the comparisons say)
   }
   __syncthreads();
-  if (tid < S) {
-    const double li = lam[tid];
-    int rank = 0;
-    for (int j = 0; j < S; ++j) {
-      const double lj = lam[j];
-      rank += (lj > li || (lj == li && j < tid)) ? 1 : 0;
-    }
-    order[rank] = tid;
-  }
-  __syncthreads();
+  rank_descending(lam, order, S, tid);
   if (tid < S) {
     int rank = -1;
     for (int r = 0; r < dimensions; ++r)
@@ -359,6 +381,190 @@ __global__ __launch_bounds__(256) void spectral_finish_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// The eigenvalue and residual losses on the same Gram (model/losses.py:310-370, 613-624).  What
+// differs from wrd is the matrix of a side and the function of its eigenvalues:
+//   residual kinds   W R W over the side's own rows (P x P or N x N), w = 1 except for swrd
+//   Gram kinds       the plain Gram block of the rows {0} u side ((P + 1)^2 or (N + 1)^2 <= 32^2)
+// and a diagonal d with the side's coefficient block M = U diag(d) U^T:
+//   det / swrd   term = prod of the k largest s_i,  d_i = (prod_{l != i} s_l) / s_i in the top k
+//   trace        term = sum of the k largest s_i,   d_i = 1 / s_i in the top k
+//   l_min/l_max  term = that eigenvalue,            d_i = 2 at its index
+//   tr(Gram)     term = sum_i G_ii, no solve,       d_i = 2 everywhere (M = 2 I)
+// (s_i = sqrt(lambda_i); an exactly zero s_i gives no term, as in spectral_solve_kernel).
+// Workgroup = (side, tuple); neg_eigenvalue launches the negative side only (side0 = 1).
+__global__ __launch_bounds__(kSolveThreads) void eigen_solve_kernel(
+    int kind, const double* __restrict__ part, int nslice, const float* __restrict__ pos_w,
+    const float* __restrict__ neg_w, int P, int N, int dimensions, int side0,
+    double* __restrict__ terms_out, double* __restrict__ side_coef) {
+  __shared__ double Gs[kMaxRows * kLd];         // Gram of Z, full symmetric
+  __shared__ double A[kMaxS * kLd];             // the side's matrix, then M
+  __shared__ double V[kMaxS * kLd];             // eigenvectors in columns
+  __shared__ double w[kMaxS], lam[kMaxS], dcoef[kMaxS], rsum[kMaxS];
+  __shared__ int order[kMaxS];
+
+  const int tid = threadIdx.x, side = blockIdx.x + side0, t = blockIdx.y;
+  const int S1 = P + N + 1;
+  const bool residual = kind <= SCL_EIGEN_SWRD;
+  const int m = side == 0 ? P : N;              // this side's rows of Z are off + 1 .. off + m
+  const int off = side == 0 ? 0 : P;
+  const int n = residual ? m : m + 1;           // the Gram kinds take the anchor as row 0
+  const int n2 = n + (n & 1);
+
+  load_gram(part, t, nslice, S1, Gs, tid);
+
+  if (tid < kMaxS) {
+    double wj = 0.0;
+    if (tid < m)
+      wj = kind == SCL_EIGEN_SWRD ? (double)(side == 0 ? pos_w : neg_w)[(int64_t)t * m + tid] : 1.0;
+    w[tid] = wj;
+  }
+  __syncthreads();
+
+  // ---- the side's matrix (zero in the padding row of an odd n), V = I ----
+  for (int i = tid; i < n2 * n2; i += kSolveThreads) {
+    const int r = i / n2, c = i - r * n2;
+    double a = 0.0;
+    if (r < n && c < n) {
+      if (residual) {
+        const int gi = off + 1 + r, gj = off + 1 + c;
+        const double res = Gs[gi * kLd + gj] - Gs[gi * kLd] - Gs[gj] + Gs[0];
+        a = w[r] * res * w[c];
+      } else {
+        a = Gs[(r == 0 ? 0 : off + r) * kLd + (c == 0 ? 0 : off + c)];
+      }
+    }
+    A[r * kLd + c] = a;
+    V[r * kLd + c] = r == c ? 1.0 : 0.0;
+  }
+  __syncthreads();
+
+  if (kind != SCL_EIGEN_NTUPLET_TRACE) jacobi_solve(A, V, n2, tid);   // the trace: diagonal only
+
+  if (tid < kMaxS) {
+    lam[tid] = tid < n ? A[tid * kLd + tid] : 0.0;
+    order[tid] = 0;                             // (stays in range whatever the comparisons say)
+  }
+  __syncthreads();
+  rank_descending(lam, order, n, tid);
+
+  // ---- the term and d ----
+  const bool det = kind == SCL_EIGEN_RESIDUAL_DET || kind == SCL_EIGEN_SWRD;
+  // index of the one eigenvalue of evmm / neg_eigenvalue: l_min, but l_max on evmm's negative side
+  const int pick = order[(kind == SCL_EIGEN_NTUPLET_EVMM && side == 1) ? 0 : n - 1];
+  if (tid < n) {
+    double d = 0.0;
+    if (residual) {
+      int rank = -1;
+      for (int r = 0; r < dimensions; ++r)
+        if (order[r] == tid) rank = r;
+      if (rank >= 0) {
+        double others = 1.0;                    // det: the other singular values, largest first
+        if (det)
+          for (int r = 0; r < dimensions; ++r)
+            if (r != rank) others *= sqrt(fmax(lam[order[r]], 0.0));
+        const double si = sqrt(fmax(lam[tid], 0.0));
+        d = si > 0.0 ? others / si : 0.0;       // an exactly zero singular value: no term
+      }
+    } else if (kind == SCL_EIGEN_NTUPLET_TRACE || tid == pick) {
+      d = 2.0;
+    }
+    dcoef[tid] = d;
+  }
+  if (tid == 0) {
+    double term;
+    if (det) {
+      term = 1.0;
+      for (int r = 0; r < dimensions; ++r) term *= sqrt(fmax(lam[order[r]], 0.0));
+    } else if (kind == SCL_EIGEN_RESIDUAL_TRACE) {
+      term = 0.0;
+      for (int r = 0; r < dimensions; ++r) term += sqrt(fmax(lam[order[r]], 0.0));
+    } else if (kind == SCL_EIGEN_NTUPLET_TRACE) {
+      term = 0.0;
+      for (int j = 0; j < n; ++j) term += lam[j];
+    } else {
+      term = lam[pick];
+    }
+    terms_out[(int64_t)t * 2 + side] = term;
+    if (kind == SCL_EIGEN_NEG_EIGENVALUE) terms_out[(int64_t)t * 2] = 0.0;
+  }
+  __syncthreads();
+
+  // ---- M = U diag(d) U^T over A ----
+  for (int i = tid; i < n * n; i += kSolveThreads) {
+    const int r = i / n, c = i - r * n;
+    double v = 0.0;
+    for (int e = 0; e < n; ++e) v += dcoef[e] * V[r * kLd + e] * V[c * kLd + e];
+    A[r * kLd + c] = v;
+  }
+  __syncthreads();
+  if (residual && tid < m) {                    // rsum_j = sum_l (W M W)_jl; M is symmetric
+    double rs = 0.0;
+    for (int l = 0; l < m; ++l) rs += A[tid * kLd + l] * w[l];
+    rsum[tid] = w[tid] * rs;
+  }
+  __syncthreads();
+
+  // ---- scatter into this side's (S+1)^2 block of C: residual kinds C[I,I] += W M W,
+  // C[I,0] -= rowsum, C[0,I] -= colsum, C[0,0] += sum; Gram kinds C[J,J] += M, J = {0} u I ----
+  double* cs = side_coef + ((int64_t)t * 2 + side) * kCoef;
+  for (int i = tid; i < S1 * S1; i += kSolveThreads) {
+    const int r = i / S1, c = i - r * S1;
+    const int lr = r - 1 - off, lc = c - 1 - off;          // side-local row numbers of r, c > 0
+    const bool in_r = r > 0 && lr >= 0 && lr < m, in_c = c > 0 && lc >= 0 && lc < m;
+    double v = 0.0;
+    if (residual) {
+      if (in_r && in_c) {
+        v = w[lr] * A[lr * kLd + lc] * w[lc];
+      } else if (in_r && c == 0) {
+        v = -rsum[lr];
+      } else if (r == 0 && in_c) {
+        v = -rsum[lc];
+      } else if (r == 0 && c == 0) {
+        for (int j = 0; j < m; ++j) v += rsum[j];
+      }
+    } else if ((r == 0 || in_r) && (c == 0 || in_c)) {
+      v = A[(r == 0 ? 0 : lr + 1) * kLd + (c == 0 ? 0 : lc + 1)];
+    }
+    cs[i] = v;
+  }
+}
+
+// float64, tuple order.  The hinge of ntuplet_evmm / ntuplet_trace is active at an argument >= 0:
+// TensorFlow's maximum(x, y) sends the gradient to x where x >= y, so a tie at exactly 0 still
+// passes the gradient (and adds 0 to the loss).
+__global__ __launch_bounds__(256) void eigen_finish_kernel(
+    int kind, const double* __restrict__ terms, const double* __restrict__ side_coef, int T, int S1,
+    float margin, float* __restrict__ loss_out, float* __restrict__ coef_out) {
+  const int t = blockIdx.x;
+  const bool hinge = kind == SCL_EIGEN_NTUPLET_EVMM || kind == SCL_EIGEN_NTUPLET_TRACE;
+  if (coef_out) {
+    const double* cp = side_coef + (int64_t)t * 2 * kCoef;
+    const double* cn = cp + kCoef;
+    float* dst = coef_out + (int64_t)t * S1 * S1;
+    const bool active = !hinge || (double)margin + terms[2 * t] - terms[2 * t + 1] >= 0.0;
+    for (int i = threadIdx.x; i < S1 * S1; i += blockDim.x) {
+      double v = 0.0;
+      if (kind == SCL_EIGEN_NEG_EIGENVALUE) {
+        v = -cn[i] / (double)T;
+      } else if (active) {
+        v = (cp[i] - cn[i]) / (double)T;
+      }
+      dst[i] = (float)v;
+    }
+  }
+  if (t == 0 && threadIdx.x == 0) {
+    double sum = 0.0;
+    for (int i = 0; i < T; ++i) {
+      const double diff = terms[2 * i] - terms[2 * i + 1];
+      sum += hinge ? fmax((double)margin + diff, 0.0) : diff;
+    }
+    double loss = sum / (double)T;
+    if (kind <= SCL_EIGEN_SWRD) loss += (double)margin;
+    *loss_out = (float)loss;
+  }
+}
+
 bool valid_shape(int T, int S, int E) { return T >= 1 && T <= 65535 && S >= 1 && S <= kMaxS && E >= 1; }
 int slices(int E) { return (E + kSlice - 1) / kSlice; }
 size_t partial_bytes(int T, int E) { return scl_round256((size_t)T * slices(E) * kPartial * sizeof(double)); }
@@ -391,5 +597,41 @@ extern "C" int scl_spectral_loss_fwd(int kind, const float* z, const float* pos_
              f_lamb, prods_out, side_coef);
   SCL_LAUNCH("spectral_finish_kernel", spectral_finish_kernel, dim3(T), dim3(256), 0, st,
              (const double*)prods_out, (const double*)side_coef, T, S + 1, margin, loss_out, coef_out);
+  return scl_launch_status();
+}
+
+extern "C" size_t scl_eigen_loss_workspace_bytes(int T, int P, int N, int E) {
+  if (P < 0 || N < 1 || !valid_shape(T, (P > 0 ? P : 1) + N, E)) return 0;
+  return scl_spectral_loss_workspace_bytes(T, (P > 0 ? P : 1) + N, E);
+}
+
+extern "C" int scl_eigen_loss_fwd(int kind, const float* z, const float* pos_w, const float* neg_w,
+                                  int T, int P, int N, int E, float margin, int dimensions,
+                                  float* loss_out, double* terms_out, float* coef_out,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+  if (!z || !loss_out || !terms_out || !workspace) return SCL_E_NULL;
+  if (kind < SCL_EIGEN_RESIDUAL_DET || kind > SCL_EIGEN_NEG_EIGENVALUE) return SCL_E_KIND;
+  if (kind == SCL_EIGEN_SWRD && (!pos_w || !neg_w)) return SCL_E_NULL;
+  // neg_eigenvalue has no positive side: P = 0 is its shape alone, and N + 1 rows must fit
+  const int min_p = kind == SCL_EIGEN_NEG_EIGENVALUE ? 0 : 1;
+  if (P < min_p || N < 1 || P > kMaxS || N > kMaxS || !valid_shape(T, (P > 0 ? P : 1) + N, E))
+    return SCL_E_SHAPE;
+  // the residual kinds take the `dimensions` largest of a side's min(rows, E) singular values
+  if (kind <= SCL_EIGEN_SWRD && (dimensions < 1 || dimensions > (P < N ? P : N))) return SCL_E_SHAPE;
+  if (!scl_aligned256(workspace) || workspace_bytes < scl_eigen_loss_workspace_bytes(T, P, N, E))
+    return SCL_E_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const int nslice = slices(E);
+  const int side0 = kind == SCL_EIGEN_NEG_EIGENVALUE ? 1 : 0;
+  double* part = static_cast<double*>(workspace);
+  double* side_coef = reinterpret_cast<double*>(static_cast<char*>(workspace) + partial_bytes(T, E));
+  SCL_LAUNCH("spectral_gram_kernel", spectral_gram_kernel, dim3(nslice, T), dim3(kGramThreads), 0, st,
+             z, P + N + 1, E, nslice, part);
+  SCL_LAUNCH("eigen_solve_kernel", eigen_solve_kernel, dim3(2 - side0, T), dim3(kSolveThreads), 0, st,
+             kind, (const double*)part, nslice, pos_w, neg_w, P, N, dimensions, side0, terms_out,
+             side_coef);
+  SCL_LAUNCH("eigen_finish_kernel", eigen_finish_kernel, dim3(T), dim3(256), 0, st, kind,
+             (const double*)terms_out, (const double*)side_coef, T, P + N + 1, margin, loss_out,
+             coef_out);
   return scl_launch_status();
 }

@@ -16,6 +16,9 @@ and backward are the hand-written gfx950 kernels behind ``include/scl_hip.h``.
   _pairwise_squared_distances  model/losses.py:656-661
   pairwise_distance_loss       model/losses.py:627-646
   wrd_loss / prodwrd_loss / sumwrd_loss       model/losses.py:373-437
+  residual_det_loss / swrd_loss / residual_trace_loss   model/losses.py:345-370, 613-624
+  ntuplet_evmm_loss / ntuplet_trace_loss / neg_eigenvalue_loss   model/losses.py:310-341
+  ms_sum                 model/losses.py:188-194
 The pointnetvlad_cls losses the trainer imports beside them (train/train.py:25)
 live in ``soft_contrastive_learning_amd.pointnetvlad_cls``.
 """
@@ -27,7 +30,8 @@ __all__ = ['wms_loss', 'ms_loss', 'ms_det', 'logratio_loss', 'evil_triplet_loss'
            'evil_quadruplet_loss', 'worst_pos_distance', '_pairwise_squared_distances',
            'distance_loss', 'huber_distance_loss', 'distance_triplet_loss',
            'distance_quadruplet_loss', 'pairwise_distance_loss', 'wrd_loss', 'prodwrd_loss',
-           'sumwrd_loss']
+           'sumwrd_loss', 'residual_det_loss', 'residual_trace_loss', 'swrd_loss',
+           'ntuplet_evmm_loss', 'ntuplet_trace_loss', 'neg_eigenvalue_loss', 'ms_sum']
 
 
 def _as_f32(t):
@@ -585,3 +589,134 @@ def sumwrd_loss(anchor, positives, negatives, pos_weights, neg_weights, margin, 
     """model/losses.py:416-437: wrd with that sigmoid added to every row weight."""
     return _spectral(L.SPECTRAL_SUMWRD, anchor, positives, negatives, pos_weights, neg_weights,
                      margin, dimensions, f_alpha_p, f_alpha_n, f_lamb, return_products)
+
+
+# ------------------------------------------------- eigenvalue and residual losses
+class _EigenLoss(torch.autograd.Function):
+    """The side-sized spectral losses on Z = [anchor; positives; negatives]; see
+    eigen_solve_kernel in csrc/spectral_loss.hip.  Returns (loss, terms [T,2] float64); the backward
+    is ``scl_gram_loss_bwd`` per tuple on the coefficient matrices the forward leaves."""
+
+    @staticmethod
+    def forward(ctx, z, pos_w, neg_w, kind, p, margin, dimensions):
+        lib = L.load()
+        t, s1, e = z.shape
+        n = s1 - 1 - p
+        need_grad = ctx.needs_input_grad[0]
+        loss = torch.empty((), dtype=torch.float32, device=z.device)
+        terms = torch.empty((t, 2), dtype=torch.float64, device=z.device)
+        coef = torch.empty((t, s1, s1), dtype=torch.float32, device=z.device) if need_grad else None
+        nbytes = lib.scl_eigen_loss_workspace_bytes(t, p, n, e)
+        if nbytes == 0:
+            raise ValueError("unsupported tuple shape T=%d P=%d N=%d E=%d" % (t, p, n, e))
+        ws = L.workspace(nbytes, z.device)
+        L.check(lib.scl_eigen_loss_fwd(
+            kind, L.ptr(z), L.ptr(pos_w), L.ptr(neg_w), t, p, n, e, float(margin), int(dimensions),
+            L.ptr(loss), L.ptr(terms), L.ptr(coef), L.ptr(ws), ws.numel(), L.stream_of(z)))
+        if need_grad:
+            ctx.save_for_backward(z, coef)
+        ctx.mark_non_differentiable(terms)
+        return loss, terms
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_terms):
+        lib = L.load()
+        z, coef = ctx.saved_tensors
+        t, s1, e = z.shape
+        g = _as_f32(grad_loss).contiguous()
+        grad = torch.empty_like(z)
+        for k in range(t):
+            L.check(lib.scl_gram_loss_bwd(L.ptr(z[k]), e, s1, e, L.ptr(coef[k]), L.ptr(g), 0, s1,
+                                          L.ptr(grad[k]), e, L.stream_of(z)))
+        return (grad,) + (None,) * 6
+
+
+_RESIDUAL_KINDS = (L.EIGEN_RESIDUAL_DET, L.EIGEN_RESIDUAL_TRACE, L.EIGEN_SWRD)
+
+
+def _eigen(kind, anchor, positives, negatives, margin, dimensions=1, pos_weights=None,
+           neg_weights=None, return_terms=False):
+    """Validation (ValueError before any launch) and dispatch; ``positives`` is None for
+    neg_eigenvalue, whose Z is [anchor; negatives]."""
+    rows = [('anchor', anchor), ('negatives', negatives)]
+    if positives is not None:
+        rows.insert(1, ('positives', positives))
+    for name, x in rows:
+        if not isinstance(x, torch.Tensor) or x.dim() != 3:
+            raise ValueError("%s must be rank 3 [T,R,E]" % name)
+    t, n, e = negatives.shape
+    p = 0 if positives is None else positives.shape[1]
+    count = {'anchor': 1, 'positives': p, 'negatives': n}
+    if any(tuple(x.shape) != (t, count[name], e) for name, x in rows):
+        raise ValueError("inconsistent tuple shapes " + " ".join(
+            "%s%s" % (name, tuple(x.shape)) for name, x in rows))
+    if n < 1 or (positives is not None and p < 1):
+        raise ValueError("need at least one positive and one negative per tuple, got %d and %d" % (p, n))
+    if max(p, 1) + n > L.SPECTRAL_MAX_S:         # [anchor; negatives] alone has N + 1 rows
+        raise ValueError("positives + negatives = %d above the kernel's cap of %d"
+                         % (max(p, 1) + n, L.SPECTRAL_MAX_S))
+    dimensions = int(dimensions)
+    if kind in _RESIDUAL_KINDS and (dimensions < 1 or dimensions > min(p, n)):
+        # a side has min(rows, E) singular values: the reference's tf.slice fails beyond them
+        raise ValueError("dimensions must be in 1..min(positives, negatives) = %d, got %d"
+                         % (min(p, n), dimensions))
+    pw = nw = None
+    if kind == L.EIGEN_SWRD:
+        pw = _side_weights(pos_weights, t, p, 'pos_weights')
+        nw = _side_weights(neg_weights, t, n, 'neg_weights')
+    L.require_device(*([x for _, x in rows] + [pw, nw]))
+    z = torch.cat([_as_f32(x) for _, x in rows], dim=1)
+    loss, terms = _EigenLoss.apply(z, pw, nw, kind, p, margin, dimensions)
+    return (loss, terms) if return_terms else loss
+
+
+def residual_det_loss(anchor, positives, negatives, margin, dimensions=10, return_terms=False):
+    """model/losses.py:345-356: per tuple the product of the ``dimensions`` largest singular values
+    of the positives' residual rows ``x_j - anchor`` minus the same over the negatives', plus
+    ``margin``; mean over tuples.  ``return_terms=True`` also returns the [T,2] float64 products
+    (the loss alone hides them behind the margin)."""
+    return _eigen(L.EIGEN_RESIDUAL_DET, anchor, positives, negatives, margin, dimensions,
+                  return_terms=return_terms)
+
+
+def residual_trace_loss(anchor, positives, negatives, margin, dimensions=10, return_terms=False):
+    """model/losses.py:613-624: residual_det_loss with the sum of the singular values in place of
+    their product; the terms are the two sums."""
+    return _eigen(L.EIGEN_RESIDUAL_TRACE, anchor, positives, negatives, margin, dimensions,
+                  return_terms=return_terms)
+
+
+def swrd_loss(anchor, positives, negatives, pos_weights, neg_weights, margin, dimensions=10,
+              return_terms=False):
+    """model/losses.py:359-370: residual_det_loss on the residual rows scaled by ``pos_weights``
+    ([T,P,1] or [T,P]) and ``neg_weights`` ([T,N,1] or [T,N]); the weights carry no gradient."""
+    return _eigen(L.EIGEN_SWRD, anchor, positives, negatives, margin, dimensions, pos_weights,
+                  neg_weights, return_terms)
+
+
+def ntuplet_evmm_loss(anchor, positives, negatives, margin, return_terms=False):
+    """model/losses.py:317-327: mean over tuples of max(margin + lambda_min(G[anchor; positives]) -
+    lambda_max(G[anchor; negatives]), 0), G = F F^T.  The terms are the two eigenvalues."""
+    return _eigen(L.EIGEN_NTUPLET_EVMM, anchor, positives, negatives, margin,
+                  return_terms=return_terms)
+
+
+def ntuplet_trace_loss(anchor, positives, negatives, margin, return_terms=False):
+    """model/losses.py:331-341: ntuplet_evmm_loss with the trace of each Gram in place of its
+    extreme eigenvalue; the terms are the two traces."""
+    return _eigen(L.EIGEN_NTUPLET_TRACE, anchor, positives, negatives, margin,
+                  return_terms=return_terms)
+
+
+def neg_eigenvalue_loss(anchor, negatives, return_terms=False):
+    """model/losses.py:310-313: minus the mean over tuples of lambda_min(G[anchor; negatives]).
+    The terms hold that eigenvalue in column 1 and 0 in column 0."""
+    return _eigen(L.EIGEN_NEG_EIGENVALUE, anchor, None, negatives, 0.0, return_terms=return_terms)
+
+
+def ms_sum(anchor, positives, negatives, margin, labels, embeddings, alpha=2.0, beta=50.0, lamb=1.0,
+           eps=0.1, ms_mining=False, dimensions=10):
+    """model/losses.py:188-194: 5 ms_loss + residual_det_loss."""
+    ms = ms_loss(labels, embeddings, alpha, beta, lamb, eps, ms_mining)
+    res = residual_det_loss(anchor, positives, negatives, margin, dimensions)
+    return ms * 5.0 + res

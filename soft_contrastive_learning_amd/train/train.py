@@ -18,9 +18,17 @@ schedule (:118-121), the optimisers (:865-878) and the three checkpoint cadences
 * default: ``SyntheticTuples`` — random images with the per-loss ``distances`` payload the GPU
   thread receives (:263-275); what bench.py's workload looks like.
 
-The PCA threads and the eigenvalue / incremental-PCA losses stay out; of the
-residual-determinant family wrd, prodwrd and sumwrd are in (model/losses.py), swrd and
-residual_det are not.
+Of the eigenvalue and residual-determinant families wrd, prodwrd, sumwrd, residual_trace,
+ntuplet_evmm, ntuplet_trace and ms_sum train here (model/losses.py).  Still refused:
+
+* ``--loss residual_det``, ``--loss swrd`` and the sampler's ``'swrd'`` payload: the loss functions
+  exist (``residual_det_loss``, ``swrd_loss``) and ms_sum trains through the first, but the two
+  names are not switched on in the trainer yet;
+* ``pairwise_distance_neg_eigenvalue`` and ``pairwise_huber_distance_neg_eigenvalue``: the
+  reference trains them with two ``optimizer.minimize`` calls per batch (PN_LOSS, :872-875), which
+  changes the training step; ``neg_eigenvalue_loss`` is the part of them that exists;
+* the ``incremental_*`` losses and ``ms_det``: stateful incremental PCA (and its PCA threads,
+  SURVEY.md §2).
 
     python -m soft_contrastive_learning_amd.train.train --loss wms --vlad_cores 64 \
         --reduction none --tuples_per_batch 1 --steps 20
@@ -174,7 +182,32 @@ SUPPORTED_LOSSES = ('triplet', 'lazy_triplet', 'evil_triplet', 'quadruplet', 'la
                     'distance_triplet', 'distance_lazy_triplet', 'distance_quadruplet',
                     'distance_lazy_quadruplet', 'huber_distance_triplet',
                     'huber_distance_lazy_triplet', 'huber_distance_quadruplet',
-                    'huber_distance_lazy_quadruplet', 'wrd', 'prodwrd', 'sumwrd')
+                    'huber_distance_lazy_quadruplet', 'wrd', 'prodwrd', 'sumwrd',
+                    'residual_trace', 'ntuplet_evmm', 'ntuplet_trace', 'ms_sum')
+
+# losses that take the reference's default ``dimensions = 10`` singular values of EACH side
+SIDE_DIMENSIONS_LOSSES = ('residual_trace', 'ms_sum')
+SIDE_DIMENSIONS = 10
+
+
+def check_tuple_sizes(flags):
+    """Refuse, before the first step, a tuple whose sides have fewer rows than the loss takes
+    singular values (the reference's tf.slice fails in the first session run)."""
+    if flags.loss in SIDE_DIMENSIONS_LOSSES:
+        for name in ('positives_per_tuple', 'negatives_per_tuple'):
+            if getattr(flags, name) < SIDE_DIMENSIONS:
+                raise SystemExit('--loss %s takes the %d largest singular values of each side: --%s %d is '
+                                 'below %d' % (flags.loss, SIDE_DIMENSIONS, name, getattr(flags, name),
+                                               SIDE_DIMENSIONS))
+
+
+def tuple_labels(flags, tuples, first=0):
+    """The class labels of ms_loss / ms_sum (train/train.py:822-826, 830-834) for ``tuples``
+    tuples, numbered from tuple ``first``: 0 for the anchor and its positives, one class per
+    negative, shifted by negatives_per_tuple + 1 per tuple."""
+    one = np.concatenate((np.zeros(1 + flags.positives_per_tuple),
+                          np.arange(flags.negatives_per_tuple) + 1))
+    return np.concatenate([one + (k + first) * (flags.negatives_per_tuple + 1) for k in range(tuples)])
 
 
 def compute_loss(flags, tuple_shape, output, distances, local_rows=None, group=None):
@@ -187,6 +220,13 @@ def compute_loss(flags, tuple_shape, output, distances, local_rows=None, group=N
             return parallel.wms_loss_dp(distances, output, flags.alpha, flags.beta, group=group,
                                         wfunction=flags.wfunction, sumfunction=flags.sumfunction)
         return parallel.ms_loss_dp(distances, output, group=group, ms_mining=flags.msmining)
+    if loss == 'ms_sum' and group is not None:
+        # ms_loss on the gathered batch, residual_det on this rank's tuples (mean over ranks)
+        ms = parallel.ms_loss_dp(distances, output, group=group, ms_mining=flags.msmining)
+        outs = torch.split(output.reshape(t, s, -1), tuple_shape, dim=1)
+        det = parallel.tuple_loss_dp(losses.residual_det_loss(outs[0], outs[1], outs[2], flags.margin_1),
+                                     group)
+        return ms * 5.0 + det
     if group is not None and loss in SUPPORTED_LOSSES:
         # per-tuple losses shard by tuple: the local mean, then the mean over ranks
         return parallel.tuple_loss_dp(compute_loss(flags, tuple_shape, output, distances), group)
@@ -232,6 +272,13 @@ def compute_loss(flags, tuple_shape, output, distances, local_rows=None, group=N
         fn = {'wrd': losses.wrd_loss, 'prodwrd': losses.prodwrd_loss,
               'sumwrd': losses.sumwrd_loss}[loss]
         return fn(outs[0], outs[1], outs[2], pos_w, neg_w, flags.margin_1)
+    if loss in ('ntuplet_evmm', 'ntuplet_trace', 'residual_trace'):            # :780-791
+        fn = {'ntuplet_evmm': losses.ntuplet_evmm_loss, 'ntuplet_trace': losses.ntuplet_trace_loss,
+              'residual_trace': losses.residual_trace_loss}[loss]
+        return fn(outs[0], outs[1], outs[2], flags.margin_1)
+    if loss == 'ms_sum':                                                       # :829-837
+        return losses.ms_sum(outs[0], outs[1], outs[2], flags.margin_1, distances, output,
+                             ms_mining=flags.msmining)
     if loss == 'logratio':
         p = flags.positives_per_tuple
         pos_d, neg_d = torch.split(distances.reshape(t, -1, 1), [p, flags.negatives_per_tuple], 1)
@@ -276,12 +323,9 @@ class SyntheticTuples:
                                 self.rng.uniform(f.min_neg_radius, 200.0, (t * self.world, n))], 1)
             d = np.concatenate([1 / (1 + np.exp(f.alpha * (m - f.beta))),
                                 1 / (1 + np.exp(f.alpha * (f.beta - m)))], 1).astype(np.float32)[mine]
-        elif f.loss == 'ms_loss':
-            # labels built in build_model (:822-826), globally unique across ranks
-            p = f.positives_per_tuple
-            one = np.concatenate((np.zeros(1 + p), np.arange(f.negatives_per_tuple) + 1))
-            d = np.concatenate([one + k * (f.negatives_per_tuple + 1)
-                                for k in range(t * self.world)])
+        elif f.loss in ('ms_loss', 'ms_sum'):
+            # labels built in build_model (:822-826, 830-834), globally unique across ranks
+            d = tuple_labels(f, t * self.world)
         else:
             d = None
         dist_t = None if d is None else torch.as_tensor(d).to(self.dev)
@@ -290,14 +334,10 @@ class SyntheticTuples:
 
 def batch_distances(flags, distances, device, world=1, rank_offset=0):
     """The sampler's per-anchor payloads -> the tensor ``ops['distances']`` holds for the loss
-    (train/train.py:665-691); ms_loss takes the labels of :822-826 instead."""
+    (train/train.py:665-691); ms_loss and ms_sum take the labels of :822-826 / :830-834 instead."""
     t = flags.tuples_per_batch
-    if flags.loss == 'ms_loss':
-        one = np.concatenate((np.zeros(1 + flags.positives_per_tuple),
-                              np.arange(flags.negatives_per_tuple) + 1))
-        lab = np.concatenate([one + (k + rank_offset) * (flags.negatives_per_tuple + 1)
-                              for k in range(t * world)])
-        return torch.as_tensor(lab).to(device)
+    if flags.loss in ('ms_loss', 'ms_sum'):
+        return torch.as_tensor(tuple_labels(flags, t * world, rank_offset)).to(device)
     if distance_type(flags.loss) == 'none':
         return None
     return torch.as_tensor(np.asarray(distances, dtype=np.float32)).to(device)
@@ -434,7 +474,7 @@ def train_dataset_epoch(flags, epoch, state, log):
             xy = np.asarray(local_ref.xy, dtype=np.float64)[idx_all]
             dmat = np.sqrt(((xy[:, None] - xy[None]) ** 2).sum(2)).astype(np.float32)[None]
             payload = torch.as_tensor(dmat).to(dev)
-        elif flags.loss == 'ms_loss':
+        elif flags.loss in ('ms_loss', 'ms_sum'):
             payload = batch_distances(flags, distances, dev, world=world)   # globally unique labels
         else:
             payload = batch_distances(flags, distances, dev)
@@ -585,6 +625,7 @@ def main(argv=None):
                          % (flags.reduction, UNAVAILABLE_REDUCTIONS[flags.reduction]))
     if flags.vlad_cores not in (0, 64) or flags.reduction not in ('none',) + reduction.KINDS:
         raise SystemExit('only --vlad_cores 64 | 0 with --reduction none|1fc|2fc|3fc is on the hot path')
+    check_tuple_sizes(flags)
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
     local_rank = int(os.environ.get('LOCAL_RANK', '0'))
