@@ -379,9 +379,10 @@ int scl_conv3x3_fused(const void* x, const void* w, int64_t w_stride_k, int64_t 
                       void* pooled, void* workspace, size_t workspace_bytes, void* stream);
 
 /* The deeper layers (conv3_x .. conv5_x: cin % 32 == 0, kout % 128 == 0, up to 1024): weights
- * streamed through LDS, [12 / 8 / 6 x 40 pixel] x 128-channel workgroup tiles — csrc/convh.hip
- * (v_mfma_f32_16x16x32_bf16; cin % 64 == 0) or csrc/convg.hip (32x32x16; any cin % 32 == 0),
- * same results bit for bit.  Same arguments as scl_conv3x3_fused without the pooled output. */
+ * streamed through LDS, [12 / 8 / 6 x 40 pixel] x 128-channel workgroup tiles.  csrc/conv_lds.hip
+ * checks the arguments and chooses the kernel: csrc/convh.hip (v_mfma_f32_16x16x32_bf16) where
+ * cin % 64 == 0, else csrc/convg.hip (32x32x16; any cin % 32 == 0), same results bit for bit.
+ * Same arguments as scl_conv3x3_fused without the pooled output. */
 size_t scl_convg_workspace_bytes(int cin, int kout);
 int scl_convg(const void* x, const void* w, int64_t w_stride_k, int64_t w_stride_c,
               int64_t w_stride_h, int64_t w_stride_w, int transposed, int B, int H, int W,
@@ -606,8 +607,8 @@ int scl_build_is_diag(void);
  *   3006 / 3008 / 3012   LDS-weights convolution: pin the block height (6: 16x16x32 kernel only)
  *   3099          LDS-weights convolution: one tile per workgroup instead of persistent ones
  *   3100 + g      LDS-weights convolution: persistent grid of g + 1 groups of 8 * kout / 128
- *   40000 + v / 50000 + v  LDS-weights convolution: pin the v_mfma 32x32x16 kernel
- *                 (csrc/convg.hip) / the 16x16x32 kernel (csrc/convh.hip, the default), with
+ *   40000 + v / 50000 + v  LDS-weights convolution: csrc/conv_lds.hip pins the v_mfma 32x32x16
+ *                 kernel (csrc/convg.hip) / the 16x16x32 kernel (csrc/convh.hip, the default), with
  *                 v = 0 or one of the 3xxx values above — these two give CORRECT results
  *   60000 + bits  register-weights convolution: bit 0 no window staging after the first
  *                 tile, bit 1 no output stores, bit 2 (and 53040 for the LDS-weights kernel)

@@ -1760,8 +1760,6 @@ __global__ __launch_bounds__(64) void conv_first_davg_kernel(
 
 }  // namespace
 
-static int conv64_cus();
-
 #ifdef SCL_DIAG
 // the diagnostic variants (conv64_diag.hip): true when the variant owns the call, its status in *rc
 static bool conv3x3_diag(const void* x, const void* w, int64_t sk, int64_t sc, int64_t sh, int64_t sw,
@@ -1797,7 +1795,7 @@ int launch_conv3x3(const void* x, const void* w, int64_t sk, int64_t sc, int64_t
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_kernel<CIN, CIN, 3, 1, 0, GEO>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS);
   });
-  const int cus = conv64_cus() * (GEO ? 2 : 1);
+  const int cus = scl_conv_cus() * (GEO ? 2 : 1);
   const unsigned short* packed = (const unsigned short*)workspace;
   if (transposed & SCL_W_PACKED)
     packed = (const unsigned short*)w;                   // scl_conv_pack_batch wrote it
@@ -1946,14 +1944,6 @@ extern "C" int scl_conv64(const void* x, const void* w, int64_t w_stride_k, int6
                      64, 64, out, workspace, workspace_bytes, stream);
 }
 
-// CUs the persistent grids may fill: the hardware's count (asked once), minus the reserve AS IT
-// IS NOW — scl_set_reserve_cus may change between calls (bench.py tries 0 and 8 at N > 1)
-static int conv64_cus() {
-  const int n = scl_device_cus();      // per device (scl_common.h)
-  const int u = scl_usable_cus(n);
-  return u > 1024 ? 1024 : u;
-}
-
 static int wrw_splits(int C, int K, int tiles, int cus) {
   const int blocks = (C / 64) * (K / 64);
   int p = (cus + blocks - 1) / blocks;                 // about one workgroup per CU
@@ -2009,7 +1999,7 @@ static int wrw3x3_run(const void* x, const void* gz, const unsigned char* pidx, 
       return rc;
   }
 #endif
-  const int cus = conv64_cus();
+  const int cus = scl_conv_cus();
   // [64 c] x [128 k] blocks wherever the output channels allow (scl_debug_set_variant(2100)
   // pins the 64 x 64 variant); tile shape: wide, or tall where that pads the map less
   const int nkb = (kout % 128 == 0 && scl_variant() != 2100) ? 2 : 1;
@@ -2103,7 +2093,7 @@ extern "C" int scl_conv_first(const float* img, const float* avg, const void* w,
   if (!img || !avg || !w || !bias || !x0 || !y) return SCL_E_NULL;
   if (B < 1 || H < 1 || W < 1 || (int64_t)B * H * W > (int64_t)1 << 30) return SCL_E_SHAPE;
   if ((uintptr_t)y % 16) return SCL_E_SHAPE;
-  const int cus = conv64_cus();
+  const int cus = scl_conv_cus();
   const int tiles = B * ((H + TH - 1) / TH) * ((W + TW - 1) / TW);
   // (8 workgroups per CU although four are resident at a time: measured 337-348 us against
   // 351-361 with 4 — the tail is finer)
@@ -2147,7 +2137,7 @@ extern "C" int scl_conv_first_pool_idx(const float* img, const float* avg, const
     SCL_LAUNCH("conv3x3_pack_kernel", (conv3x3_pack_kernel<64, 64>),
                dim3(Cfg::NT * Cfg::KS * 512 / 256), dim3(256), 0, st, w2, w2_stride_k, w2_stride_c,
                w2_stride_h, w2_stride_w, w2_flags & SCL_W_F32, (unsigned short*)workspace);
-  const int cus = conv64_cus();
+  const int cus = scl_conv_cus();
   const int tiles = B * ((H + TH - 1) / TH) * ((W + TW - 1) / TW);
   SCL_LAUNCH("conv12_kernel", conv12_kernel, dim3(tiles < cus ? tiles : cus), dim3(512), kConv12Lds,
              st, img, avg, w1, w1_f32 ? 1 : 0, w1_stride_k, w1_stride_c, w1_stride_h, w1_stride_w,
@@ -2178,7 +2168,7 @@ extern "C" int scl_conv_first_wrw(const void* x0, const void* gz, int B, int H, 
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_first_wrw_kernel),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFirstWrwLds);
   });
-  const int cus = conv64_cus();
+  const int cus = scl_conv_cus();
   const int tiles = B * ((H + TH - 1) / TH) * ((W + TW - 1) / TW);
   const int grid = first_wrw_grid(tiles, cus);
   hipStream_t st = (hipStream_t)stream;
@@ -2224,7 +2214,7 @@ extern "C" int scl_conv3x3_masked_pooled_first_wrw(
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds);
   });
   hipStream_t st = (hipStream_t)stream;
-  const int cus = conv64_cus();
+  const int cus = scl_conv_cus();
   const unsigned short* packed = (const unsigned short*)workspace;
   const int transposed = (flags & (SCL_W_F32 | SCL_W_PACKED)) | SCL_CONV_TRANSPOSED;
   if (flags & SCL_W_PACKED)

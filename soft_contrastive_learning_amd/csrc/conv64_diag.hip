@@ -58,7 +58,7 @@ static bool wrw3x3_diag(const void* x, const void* gz, const unsigned char* pidx
     SCL_WRW_ATTR(16, 32, 2, 0) SCL_WRW_ATTR(16, 8, 2, 0) SCL_WRW_ATTR(16, 32, 2, 1) SCL_WRW_ATTR(16, 8, 2, 1)
 #undef SCL_WRW_ATTR
   });
-  const int cus = conv64_cus();
+  const int cus = scl_conv_cus();
   const int nkb = kout % 128 == 0 && dbg == 0 ? 2 : 1;   // (dbg != 0: 64 x 64 blocks and wide tiles)
   const int th_w = nkb == 1 ? 8 : 4, th_t = nkb == 1 ? 32 : 16;
   const int tiles_wide = B * ((H + th_w - 1) / th_w) * ((W + 31) / 32);

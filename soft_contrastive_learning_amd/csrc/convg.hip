@@ -2,6 +2,8 @@
 // channels, model/nets.py:44-63) on bf16 channels-last activations: forward and, with the
 // weights transposed and the taps flipped, backward-data.  The register-resident-weights
 // kernel of conv64.hip does not scale past 128 channels; here the weights stream through LDS.
+// Kernel (32x32x16 MFMA), pack kernel and launcher; conv_lds.hip owns the entry points, validates and
+// chooses: this kernel where cin % 64 != 0, or pinned by scl_debug_set_variant(40000 + v).
 //
 // Implicit GEMM on v_mfma_f32_32x32x16_bf16 with a large M tile so that a staged weight chunk
 // is reused by many pixels:
@@ -18,8 +20,8 @@
 //   * epilogue as conv64.hip: bf16 through a per-wave LDS transpose, optional bias (+ ReLU).
 #include <mutex>
 
+#include "conv_lds.h"
 #include "conv_pack_layout.h"
-#include "scl_common.h"
 
 namespace {
 
@@ -30,6 +32,7 @@ constexpr int GWC = BW + 4;                         // halo window: 42 columns u
                                                     // of an A fragment hits 16 different slots
 constexpr int CCH = 32;                             // channels per staged chunk
 constexpr int GPIX = CCH + 8;                       // bf16 per staged pixel / weight row (80 B)
+static_assert(CCH == 32 && GPIX == LDS_CONV_ROW, "scl_convg_workspace_bytes sizes this image");
 constexpr int NTHR = 512;                           // 8 waves: two per SIMD
 constexpr int NB = 128;                             // output channels per workgroup
 constexpr int GWT = NB * GPIX;                      // bf16 per weight buffer (5120)
@@ -354,47 +357,27 @@ __global__ __launch_bounds__(NTHR, 1) void convg_kernel(const unsigned short* __
 
 }  // namespace
 
-extern "C" size_t scl_convg_workspace_bytes(int cin, int kout) {
-  if (cin < 32 || kout < 128 || cin % 32 || kout % 128 || cin > 1024 || kout > 1024) return 0;
-  return scl_round256((size_t)9 * (cin / CCH) * kout * GPIX * sizeof(unsigned short));
+// c: validated by conv_lds.hip; the packed weights take the whole scl_convg_workspace_bytes
+template <int E, int BHV>
+static void convg_run(const LdsConvCall& c, const unsigned short* packed, const LdsConvGrid& g,
+                      int relu) {
+  SCL_LAUNCH("convg_kernel", (convg_kernel<E, BHV>), dim3(g.gsize), dim3(NTHR), GCfg<BHV>::LDS,
+             c.stream, (const unsigned short*)c.x, packed, c.B, c.H, c.W, c.cin, c.kout,
+             (unsigned short*)c.out, c.bias, relu, (const unsigned short*)c.mask,
+             (unsigned char*)c.pidx, g.vblocks);
+}
+template <int BHV>
+static void convg_epilogue(const LdsConvCall& c, const unsigned short* packed, const LdsConvGrid& g,
+                           int dbgbits) {
+  if (c.pidx) convg_run<3, BHV>(c, packed, g, 0);
+  else if (c.mask) convg_run<2, BHV>(c, packed, g, 0);
+  else if (c.bias) convg_run<1, BHV>(c, packed, g, c.relu ? 1 : 0);
+  else convg_run<0, BHV>(c, packed, g, dbgbits);
 }
 
-static int convg_cus() {
-  const int n = scl_device_cus();      // per device (scl_common.h)
-  return scl_usable_cus(n);
-}
-
-// Same contract as scl_conv3x3_fused / scl_conv3x3_masked (include/scl_hip.h) without the
-// pooled output, for cin % 32 == 0 and kout % 128 == 0.
-static int convg_dispatch(const void* x, const void* w, int64_t w_stride_k, int64_t w_stride_c,
-                          int64_t w_stride_h, int64_t w_stride_w, int transposed, int B, int H,
-                          int W, int cin, int kout, void* out, const float* bias, int relu,
-                          const void* mask, void* pidx, void* workspace, size_t workspace_bytes,
-                          void* stream) {
-  if (!x || !w || !out || !workspace) return SCL_E_NULL;
-  if (pidx && (!bias || mask)) return SCL_E_NULL;
-  if (mask && (bias || ((uintptr_t)mask % 16))) return SCL_E_NULL;
-  const size_t need = scl_convg_workspace_bytes(cin, kout);
-  if (need == 0 || B < 1 || H < 1 || W < 1 || (int64_t)B * H * W > (int64_t)1 << 30)
-    return SCL_E_SHAPE;
-  if (((uintptr_t)x % 16) || ((uintptr_t)out % 16)) return SCL_E_SHAPE;
-  if ((int64_t)B * H * W * cin >= (int64_t)1 << 31) return SCL_E_SHAPE;   // 32-bit offsets
-  if (!scl_aligned256(workspace) || workspace_bytes < need) return SCL_E_WORKSPACE;
-  // scl_debug_set_variant(40000 + v) pins this (32x32x16) kernel, 50000 + v the 16x16x32 one of
-  // convh.hip, each with the diagnostic variant v of the list below; plain v = the default kernel
-  int dv = scl_variant();
-  bool use_h = SCL_CONVH_DEFAULT;
-  if (dv >= 40000 && dv < 60000) {
-    use_h = dv >= 50000;
-    dv -= use_h ? 50000 : 40000;
-  }
-  if ((transposed & SCL_W_PACKED) && !(use_h && cin % 64 == 0))
-    return SCL_E_KIND;                       // packed images exist in convh.hip's layout only
-  if (use_h && (cin / 64) * 64 == cin)     // convh.hip walks the 32-channel chunks in pairs
-    return scl_convh_dispatch(x, w, w_stride_k, w_stride_c, w_stride_h, w_stride_w, transposed, B, H,
-                              W, cin, kout, out, bias, relu, mask, pidx, workspace, dv, stream);
+int convg_launch(const LdsConvCall& c) {
   static SclDeviceOnce once;
-  scl_call_once(once, [] {
+  scl_call_once(once, [] {        // (in the order the kernels are emitted: their code depends on it)
 #define SCL_CONVG_ATTR(E, BHV)                                                                 \
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&convg_kernel<E, BHV>),              \
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)GCfg<BHV>::LDS);
@@ -402,77 +385,22 @@ static int convg_dispatch(const void* x, const void* w, int64_t w_stride_k, int6
     SCL_CONVG_ATTR(0, 8) SCL_CONVG_ATTR(1, 8) SCL_CONVG_ATTR(2, 8) SCL_CONVG_ATTR(3, 8)
 #undef SCL_CONVG_ATTR
   });
-  hipStream_t st = (hipStream_t)stream;
-  unsigned short* packed = (unsigned short*)workspace;
-  const int64_t total = (int64_t)9 * (cin / CCH) * kout * GPIX;
+  const int dv = SCL_DIAG_ONLY(c.dv);
+  unsigned short* packed = (unsigned short*)c.workspace;
+  const int64_t total = (int64_t)9 * (c.cin / CCH) * c.kout * GPIX;
   SCL_LAUNCH("convg_pack_kernel", convg_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256),
-             0, st, w, w_stride_k, w_stride_c, w_stride_h, w_stride_w, transposed, cin, kout, packed);
+             0, c.stream, c.w, c.sk, c.sc, c.sh, c.sw, c.flags, c.cin, c.kout, packed);
   // block height: 12 rows, or 8 where the 12-row blocks would be too few or pad more
-  const int bx = (W + BW - 1) / BW, kb = kout / NB;
-  const int64_t wg12 = (int64_t)B * ((H + 11) / 12) * bx * kb, wg8 = (int64_t)B * ((H + 7) / 8) * bx * kb;
-  int cus = convg_cus();
+  const int bx = (c.W + BW - 1) / BW, kb = c.kout / NB;
+  const int64_t wg12 = (int64_t)c.B * ((c.H + 11) / 12) * bx * kb, wg8 = (int64_t)c.B * ((c.H + 7) / 8) * bx * kb;
+  const int cus = scl_conv_cus();
   // rounds of workgroups (one per CU) x rows per block = time in units of a block row
   const int64_t t12 = ((wg12 + cus - 1) / cus) * 12, t8 = ((wg8 + cus - 1) / cus) * 8;
   // scl_debug_set_variant(3012 / 3008) pins the block height (tests cover both variants)
   const bool low = dv == 3012 ? false : dv == 3008 ? true : t8 < t12;
   const int dbgbits = (dv >= 3001 && dv <= 3003) ? (dv & 3) << 1 : 0;
-  const int64_t pblocks = (low ? wg8 : wg12) / kb;
-  const int vblocks = (int)(((pblocks + 7) / 8) * 8 * kb);      // virtual grid (XCD-aware order)
-  // persistent workgroups: one per CU (160 KB of LDS each), a multiple of 8 kb so that the
-  // virtual blocks that share windows stay 8 apart; scl_debug_set_variant(3100 + g) pins the
-  // grid to g groups of 8 kb (tests: several tiles per workgroup on small shapes)
-  int groups = cus / (8 * kb) > 0 ? cus / (8 * kb) : 1;
-  if (dv >= 3100 && dv < 3200) groups = dv - 3100 + 1;
-  int gsize = groups * 8 * kb;
-  if (gsize > vblocks) gsize = vblocks;
-  if (dv == 3099) gsize = vblocks;               // one tile per workgroup (A/B)
-  const dim3 grid((unsigned)gsize);
-#define SCL_CONVG_LAUNCH(E, BHV, BIAS, RELU, MASK)                                             \
-  SCL_LAUNCH("convg_kernel", (convg_kernel<E, BHV>), grid, dim3(NTHR), GCfg<BHV>::LDS, st,     \
-             (const unsigned short*)x, (const unsigned short*)packed, B, H, W, cin, kout,      \
-             (unsigned short*)out, BIAS, RELU, (const unsigned short*)MASK,                    \
-             (unsigned char*)pidx, vblocks)
-  if (pidx) {
-    if (low) SCL_CONVG_LAUNCH(3, 8, bias, 0, nullptr); else SCL_CONVG_LAUNCH(3, 12, bias, 0, nullptr);
-  } else if (mask) {
-    if (low) SCL_CONVG_LAUNCH(2, 8, bias, 0, mask); else SCL_CONVG_LAUNCH(2, 12, bias, 0, mask);
-  } else if (bias) {
-    if (low) SCL_CONVG_LAUNCH(1, 8, bias, relu ? 1 : 0, nullptr);
-    else SCL_CONVG_LAUNCH(1, 12, bias, relu ? 1 : 0, nullptr);
-  } else {
-    if (low) SCL_CONVG_LAUNCH(0, 8, bias, dbgbits, nullptr);
-    else SCL_CONVG_LAUNCH(0, 12, bias, dbgbits, nullptr);
-  }
-#undef SCL_CONVG_LAUNCH
+  const LdsConvGrid g = lds_conv_grid((low ? wg8 : wg12) / kb, kb, cus, dv);
+  if (low) convg_epilogue<8>(c, packed, g, dbgbits);
+  else convg_epilogue<12>(c, packed, g, dbgbits);
   return scl_launch_status();
-}
-
-extern "C" int scl_convg(const void* x, const void* w, int64_t w_stride_k, int64_t w_stride_c,
-                         int64_t w_stride_h, int64_t w_stride_w, int transposed, int B, int H,
-                         int W, int cin, int kout, void* out, const float* bias, int relu,
-                         void* workspace, size_t workspace_bytes, void* stream) {
-  return convg_dispatch(x, w, w_stride_k, w_stride_c, w_stride_h, w_stride_w, transposed, B, H, W,
-                        cin, kout, out, bias, relu, nullptr, nullptr, workspace, workspace_bytes,
-                        stream);
-}
-
-extern "C" int scl_convg_pool_idx(const void* x, const void* w, int64_t w_stride_k,
-                                  int64_t w_stride_c, int64_t w_stride_h, int64_t w_stride_w,
-                                  int flags, int B, int H, int W, int cin, int kout,
-                                  const float* bias, void* pooled, void* pool_idx, void* workspace,
-                                  size_t workspace_bytes, void* stream) {
-  if (!pool_idx || !pooled || !bias) return SCL_E_NULL;
-  return convg_dispatch(x, w, w_stride_k, w_stride_c, w_stride_h, w_stride_w, flags & 6, B, H, W,
-                        cin, kout, pooled, bias, 0, nullptr, pool_idx, workspace, workspace_bytes,
-                        stream);
-}
-
-extern "C" int scl_convg_masked(const void* x, const void* w, int64_t w_stride_k,
-                                int64_t w_stride_c, int64_t w_stride_h, int64_t w_stride_w,
-                                int transposed, int B, int H, int W, int cin, int kout, void* out,
-                                const void* mask, void* workspace, size_t workspace_bytes,
-                                void* stream) {
-  if (!mask) return SCL_E_NULL;
-  return convg_dispatch(x, w, w_stride_k, w_stride_c, w_stride_h, w_stride_w, transposed, B, H, W,
-                        cin, kout, out, nullptr, 0, mask, nullptr, workspace, workspace_bytes, stream);
 }

@@ -1,4 +1,8 @@
-// The LDS-weights 3x3 convolution of convg.hip on v_mfma_f32_16x16x32_bf16.
+// The LDS-weights 3x3 convolution on v_mfma_f32_16x16x32_bf16 — every VGG layer from conv3_1 on,
+// forward and backward-data: kernel, pack kernel and launcher.  conv_lds.hip owns the entry points
+// (scl_convg*), validates the arguments and chooses the kernel: this one where the 32-channel chunks
+// come in pairs (cin % 64 == 0), convg.hip's 32x32x16 one otherwise.  What only a diagnostic variant
+// reaches is in convh_diag.hip.
 //
 // Same decomposition (workgroup = [12 or 8 rows x 40 cols] of output pixels x 128 output
 // channels, eight waves, K loop over (32-channel chunk, tap) in groups of three, windows and
@@ -30,8 +34,8 @@
 //   * LDS: 2 x 40 KB windows + 3 x 24 KB weights = 152 KB (12-row blocks).
 #include <mutex>
 
+#include "conv_lds.h"
 #include "conv_pack_layout.h"
-#include "scl_common.h"
 
 namespace {
 
@@ -568,118 +572,86 @@ __global__ __launch_bounds__(HTHR, 1) void convh_kernel(const unsigned short* __
 #undef HSTAMP
 }
 
-int convh_cus() {
-  const int n = scl_device_cus();      // per device (scl_common.h)
-  return scl_usable_cus(n);
-}
-
 }  // namespace
 
-// Same contract as convg_dispatch (convg.hip), which validates the arguments and calls this
-// (dv = the diagnostic variant: 3006 / 3008 / 3012 block height, 3099 one tile per workgroup,
-// 3100 + g grid of g + 1 groups).  The packed weights fit the workspace
-// of scl_convg_workspace_bytes (8 KB per step instead of 10).
-int scl_convh_dispatch(const void* x, const void* w, int64_t w_stride_k, int64_t w_stride_c,
-                       int64_t w_stride_h, int64_t w_stride_w, int flags, int B, int H, int W,
-                       int cin, int kout, void* out, const float* bias, int relu, const void* mask,
-                       void* pidx, void* workspace, int dv, void* stream) {
-  static SclDeviceOnce once;
+// Where a launch runs: the packed weights, the block height and the persistent grid.
+struct HGeom {
+  const unsigned short* packed;
+  int bh;
+  LdsConvGrid grid;
+};
+
+// relu: the kernel's flag word (bit 0 ReLU; above it the timing bits, or the stamped wave)
+template <int E, int BHV, bool STAMP = false, bool FULL = false>
+static void convh_run(const LdsConvCall& c, const HGeom& g, int relu) {
+  if constexpr (!STAMP && !FULL)   // FULL: no tile crosses the image's lower or right border
+    if (c.H % HCfg<BHV>::BH == 0 && c.W % HBW == 0) return convh_run<E, BHV, false, true>(c, g, relu);
+  static SclDeviceOnce once;      // per instantiation: what has its attribute set is what launches
   scl_call_once(once, [] {
-#define SCL_CONVH_ATTR(E, BHV)                                                                 \
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&convh_kernel<E, BHV>),              \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)HCfg<BHV>::LDS);  \
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&convh_kernel<E, BHV, false, true>), \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)HCfg<BHV>::LDS);
-    SCL_CONVH_ATTR(0, 12) SCL_CONVH_ATTR(1, 12) SCL_CONVH_ATTR(2, 12) SCL_CONVH_ATTR(3, 12)
-    SCL_CONVH_ATTR(0, 24) SCL_CONVH_ATTR(1, 24) SCL_CONVH_ATTR(2, 24) SCL_CONVH_ATTR(3, 24)
-    SCL_CONVH_ATTR(0, 8) SCL_CONVH_ATTR(1, 8) SCL_CONVH_ATTR(2, 8) SCL_CONVH_ATTR(3, 8)
-    SCL_CONVH_ATTR(0, 6) SCL_CONVH_ATTR(1, 6) SCL_CONVH_ATTR(2, 6) SCL_CONVH_ATTR(3, 6)
-#undef SCL_CONVH_ATTR
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&convh_kernel<1, 12, true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)HCfg<12>::LDS);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&convh_kernel<1, 24, true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)HCfg<24>::LDS);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&convh_kernel<E, BHV, STAMP, FULL>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)HCfg<BHV>::LDS);
   });
-  hipStream_t st = (hipStream_t)stream;
-  const unsigned short* packed = (const unsigned short*)workspace;
-  if (flags & SCL_W_PACKED) {
-    packed = (const unsigned short*)w;                 // scl_conv_pack_batch wrote it
+  SCL_LAUNCH("convh_kernel", (convh_kernel<E, BHV, STAMP, FULL>), dim3(g.grid.gsize), dim3(HTHR),
+             HCfg<BHV>::LDS, c.stream, (const unsigned short*)c.x, g.packed, c.B, c.H, c.W, c.cin,
+             c.kout, (unsigned short*)c.out, c.bias, relu, (const unsigned short*)c.mask,
+             (unsigned char*)c.pidx, g.grid.vblocks);
+}
+template <int BHV>
+static void convh_epilogue(const LdsConvCall& c, const HGeom& g, int dbgbits) {
+  if (c.pidx) convh_run<3, BHV>(c, g, dbgbits);
+  else if (c.mask) convh_run<2, BHV>(c, g, dbgbits);
+  else if (c.bias) convh_run<1, BHV>(c, g, (c.relu ? 1 : 0) | dbgbits);
+  else convh_run<0, BHV>(c, g, 0);
+}
+
+#ifdef SCL_DIAG
+// the diagnostic variants (convh_diag.hip): true when the variant owns the call, its status in *rc
+static bool convh_diag(const LdsConvCall& c, const HGeom& g, int* rc);
+#endif
+
+// c: validated by conv_lds.hip (c.dv: 3006 / 3008 / 3012 / 3013 block height and wave cut,
+// 3020 + bits / 3040 timing, 3099 / 3100 + g grid).  The packed weights fit the workspace of
+// scl_convg_workspace_bytes (8 KB per step instead of 10).
+int convh_launch(const LdsConvCall& c) {
+  const int dv = SCL_DIAG_ONLY(c.dv);
+  HGeom g;
+  g.packed = (const unsigned short*)c.workspace;
+  if (c.flags & SCL_W_PACKED) {
+    g.packed = (const unsigned short*)c.w;             // scl_conv_pack_batch wrote it
   } else {
-    const int64_t total = (int64_t)9 * (cin / HCCH) * kout * HCCH;
+    const int64_t total = (int64_t)9 * (c.cin / HCCH) * c.kout * HCCH;
     SCL_LAUNCH("convh_pack_kernel", convh_pack_kernel, dim3((unsigned)((total + 255) / 256)),
-               dim3(256), 0, st, w, w_stride_k, w_stride_c, w_stride_h, w_stride_w, flags, cin, kout,
-               (unsigned short*)workspace);
+               dim3(256), 0, c.stream, c.w, c.sk, c.sc, c.sh, c.sw, c.flags, c.cin, c.kout,
+               (unsigned short*)c.workspace);
   }
-  const int bx = (W + HBW - 1) / HBW, kb = kout / HNB;
+  const int bx = (c.W + HBW - 1) / HBW, kb = c.kout / HNB;
   // block height: the one with the fewest (rounds of one workgroup per CU) x (window rows)
-  const int cus = convh_cus();
-  int bh = 12;
-  int64_t best = -1, pblocks = 0;
+  const int cus = scl_conv_cus();
+  g.bh = 12;
+  int64_t best = -1;
   for (int cand : {12, 8, 6}) {
-    const int64_t wg = (int64_t)B * ((H + cand - 1) / cand) * bx * kb;
+    const int64_t wg = (int64_t)c.B * ((c.H + cand - 1) / cand) * bx * kb;
     const int64_t cost = ((wg + cus - 1) / cus) * (cand + 2);
     if (best < 0 || cost < best) {
       best = cost;
-      bh = cand;
+      g.bh = cand;
     }
   }
-  if (dv == 3012 || dv == 3008 || dv == 3006) bh = dv - 3000;
-  if (dv == 3013) bh = 12;
-  const bool cut2x4 = dv != 3012;      // 12 rows: 2 x 4 waves (HCfg<24>); 3012 pins the 4 x 2 cut, 3013 this one
-  pblocks = (int64_t)B * ((H + bh - 1) / bh) * bx;
-  const int vblocks = (int)(((pblocks + 7) / 8) * 8 * kb);
-  int groups = cus / (8 * kb) > 0 ? cus / (8 * kb) : 1;
-  if (dv >= 3100 && dv < 3200) groups = dv - 3100 + 1;
-  int gsize = groups * 8 * kb;
-  if (gsize > vblocks) gsize = vblocks;
-  if (dv == 3099) gsize = vblocks;
-  const dim3 grid((unsigned)gsize);
+  // 12 rows run cut 2 x 4 waves (HCfg<24>); 3013 pins that, 3012 the 4 x 2 cut (convh_diag.hip)
+  if (dv == 3012 || dv == 3008 || dv == 3006) g.bh = dv - 3000;
+  if (dv == 3013) g.bh = 12;
+  g.grid = lds_conv_grid((int64_t)c.B * ((c.H + g.bh - 1) / g.bh) * bx, kb, cus, dv);
+#ifdef SCL_DIAG
+  {
+    int rc;
+    if (convh_diag(c, g, &rc)) return rc;
+  }
+#endif
   // 3020 + bits: 1 no wait / barrier at the top of a tile, 2 no output stores
   // 3040: EXPERIMENT (correct results): s_setprio 1 for waves 4..7 before the tile loop
   const int dbgbits = (dv >= 3020 && dv < 3024) ? (dv - 3020) << 1 : (dv == 3040 ? 4 << 1 : 0);
-#define SCL_CONVH_LAUNCH_F(E, BHV, FULLV, BIAS, RELU, MASK)                                   \
-  SCL_LAUNCH("convh_kernel", (convh_kernel<E, BHV, false, FULLV>), grid, dim3(HTHR),           \
-             HCfg<BHV>::LDS, st, (const unsigned short*)x, (const unsigned short*)packed, B, H, \
-             W, cin, kout, (unsigned short*)out, BIAS, RELU, (const unsigned short*)MASK,      \
-             (unsigned char*)pidx, vblocks)
-#define SCL_CONVH_LAUNCH(E, BHV, BIAS, RELU, MASK)                                             \
-  do {                                                                                         \
-    if (H % HCfg<BHV>::BH == 0 && W % HBW == 0)                                                \
-      SCL_CONVH_LAUNCH_F(E, BHV, true, BIAS, RELU, MASK);                                      \
-    else                                                                                       \
-      SCL_CONVH_LAUNCH_F(E, BHV, false, BIAS, RELU, MASK);                                     \
-  } while (0)
-#define SCL_CONVH_BH(E, BIAS, RELU, MASK)                                                      \
-  do {                                                                                         \
-    if (bh == 12 && cut2x4) SCL_CONVH_LAUNCH(E, 24, BIAS, RELU, MASK);                         \
-    else if (bh == 12) SCL_CONVH_LAUNCH(E, 12, BIAS, RELU, MASK);                              \
-    else if (bh == 8) SCL_CONVH_LAUNCH(E, 8, BIAS, RELU, MASK);                                \
-    else SCL_CONVH_LAUNCH(E, 6, BIAS, RELU, MASK);                                             \
-  } while (0)
-  // stamps of wave dv - 3024 (2 x 4 cut) / dv - 3032 (4 x 2 cut)
-  if (dv >= 3024 && dv < 3040 && bias && !mask && !pidx && bh == 12) {
-    if (dv < 3032)
-      SCL_LAUNCH("convh_kernel", (convh_kernel<1, 24, true>), grid, dim3(HTHR), HCfg<24>::LDS, st,
-                 (const unsigned short*)x, (const unsigned short*)packed, B, H, W, cin, kout,
-                 (unsigned short*)out, bias, (relu ? 1 : 0) | ((dv - 3024) << 4),
-                 (const unsigned short*)nullptr, (unsigned char*)nullptr, vblocks);
-    else
-      SCL_LAUNCH("convh_kernel", (convh_kernel<1, 12, true>), grid, dim3(HTHR), HCfg<12>::LDS, st,
-                 (const unsigned short*)x, (const unsigned short*)packed, B, H, W, cin, kout,
-                 (unsigned short*)out, bias, (relu ? 1 : 0) | ((dv - 3032) << 4),
-                 (const unsigned short*)nullptr, (unsigned char*)nullptr, vblocks);
-    return scl_launch_status();
-  }
-  if (pidx)
-    SCL_CONVH_BH(3, bias, dbgbits, nullptr);
-  else if (mask)
-    SCL_CONVH_BH(2, bias, dbgbits, mask);
-  else if (bias)
-    SCL_CONVH_BH(1, bias, (relu ? 1 : 0) | dbgbits, nullptr);
-  else
-    SCL_CONVH_BH(0, bias, 0, nullptr);
-#undef SCL_CONVH_BH
-#undef SCL_CONVH_LAUNCH
-#undef SCL_CONVH_LAUNCH_F
+  if (g.bh == 12) convh_epilogue<24>(c, g, dbgbits);
+  else if (g.bh == 8) convh_epilogue<8>(c, g, dbgbits);
+  else convh_epilogue<6>(c, g, dbgbits);
   return scl_launch_status();
 }

@@ -259,9 +259,10 @@ extern SclProfSink* volatile scl_prof_sink;
 // without it: scl_variant() is the constant 0 there, every variant branch of the dispatch code
 // and every `dbg` test inside a kernel folds away, and scl_debug_set_variant rejects anything
 // but 0 — the shipped library has no process-wide switch that changes a result.  Kernels and
-// launch structures that only a variant reaches live in netvlad_diag.hip, gram_loss_diag.hip and
-// conv64_diag.hip, which the diagnostic build compiles in place of their product sources; what
-// stays here are hooks that fold to 0 and one-line knobs between kernels the product launches.
+// launch structures that only a variant reaches live in netvlad_diag.hip, gram_loss_diag.hip,
+// conv64_diag.hip and convh_diag.hip, which the diagnostic build compiles in place of their
+// product sources; what stays here are hooks that fold to 0 and one-line knobs between kernels
+// the product launches.
 #ifdef SCL_DIAG
 extern volatile int scl_debug_variant;
 static inline int scl_variant() { return scl_debug_variant; }
@@ -270,14 +271,6 @@ static inline int scl_variant() { return scl_debug_variant; }
 static constexpr int scl_variant() { return 0; }
 #define SCL_DIAG_ONLY(x) 0
 #endif
-
-// 3x3 convolution with LDS-resident weights on v_mfma_f32_16x16x32_bf16 (convh.hip); arguments
-// already validated by convg_dispatch (convg.hip)
-#define SCL_CONVH_DEFAULT true
-int scl_convh_dispatch(const void* x, const void* w, int64_t w_stride_k, int64_t w_stride_c,
-                       int64_t w_stride_h, int64_t w_stride_w, int flags, int B, int H, int W,
-                       int cin, int kout, void* out, const float* bias, int relu, const void* mask,
-                       void* pidx, void* workspace, int dv, void* stream);
 
 // CUs the persistent convolution grids leave free (SCL_RESERVE_CUS, default 0; or
 // scl_set_reserve_cus).  With more than one rank the RCCL kernels need somewhere to run while
@@ -310,6 +303,13 @@ static inline int scl_device_cus() {
     table[dev].store(n, std::memory_order_relaxed);
   }
   return n;
+}
+
+// CUs the persistent convolution grids may fill: the device's, minus the reserve AS IT IS NOW (it may
+// change between calls: bench.py tries 0 and 8 at N > 1), at most the 1024 the wrw workspace is sized for.
+static inline int scl_conv_cus() {
+  const int u = scl_usable_cus(scl_device_cus());
+  return u > 1024 ? 1024 : u;
 }
 
 // One-time function attributes (dynamic LDS limits) are set once PER DEVICE: a function object

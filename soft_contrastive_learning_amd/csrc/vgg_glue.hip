@@ -2,7 +2,7 @@
 //
 // The reference's layers are tf.layers.conv2d / max_pooling2d / tf.nn.relu with TF autodiff
 // (model/nets.py:27-63).  In the bf16 step every convolution is an own kernel (conv64.hip,
-// convh.hip, convg.hip) that fuses most of this glue into its epilogue; the passes below serve
+// conv_lds.hip) that fuses most of this glue into its epilogue; the passes below serve
 // what is left (the un-pooling by window index, the bias-gradient column sums where no
 // weight-gradient kernel produces them) and the float32 / small-map mode, where the
 // convolutions run in the library.  Around library convolutions PyTorch

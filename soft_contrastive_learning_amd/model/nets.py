@@ -3,7 +3,7 @@
 ``vgg16Netvlad(image_batch)`` and ``vgg16(image_batch)`` keep the reference names and
 the NHWC / raw-0..255-RGB input convention (model/nets.py:7-69, :72-131).  In bf16 mode every
 VGG16 convolution pass (forward, backward-data, weight gradient, every layer) runs on the
-hand-written implicit-GEMM kernels of csrc/conv64.hip, csrc/convh.hip and csrc/convg.hip (bias /
+hand-written implicit-GEMM kernels of csrc/conv64.hip and csrc/conv_lds.hip (convh.hip, convg.hip; bias /
 ReLU / max-pool / ReLU' fused into their epilogues, float32 master weights read directly,
 weight gradients written straight into the flat gradient buffer); only the float32 mode and
 maps below 30x40 use the library (MIOpen / CK) with the fused glue passes of
@@ -161,8 +161,8 @@ def _grad_ret(g, p_like):
 
 def _lds_work(flops, nbytes):
     """Work of an LDS-weights convolution, under the names of both kernels that may serve it
-    (csrc/convh.hip by default, csrc/convg.hip when pinned or for odd chunk counts): bench.py
-    prices whichever one it timed."""
+    (csrc/conv_lds.hip chooses: csrc/convh.hip, or csrc/convg.hip when pinned or for odd chunk
+    counts): bench.py prices whichever one it timed."""
     _work('convh_kernel', flops, nbytes)
     _work('convg_kernel', flops, nbytes)
 
@@ -321,7 +321,7 @@ def _lib_weight(w, x):
 
 def _own_conv_kind(x, w, transposed=False):
     """'reg' (weights in registers, csrc/conv64.hip), 'lds' (weights streamed through LDS,
-    csrc/convg.hip) or None (library)."""
+    csrc/conv_lds.hip) or None (library)."""
     if not (USE_CONV64 and x.is_cuda and x.dtype == torch.bfloat16 and w.dtype in _W_DTYPES
             and x.dim() == 4 and w.dim() == 4 and tuple(w.shape[2:]) == (3, 3)):
         return None
@@ -336,7 +336,7 @@ def _own_conv_kind(x, w, transposed=False):
 
 
 def _lds_conv_pays(x, transposed=False, fused_tail=False, kout=512):
-    """Own LDS-weights kernel (csrc/convh.hip) or the library?  Measured on MI355X
+    """Own LDS-weights kernel (csrc/conv_lds.hip -> csrc/convh.hip) or the library?  Measured on MI355X
     (scripts/conv_layers.py; profiles/r02 for the bench shapes, profiles/r05/conv_layers_*.txt for
     the small maps): what decides is how many workgroup tiles ([8 rows x 40 px] x 128 output
     channels) the launch has for the chip's 256 CUs, not the map size —

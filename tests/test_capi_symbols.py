@@ -71,9 +71,17 @@ def test_product_library_has_no_variants_and_the_diagnostic_build_does(lib):
                  b'vlad_split_w_kernel', b'vlad_fwd_kernelILb1E', b'vlad_bwd_kernel', b'vlad_finish_sum_kernel',
                  b'vlad_wgrad_partial_kernel', b'bwd_dots_kernel', b'bwd_du_kernel', b'persist_kernel',
                  b'gram16x6_kernelILi9ELi2ELb1E', b'gram16x6_kernelILi20ELi2ELb1E',
-                 b'conv3x3_kernelILi64ELi64ELi0ELi0ELi0ELi1E'):
+                 b'conv3x3_kernelILi64ELi64ELi0ELi0ELi0ELi1E',
+                 b'convh_kernelILi0ELi12E', b'convh_kernelILi1ELi12E', b'convh_kernelILi2ELi12E',
+                 b'convh_kernelILi3ELi12E', b'convh_kernelILi1ELi24ELb1E'):
         assert name not in product, name
         assert name in diagnostic, name
+    # ... and every LDS-weights kernel the product launchers (csrc/convh.hip, csrc/convg.hip) can choose
+    kept = ['convh_kernelILi%dELi%dELb0ELb%dE' % (e, bh, full) for e in range(4) for bh in (24, 8, 6)
+            for full in (0, 1)] + ['convg_kernelILi%dELi%dE' % (e, bh) for e in range(4) for bh in (12, 8)]
+    for name in kept:
+        assert name.encode() in product, name
+        assert name.encode() in diagnostic, name
 
 
 def test_abi_version_and_error_strings(lib):
@@ -136,3 +144,51 @@ def test_pooled_backward_entry_points_validate_on_the_host(lib):
                                          None) == -1
     assert lib.scl_conv3x3_masked_pooled(p, p, p, 576, 9, 3, 1, 1, 1, 8, 9, 64, 64, p, p, p, cw,
                                          None) == -1
+
+
+def test_lds_convolution_entry_points_validate_on_the_host(lib):
+    """scl_convg / scl_convg_masked / scl_convg_pool_idx (csrc/conv_lds.hip): every refusal of the
+    argument checks, in their order of precedence, comes back before any launch.  (Two of the
+    checks — an index map with a mask, a mask with a bias — guard combinations no entry point forms.)"""
+    from soft_contrastive_learning_amd import _lib
+    NULL, SHAPE, WORKSPACE, KIND = -3, -1, -4, -2
+    buf = ctypes.create_string_buffer(8192)
+    base = (ctypes.addressof(buf) + 255) & ~255
+    p, odd = ctypes.c_void_p(base), ctypes.c_void_p(base + 8)       # 256-byte / only 8-byte aligned
+    ws = lib.scl_convg_workspace_bytes(160, 128)
+    assert ws > 0 and ws % 256 == 0 and lib.scl_convg_workspace_bytes(48, 128) == 0
+    assert lib.scl_convg_workspace_bytes(128, 64) == 0 and lib.scl_convg_workspace_bytes(2048, 128) == 0
+
+    def conv(x=p, w=p, flags=0, b=1, h=8, wd=8, cin=160, kout=128, out=p, work=p, nbytes=ws):
+        return lib.scl_convg(x, w, 1, 1, 1, 1, flags, b, h, wd, cin, kout, out, None, 0, work, nbytes, None)
+
+    def masked(mask=p, cin=160, nbytes=ws):
+        return lib.scl_convg_masked(p, p, 1, 1, 1, 1, 0, 1, 8, 8, cin, 128, p, mask, p, nbytes, None)
+
+    def pool(bias=p, pooled=p, idx=p, cin=160, flags=0, nbytes=ws):
+        return lib.scl_convg_pool_idx(p, p, 1, 1, 1, 1, flags, 1, 8, 8, cin, 128, bias, pooled, idx, p, nbytes, None)
+
+    # NULL operands — before the shape: cin = 48 has no kernel
+    for kw in (dict(x=None), dict(w=None), dict(out=None), dict(work=None)):
+        assert conv(cin=48, **kw) == NULL, kw
+    assert masked(mask=None) == NULL and masked(mask=odd, cin=48) == NULL     # mask NULL / not 16-byte aligned
+    assert pool(bias=None) == NULL and pool(pooled=None) == NULL and pool(idx=None, cin=48) == NULL
+    # shapes — before the workspace
+    assert conv(cin=48) == SHAPE and conv(kout=64) == SHAPE and conv(cin=2048) == SHAPE
+    assert conv(b=0) == SHAPE and conv(h=0) == SHAPE and conv(wd=0) == SHAPE
+    assert conv(b=1 << 11, h=1 << 10, wd=1 << 10) == SHAPE                   # more than 2^30 pixels
+    assert conv(x=odd) == SHAPE and conv(out=odd, nbytes=0) == SHAPE         # not 16-byte aligned
+    assert conv(b=1 << 10, h=1 << 7, wd=1 << 7, cin=128) == SHAPE            # B H W cin = 2^31
+    assert masked(cin=48) == SHAPE and pool(cin=48) == SHAPE
+    # workspace: too small, not 256-byte aligned — before the weight format
+    assert conv(nbytes=ws - 1) == WORKSPACE and conv(work=odd) == WORKSPACE
+    assert masked(nbytes=ws - 1) == WORKSPACE and pool(nbytes=ws - 1) == WORKSPACE
+    assert conv(flags=_lib.W_PACKED, nbytes=0) == WORKSPACE
+    # packed images exist in the 16x16x32 kernel's layout only, and five 32-channel chunks go to the other
+    assert conv(flags=_lib.W_PACKED) == KIND and pool(flags=_lib.W_PACKED) == KIND
+    # ... so a packed image is refused too where the diagnostic build pins the other kernel (40000 + v)
+    ws2 = lib.scl_convg_workspace_bytes(256, 128)
+    big = ctypes.create_string_buffer(ws2 + 256)
+    q = ctypes.c_void_p((ctypes.addressof(big) + 255) & ~255)
+    with _lib.variant(40000) as diag:
+        assert diag.scl_convg(q, q, 1, 1, 1, 1, _lib.W_PACKED, 1, 8, 8, 256, 128, q, None, 0, q, ws2, None) == KIND

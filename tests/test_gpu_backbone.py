@@ -237,8 +237,8 @@ def test_own_conv_fused_tails(dev, cin, cout, shape):
 
 @pytest.fixture(params=['mfma32x32x16', 'mfma16x16x32'])
 def lds_kernel(request):
-    """Pins which of the two LDS-weights convolution kernels runs (csrc/convg.hip: 40000 + v,
-    csrc/convh.hip: 50000 + v); yields the variant base for tests that add their own v."""
+    """Pins which of the two LDS-weights convolution kernels csrc/conv_lds.hip hands a call to
+    (csrc/convg.hip: 40000 + v, csrc/convh.hip: 50000 + v); yields the variant base for tests that add their own v."""
     from soft_contrastive_learning_amd import _lib as L
     base = 40000 if request.param == 'mfma32x32x16' else 50000
     with L.variant(base):                      # (the diagnostic build for the test's duration)
@@ -281,8 +281,8 @@ def test_lds_weight_conv_deeper_layers(dev, cin, cout, shape, block_height):
 
 
 def test_lds_weight_conv_odd_chunk_count(dev, lds_kernel):
-    """cin = 160 is five 32-channel chunks: csrc/convh.hip walks chunks in pairs and leaves such
-    shapes to csrc/convg.hip — the forward must be right whichever kernel is pinned."""
+    """cin = 160 is five 32-channel chunks: csrc/convh.hip walks chunks in pairs, so csrc/conv_lds.hip
+    hands such shapes to csrc/convg.hip — the forward must be right whichever kernel is pinned."""
     from soft_contrastive_learning_amd.model import nets
     g = torch.Generator().manual_seed(71)
     x = torch.randn(1, 160, 12, 40, generator=g).to(dev).bfloat16().contiguous(memory_format=torch.channels_last)

@@ -1,5 +1,5 @@
-"""Bit-exact checks of the own backbone kernels (csrc/conv64.hip, convg.hip, convh.hip,
-conv_pack.hip, vgg_glue.hip) on integer-valued data.
+"""Bit-exact checks of the own backbone kernels (csrc/conv64.hip, conv_lds.hip with convh.hip and
+convg.hip, conv_pack.hip, vgg_glue.hip) on integer-valued data.
 
 With small-integer bf16 operands every product is exact and, while every partial sum is an integer
 below 2^24 (``exact_conv.premise``, asserted first in every test), the float32 accumulation is
@@ -33,7 +33,7 @@ def dev():
 
 @pytest.fixture(params=['mfma32x32x16', 'mfma16x16x32'])
 def lds_kernel(request):
-    """Pins the LDS-weights kernel (csrc/convg.hip: 40000 + v, csrc/convh.hip: 50000 + v)."""
+    """Pins the kernel csrc/conv_lds.hip hands a call to (csrc/convg.hip: 40000 + v, csrc/convh.hip: 50000 + v)."""
     from soft_contrastive_learning_amd import _lib as L
     base = 40000 if request.param == 'mfma32x32x16' else 50000
     with L.variant(base):
@@ -209,13 +209,64 @@ def test_lds_forward_and_backward_data(dev, regime, cin, kout, shape, block_heig
 
 @pytest.mark.parametrize('regime', REGIMES)
 def test_lds_forward_odd_chunk_count(dev, lds_kernel, regime):
-    """cin = 160: five 32-channel chunks (convh.hip walks pairs and hands these to convg.hip)."""
+    """cin = 160: five 32-channel chunks (convh.hip walks pairs; conv_lds.hip hands these to convg.hip)."""
     from soft_contrastive_learning_amd.model import nets
     x, wt, g = _operands(regime, 1, 160, 128, 13, 41, 41, dev)
     assert nets._own_conv_kind(x, wt) == 'lds'
     bias = X.int_bias(128, g, dev)
     z = _fwd_ref(regime, x, wt, bias)
     _same(nets.conv64(x, wt, False, bias=bias, relu=True), X.to_bf16(torch.relu(z)), 'conv + bias + relu')
+
+
+# The PRODUCT library's own choice (no variant: csrc/conv_lds.hip picks the kernel, the launcher the
+# block height).  With 16 usable CUs and kout = 256 the 16x16x32 launcher's cost rule,
+# ceil(B ceil(H / bh) ceil(W / 40) (kout / 128) / cus) (bh + 2) with ties to 12, then 8, then 6,
+# gives every block height on small maps — (cin, kout, shape, height it picks, tiles the map exactly).
+# The heights are by that rule (restated in _product_block_height, which checks this table), not
+# observed: the library does not report its choice, so a wrong choice that computed right would pass.
+# cin = 160 is five 32-channel chunks, which conv_lds.hip hands to the 32x32x16 kernel.
+PRODUCT = [(256, 256, (4, 24, 40), 12, True), (256, 256, (4, 22, 38), 12, False),
+           (256, 256, (4, 23, 41), 12, False), (256, 256, (4, 16, 40), 8, True),
+           (256, 256, (4, 15, 40), 8, False), (256, 256, (1, 12, 40), 6, True),
+           (256, 256, (1, 13, 41), 6, False), (160, 128, (1, 13, 41), None, False)]
+
+
+def _product_block_height(b, h, w, kout, cus):
+    cost = {bh: -(-(b * -(-h // bh) * -(-w // 40) * (kout // 128)) // cus) * (bh + 2) for bh in (12, 8, 6)}
+    return min((12, 8, 6), key=lambda bh: cost[bh])           # (min keeps the first of equals)
+
+
+@pytest.mark.parametrize('regime', REGIMES)
+@pytest.mark.parametrize('cin,kout,shape,bh,exact', PRODUCT, ids=['%dx%d-%dx%dx%d' % ((r[0], r[1]) + r[2]) for r in PRODUCT])
+def test_lds_product_dispatch(dev, reserve, regime, cin, kout, shape, bh, exact):
+    from soft_contrastive_learning_amd import _lib as L
+    from soft_contrastive_learning_amd.model import nets
+    assert L.load().scl_build_is_diag() == 0
+    b, h, w = shape
+    if bh is not None:
+        assert _product_block_height(b, h, w, kout, 16) == bh and (h % bh == 0 and w % 40 == 0) == exact
+    reserve(torch.cuda.get_device_properties(dev).multi_processor_count - 16)
+    x, wt, g = _operands(regime, b, cin, kout, h, w, 250 + cin + h * w, dev)
+    wt = _cl(wt)
+    assert nets._own_conv_kind(x, wt) == 'lds'
+    bias = X.int_bias(kout, g, dev)
+    z = _fwd_ref(regime, x, wt, bias)
+    z0 = X.conv3x3(x, wt)
+    _same(nets.conv64(x, wt, False), X.to_bf16(z0), 'conv')
+    _same(nets.conv64(x, wt, False, bias=bias, relu=True), X.to_bf16(torch.relu(z)), 'conv + bias + relu')
+    if cin % 64:
+        return                          # (its backward-data pass has 160 output channels: no LDS shape)
+    if h % 2 == 0 and w % 2 == 0:
+        want_a, want_i = _pool_ref(z0, bias)
+        a, idx = nets.conv_pool_idx(x, wt, bias)
+        _same(a, want_a, 'pooled (index epilogue)')
+        _same(idx, want_i, 'pool window index')
+    gy, _, _ = _operands(regime, b, kout, cin, h, w, 350 + h * w, dev)
+    X.premise(X.conv3x3_t, gy, wt, limit=X.BF16_EXACT + 1 if regime == 'r1' else X.EXACT)
+    gx = X.to_bf16(X.conv3x3_t(gy, wt))
+    _same(nets.conv64(gy, wt, True), gx, 'backward-data')
+    mask = _mask_like((b, cin, h, w), g, dev)
+    _same(nets.conv64(gy, wt, True, mask=mask), torch.where(X.relu_mask(mask), gx, 0.0), 'masked backward-data')
 
 
 # ---- backward-data, register kernels (scl_conv3x3 transposed, _masked, _masked_pooled) ----------
