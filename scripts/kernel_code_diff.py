@@ -1,0 +1,58 @@
+#!/usr/bin/env python3
+"""Is the gfx950 device code of two builds of one object (.o / .so) the same?  Compares, kernel by
+kernel, the compiler's resource rows (scripts/kernel_resources.py: registers, scratch, LDS, code
+size) and the disassembly of every device symbol, the `__hip_cuid_*` hash apart.
+
+    python scripts/kernel_code_diff.py parent/gram_loss.o soft_contrastive_learning_amd/csrc/gram_loss.o
+
+Exit status 0: identical.  1: the differing kernels are listed with their resource rows.
+"""
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import kernel_resources as K  # noqa: E402
+
+
+def device_code(path):
+    """(resource rows by kernel, disassembly by symbol, symbol order) of the object's code object"""
+    with tempfile.TemporaryDirectory() as tmp:
+        cos = K.code_objects(path, tmp)
+        assert len(cos) == 1, (path, cos)
+        rows = {r[0]: r[1:] for r in K.kernels(cos[0])}
+        txt = subprocess.run([os.path.join(K.LLVM, 'llvm-objdump'), '-d', '--no-show-raw-insn',
+                              '--no-leading-addr', cos[0]], capture_output=True, text=True, check=True).stdout
+    txt = re.sub(r'__hip_cuid_[0-9a-f]+', '__hip_cuid', txt)
+    txt = re.sub(r'[ \t]*// [0-9A-F]{12}:.*', '', txt)           # the address column of branch targets' lines
+    syms, order, cur = {}, [], None
+    for line in txt.splitlines():
+        m = re.match(r'<(\S+)>:$', line)
+        if m:
+            cur = m.group(1)
+            order.append(cur)
+            syms[cur] = []
+        elif cur:
+            syms[cur].append(line)
+    return rows, syms, order
+
+
+def main():
+    a, b = device_code(sys.argv[1]), device_code(sys.argv[2])
+    bad = sorted(set(a[1]) ^ set(b[1]))
+    bad += [s for s in a[2] if s in b[1] and (a[1][s] != b[1][s] or a[0].get(s) != b[0].get(s))]
+    print('%d device symbols / %d kernels in %s, %d / %d in %s; symbol order %s'
+          % (len(a[2]), len(a[0]), sys.argv[1], len(b[2]), len(b[0]), sys.argv[2],
+             'equal' if a[2] == b[2] else 'DIFFERS'))
+    for s in bad:
+        print('DIFFERS  %s\n   resources (vgpr, agpr, sgpr, scratch, lds, code bytes): %s -> %s'
+              % (K.demangle([s])[0], a[0].get(s), b[0].get(s)))
+    if not bad and a[2] == b[2]:
+        print('identical: resource rows and disassembly of every symbol')
+    return 1 if bad or a[2] != b[2] else 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())

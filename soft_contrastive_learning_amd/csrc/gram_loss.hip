@@ -1,23 +1,24 @@
 // Gram-matrix loss family on gfx950: wms_loss / ms_loss forward + backward and
-// _pairwise_squared_distances.
-//
-// Reference semantics: model/losses.py:5-60 (wms_loss), :76-122 (ms_loss),
-// :656-661 (_pairwise_squared_distances).  The reference runs ~40 TF ops on B×B
-// temporaries plus one [B,E]x[E,B] matmul; here the path is
-//   1. gram_partial_kernel   split-K raw Gram  G = E E^T  on the f32 MFMA
-//                            (v_mfma_f32_32x32x2_f32: exact f32, SURVEY H2 forbids
-//                            a low-precision Gram), upper-triangular 32x32 tiles,
-//                            one [32x32] slab per (K-split, tile pair);
-//   2. gram_rows_kernel      one workgroup per row: slab reduction, row norms from
-//                            the Gram diagonal, masks, MS mining, row loss and
-//                            d loss / d S row;
-//   3. gram_coef_kernel      loss mean + the matrix M with d loss / d E = M E
-//                            (folds (G+G^T) and the l2_normalize Jacobian);
-//   4. gram_bwd_kernel       grad_E[rows] = g * M[rows,:] E   on the f32 MFMA.
-// All reductions are fixed-order (no float atomics): results are bitwise
-// reproducible run to run.
-#include <mutex>
-
+// _pairwise_squared_distances (reference: model/losses.py:5-60, :76-122, :656-661 — ~40 TF ops on B×B
+// temporaries plus one [B,E]x[E,B] matmul).  A forward leaves the loss and the matrix M with
+// d loss / d E = M E; the backward is grad_E[rows] = g * M[rows,:] E.  The Gram is float32 or
+// float32-equivalent everywhere (SURVEY H2 forbids a low-precision Gram); all reductions are
+// fixed-order (no float atomics): results are bitwise reproducible run to run.
+// Forward routes (gram_fwd_plan; "aligned" = 16-byte aligned rows: ld % 4 == 0 and the base pointer):
+//   B <= 32, sync block, every wave's pair count equal (1, 3 or 5)   gram16_fused_kernel (one launch)
+//   B <= 32 otherwise                                gram16_kernel, gram_final32_kernel
+//   64 < B <= 208, E % 128 == 0, aligned             gram16x6p_kernel, FINISH
+//   208 < B <= 256, E % 128 == 0, aligned            gram16x6_kernel, FINISH
+//   32 < B <= 256 otherwise                          gram16_kernel, FINISH
+//   256 < B <= 1024                                  gram_partial_kernel, gram_rows_kernel, gram_coef_kernel
+//   FINISH = gram_reduce_kernel, gram_rows_wave_kernel<ceil(B / 64)>, gram_coef_kernel
+// Backward routes (gram_bwd_route; "aligned" = emb and grad as above):
+//   B <= 32                                                              gram_bwd32_kernel
+//   64 < B <= 256, B % 4 == 0, >= 96 rows, E % 128 == 0, aligned + coef  gram_bwd_planes_kernel<rows / 16>
+//   64 <= B <= 512, <= 32 rows, E % 128 == 0, aligned                    gram_bwd_rows_kernel
+//   E % 512 == 0, aligned                                                gram_bwd_fast_kernel<1 | 2 | 4>
+//   otherwise                                                            gram_bwd_kernel
+// _pairwise_squared_distances: gram_partial_kernel (a batch of Grams), sqdist_finish_kernel.
 #include "scl_common.h"
 
 namespace {
@@ -604,7 +605,8 @@ struct Gram16Plan {
   int KS;       // k-ranges among the 4 waves (4, 2 or 1); pair ranges = 4 / KS
 };
 
-inline Gram16Plan make_plan16(int B, int E) {
+// split_pin > 0 (GramPins::splits, diagnostic build): that many splits instead of the rule's
+inline Gram16Plan make_plan16(int B, int E, int split_pin) {
   Gram16Plan p;
   p.T = (B + 15) / 16;
   p.P = p.T * (p.T + 1) / 2;
@@ -617,9 +619,7 @@ inline Gram16Plan make_plan16(int B, int E) {
   // small batches: fewer, larger splits (the finishing workgroup reads every slab); large ones:
   // one workgroup per CU.  (Round 5 measured 64 splits up to B = 64 for a one-launch forward there:
   // the Gram on 64 CUs takes 11.7 / 18.3 us at B = 48 / 64 against 7.8 / 9.7 on 256 — not kept.)
-  int s = B <= 32 ? 64 : 256;
-  int ov = scl_variant() / 100000;          // tuning override: splits = ov
-  if (ov > 0) s = ov;
+  const int s = split_pin > 0 ? split_pin : (B <= 32 ? 64 : 256);
   int kc = 64;                                   // power of two: staging indices by shifts
   while (kc < (E + s - 1) / s && 2 * kc <= kc_max) kc *= 2;
   p.kchunk = kc;
@@ -1570,7 +1570,8 @@ __global__ __launch_bounds__(256) void gram_bwd32_kernel(const float* __restrict
 }
 
 // =======================================================================================
-// Round 6: the forward for 32 < B <= 208 as ONE launch (was four: Gram | slab sums | rows | M).
+// Round 6: the strip-scheduled Gram kernel (the product's, 64 < B <= 208) and the forward for
+// 32 < B <= 208 as ONE launch (diagnostic build only: gram_loss_diag.hip holds persist_tail).
 //
 //   gram16x6p_body   the bf16x6 Gram of gram16x6_kernel with BOTH 64-column passes of the
 //                    workgroup's slice resident in LDS (2 x 3 planes x 8 pieces x (Bp + 1) x 16 B =
@@ -1844,79 +1845,132 @@ inline GramWs carve(void* ws, int B, size_t slab_floats) {
   return w;
 }
 
-inline size_t slab_floats_for(int B, int E) {
-  if (B <= kFastB) {
-    const Gram16Plan p = make_plan16(B, E);
-    size_t n = (size_t)p.S * p.P * 256;
-    if (B > 64 && E % 128 == 0 && (size_t)(E / 128) * p.P * 256 > n) n = (size_t)(E / 128) * p.P * 256;
-    return n;
+// The diagnostic variants (scl_debug_set_variant) that steer the forward plan and the backward route,
+// read once per call: the plan and the route are pure functions of their arguments.  The product build
+// has no variants (scl_variant() is the constant 0 there): every test of a pin folds away.
+struct GramPins {
+  int v = 0;
+  constexpr bool f32_gram() const { return v == 31; }       // forward: no bf16x6 Gram kernel
+  constexpr bool plain() const { return v == 32; }          // two-launch forward, gram_bwd_kernel above B = 32
+  constexpr bool no_bwd_rows() const { return v == 33; }    // backward: one row tile on the general kernels
+  constexpr bool no_bwd_planes() const { return v == 34; }  // backward: many rows on the float32 MFMA
+  // forward in one launch for 32 < B <= 64 as well (final64_body): bit-identical to the four launches
+  // and slower, profiles/r05/loss_one_launch_above_32.txt
+  constexpr bool fused_to_64() const { return v == 36; }
+  constexpr int splits() const { return v / 100000; }       // forward, > 0: K-splits of gram16_kernel (tuning)
+};
+inline GramPins gram_pins() { return GramPins{scl_variant()}; }
+
+// gram16_kernel: the staged [16 T][kchunk + 4] slice, reused for the cross-wave sums
+inline size_t gram16_lds(const Gram16Plan& p) {
+  const size_t stage = (size_t)16 * p.T * (p.kchunk + 4) * sizeof(float);
+  const size_t red = p.KS > 1 ? (size_t)p.KS * p.P * 64 * sizeof(f32x4) : 0;
+  return red > stage ? red : stage;
+}
+// gram16x6_kernel: the three bf16 planes of a 64-column pass; gram16x6p_kernel keeps both passes of its
+// 128-column slice, twice this: <= 160 KB up to kX6pMaxRows padded rows
+inline size_t x6_lds_bytes(int T) { return (size_t)3 * 8 * (16 * T + 1) * 16; }
+constexpr int kX6pMaxRows = 208;
+
+enum class GramFwd { X6p, X6, Fused, Gram16Final32, Gram16, Tile32 };
+
+// What the forward decides on the host: kernel sequence, template class, grid, LDS and the slabs written.
+struct GramFwdPlan {
+  GramFwd route;
+  Gram16Plan p;         // B <= kFastB; S = the slabs the route's Gram kernel writes (its grid)
+  GramPlan p32;         // Tile32
+  int pw;               // B <= kFastB: tile pairs per wave (the most)
+  int pwmax;            // gram16 / fused kernels: PWMAX
+  bool full;            //   and FULL: every wave owns exactly PWMAX pairs
+  bool dual;            // gram16x6p_kernel: <true, 11> (at most 80 tile pairs) or <false, 13>
+  int rows_c;           // gram_rows_wave_kernel<C>: 64-column groups per row
+  size_t lds;           // dynamic LDS of the route's Gram kernel (Tile32: of gram_rows_kernel)
+  size_t slab_floats;
+};
+
+// aligned: 16-byte rows (ld % 4 == 0 and the base pointer); has_sync: the caller passed a sync block
+inline GramFwdPlan gram_fwd_plan(int B, int E, bool aligned, bool has_sync, const GramPins& pins) {
+  GramFwdPlan f{};
+  if (B > kFastB) {
+    f.route = GramFwd::Tile32;
+    f.p32 = make_plan(B, E);
+    f.lds = ((size_t)rows_part_floats(B) + 5 * (size_t)((B + 63) / 64 * 64)) * sizeof(float);
+    f.slab_floats = (size_t)f.p32.splits * f.p32.npairs * kTile * kTile;
+    return f;
   }
-  const GramPlan p = make_plan(B, E);
-  return (size_t)p.splits * p.npairs * kTile * kTile;
+  Gram16Plan& p = f.p;
+  p = make_plan16(B, E, pins.splits());
+  const int ps = 4 / p.KS;                     // pair ranges among the four waves
+  const bool even = p.P % ps == 0;
+  f.pw = (p.P + ps - 1) / ps;
+  f.rows_c = (B + 63) / 64;
+  f.lds = gram16_lds(p);
+  if (B > 64 && E % 128 == 0 && aligned && !pins.f32_gram()) {
+    // the bf16x6 Gram: a workgroup and a slab per 128-column slice; the strip-scheduled kernel where both
+    // passes of the slice fit in LDS.  (Its one-launch persistent form is bit-identical and slower —
+    // three grid barriers at 6-10 us each, profiles/r06/loss_one_launch_persistent.txt — and lives in
+    // gram_loss_diag.hip.)
+    p.S = E / 128;
+    f.route = 16 * p.T <= kX6pMaxRows ? GramFwd::X6p : GramFwd::X6;
+    f.dual = (p.P + 3) / 4 <= 20;
+    f.lds = f.route == GramFwd::X6p ? 2 * x6_lds_bytes(p.T) : x6_lds_bytes(p.T);
+  } else if ((B <= 32 || (B <= 64 && pins.fused_to_64())) && has_sync && even &&
+             (f.pw == 1 || f.pw == 3 || f.pw == 5) && !pins.plain()) {
+    // one launch: the Gram and, in its last workgroup to arrive, the finish
+    f.route = GramFwd::Fused;
+    f.pwmax = f.pw;
+    f.full = true;
+    if (f.lds < 24 * 1024) f.lds = 24 * 1024;                              // final32_body's tables
+    if (B > 32 && f.lds < (size_t)kFinal64Lds) f.lds = kFinal64Lds;        // final64_body's
+  } else {
+    f.route = B <= 32 ? GramFwd::Gram16Final32 : GramFwd::Gram16;
+    f.full = even && (f.pw == 1 || f.pw == 3);
+    f.pwmax = f.full ? f.pw : f.pw <= 3 ? 3 : f.pw <= 5 ? 5 : f.pw <= 9 ? 9 : f.pw <= 20 ? 20 : 34;
+  }
+  f.slab_floats = (size_t)p.S * p.P * 256;
+  return f;
 }
 
-// bf16x6 route: aligned rows and E a multiple of the 128-column slice
-inline bool use_x6(int B, int E, int64_t ld, const float* emb) {
-  return B > 64 && B <= kFastB && E % 128 == 0 && ld % 4 == 0 && ((uintptr_t)emb % 16) == 0 &&
-         scl_variant() != 31;                             // 31: force the float32-MFMA Gram
+// The slab floats a workspace for (B, E) holds: the most that any plan for the shape writes, whatever
+// the row stride, the alignment and the sync block turn out to be at the call.
+inline size_t gram_slab_floats(int B, int E, const GramPins& pins) {
+  size_t n = 0;
+  for (int k = 0; k < 4; ++k) n = std::max(n, gram_fwd_plan(B, E, k & 1, k & 2, pins).slab_floats);
+  return n;
 }
+
+struct GramFwdCall {      // what every Gram launcher takes besides the plan
+  const float* emb;
+  int64_t ld;
+  int B, E, vec_ok;
+  float* slabs;
+  hipStream_t st;
+};
 template <int PWMAX, bool DUAL>
-void launch_gram16x6(int T, int P, const float* emb, int64_t ld, int B, int E, float* slabs,
-                     hipStream_t st) {
-  static SclDeviceOnce once;
-  scl_call_once(once, [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gram16x6_kernel<PWMAX, 2, DUAL>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024);
-  });
-  const size_t lds = (size_t)3 * 8 * (16 * T + 1) * 16;
-  SCL_LAUNCH("gram16x6_kernel", (gram16x6_kernel<PWMAX, 2, DUAL>), dim3(E / 128), dim3(256), lds, st, emb,
-             ld, B, E, T, P, slabs);
+void launch_gram16x6(const Gram16Plan& p, size_t lds, const GramFwdCall& c) {
+  scl_lds_limit<&gram16x6_kernel<PWMAX, 2, DUAL>>(100 * 1024);
+  SCL_LAUNCH("gram16x6_kernel", (gram16x6_kernel<PWMAX, 2, DUAL>), dim3(c.E / 128), dim3(256), lds, c.st,
+             c.emb, c.ld, c.B, c.E, p.T, p.P, c.slabs);
 }
-
 template <int PWMAX, bool FULL = false>
-void launch_gram16(const Gram16Plan& p, const float* emb, int64_t ld, int B, int E, int vec_ok,
-                   float* slabs, hipStream_t st) {
-  static SclDeviceOnce once;
-  scl_call_once(once, [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gram16_kernel<PWMAX, FULL>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 132 * 1024);
-  });
-  size_t lds = (size_t)16 * p.T * (p.kchunk + 4) * sizeof(float);
-  const size_t red = p.KS > 1 ? (size_t)p.KS * p.P * 64 * sizeof(f32x4) : 0;
-  if (red > lds) lds = red;
-  SCL_LAUNCH("gram16_kernel", (gram16_kernel<PWMAX, FULL>), dim3(p.S), dim3(256), lds, st, emb, ld, B, E,
-             p.T, p.P, p.kchunk, p.KS, vec_ok, slabs);
+void launch_gram16(const GramFwdPlan& f, const GramFwdCall& c) {
+  scl_lds_limit<&gram16_kernel<PWMAX, FULL>>(132 * 1024);
+  SCL_LAUNCH("gram16_kernel", (gram16_kernel<PWMAX, FULL>), dim3(f.p.S), dim3(256), f.lds, c.st, c.emb, c.ld,
+             c.B, c.E, f.p.T, f.p.P, f.p.kchunk, f.p.KS, c.vec_ok, c.slabs);
 }
-// B <= 32 with the finish inside: the last workgroup to arrive runs it
+// with the finish inside: the last workgroup to arrive runs it
 template <int PWMAX, bool FULL>
-void launch_gram16_fused(const Gram16Plan& p, const float* emb, int64_t ld, int B, int E, int vec_ok,
-                         float* slabs, const FinalArgs& fa, hipStream_t st) {
-  static SclDeviceOnce once;
-  scl_call_once(once, [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gram16_fused_kernel<PWMAX, FULL>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 132 * 1024);
-  });
-  size_t lds = (size_t)16 * p.T * (p.kchunk + 4) * sizeof(float);
-  const size_t red = p.KS > 1 ? (size_t)p.KS * p.P * 64 * sizeof(f32x4) : 0;
-  if (red > lds) lds = red;
-  if (lds < 24 * 1024) lds = 24 * 1024;                       // final32_body's tables
-  if (B > 32 && lds < (size_t)kFinal64Lds) lds = kFinal64Lds; // final64_body's
-  SCL_LAUNCH("gram16_fused_kernel", (gram16_fused_kernel<PWMAX, FULL>), dim3(p.S), dim3(1024), lds, st,
-             emb, ld, B, E, p.T, p.P, p.kchunk, p.KS, vec_ok, slabs, fa);
+void launch_gram16_fused(const GramFwdPlan& f, const GramFwdCall& c, const FinalArgs& fa) {
+  scl_lds_limit<&gram16_fused_kernel<PWMAX, FULL>>(132 * 1024);
+  SCL_LAUNCH("gram16_fused_kernel", (gram16_fused_kernel<PWMAX, FULL>), dim3(f.p.S), dim3(1024), f.lds, c.st,
+             c.emb, c.ld, c.B, c.E, f.p.T, f.p.P, f.p.kchunk, f.p.KS, c.vec_ok, c.slabs, fa);
 }
-
 template <bool DUAL, int SMAX>
-void launch_x6p(const float* emb, int64_t ld, int B, int E, int T, int P, float* slabs, hipStream_t st) {
-  static SclDeviceOnce once;
-  scl_call_once(once, [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gram16x6p_kernel<DUAL, SMAX>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  });
-  const size_t lds = (size_t)2 * 3 * 8 * (16 * T + 1) * 16;
-  SCL_LAUNCH("gram16x6p_kernel", (gram16x6p_kernel<DUAL, SMAX>), dim3(E / 128), dim3(256), lds, st, emb, ld, B, T,
-             P, slabs);
+void launch_x6p(const GramFwdPlan& f, const GramFwdCall& c) {
+  scl_lds_limit<&gram16x6p_kernel<DUAL, SMAX>>(160 * 1024);
+  SCL_LAUNCH("gram16x6p_kernel", (gram16x6p_kernel<DUAL, SMAX>), dim3(c.E / 128), dim3(256), f.lds, c.st,
+             c.emb, c.ld, c.B, f.p.T, f.p.P, c.slabs);
 }
-constexpr int kX6pMaxRows = 208;     // both passes of the slice in LDS: 2 * 3 * 8 * (Bp + 1) * 16 B <= 160 KB
 
 }  // namespace
 
@@ -1929,7 +1983,7 @@ static bool gram_loss_fwd_diag(const float* emb, int64_t ld_emb, int B, int E, c
 
 extern "C" size_t scl_gram_loss_workspace_bytes(int B, int E) {
   if (B < 1 || E < 1 || B > kMaxB) return 0;
-  return carve(nullptr, B, slab_floats_for(B, E)).total;
+  return carve(nullptr, B, gram_slab_floats(B, E, gram_pins())).total;
 }
 
 extern "C" int scl_gram_loss_fwd(const float* emb, int64_t ld_emb, int B, int E, int mask_kind,
@@ -1956,21 +2010,13 @@ extern "C" int scl_gram_loss_fwd_s(const float* emb, int64_t ld_emb, int B, int 
   if (sum_kind != SCL_SUM_MS && sum_kind != SCL_SUM_PLAIN) return SCL_E_KIND;
   if (mask_kind == SCL_MASK_LABELS ? !labels : !distances) return SCL_E_NULL;
   if (!scl_aligned256(workspace)) return SCL_E_WORKSPACE;
-  GramWs w = carve(workspace, B, slab_floats_for(B, E));
+  const GramPins pins = gram_pins();
+  const GramWs w = carve(workspace, B, gram_slab_floats(B, E, pins));
   if (workspace_bytes < w.total) return SCL_E_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   const int vec_ok = (ld_emb % 4 == 0) && ((uintptr_t)emb % 16 == 0);
-  LossParams lp;
-  lp.mask_kind = mask_kind;
-  lp.dist_rank3 = dist_rank3 ? 1 : 0;
-  lp.ms_mining = ms_mining ? 1 : 0;
-  lp.sum_kind = sum_kind;
-  lp.d_alpha = d_alpha;
-  lp.d_beta = d_beta;
-  lp.alpha = alpha;
-  lp.beta = beta;
-  lp.lamb = lamb;
-  lp.eps = eps;
+  const LossParams lp = {mask_kind, dist_rank3 ? 1 : 0, ms_mining ? 1 : 0, sum_kind, d_alpha,
+                         d_beta,    alpha,              beta,              lamb,     eps};
 #ifdef SCL_DIAG
   {
     int rc;
@@ -1979,93 +2025,55 @@ extern "C" int scl_gram_loss_fwd_s(const float* emb, int64_t ld_emb, int B, int 
       return rc;
   }
 #endif
-  if (B <= kFastB) {
-    Gram16Plan p = make_plan16(B, E);
-    const int ps = 4 / p.KS;
-    const int pw = (p.P + ps - 1) / ps;
-    const bool full = p.P % ps == 0;
-    // ---- round 6.  Product path for 64 < B <= 208: the strip-scheduled Gram kernel (gram16x6p_kernel)
-    // in front of the three finishing launches.  The ONE-launch persistent form (persist_tail) was
-    // built, is bit-identical and deadlock-free, and is SLOWER (B = 192: 52 us against 35; stamps in
-    // profiles/r06/loss_one_launch_persistent.txt: three grid barriers at 6-10 us each with their
-    // imbalance, and phases whose latency chains cost what the small kernels cost): it lives in the
-    // diagnostic build only (gram_loss_diag.hip) — scl_debug_set_variant(41), + 39 no patience (repair
-    // path), 40 stamps.  37 = round 5's four launches (the old Gram kernel).
-    const bool x6 = use_x6(B, E, ld_emb, emb);
-    const bool x6p = x6 && 16 * p.T <= kX6pMaxRows;
-    if (x6p) {
-      p.S = E / 128;
-      if ((p.P + 3) / 4 <= 20)
-        launch_x6p<true, 11>(emb, ld_emb, B, E, p.T, p.P, w.slabs, st);
-      else
-        launch_x6p<false, 13>(emb, ld_emb, B, E, p.T, p.P, w.slabs, st);
-    } else if (use_x6(B, E, ld_emb, emb)) {
-      p.S = E / 128;                                          // slabs of the bf16x6 kernel
-      launch_gram16x6<34, false>(p.T, p.P, emb, ld_emb, B, E, w.slabs, st);
-    } else if ((B <= 32 || (B <= 64 && scl_variant() == 36)) && sync_words && full &&
-               (pw == 1 || pw == 3 || pw == 5) && scl_variant() != 32) {
-      // (32: the two-launch forward, for A/B.  36: the one-launch forward for 32 < B <= 64 as well —
-      // final64_body; bit-identical to the four launches and SLOWER, so not the product path: in
-      // device time 24.8 us against 17.0 at B = 48 — one workgroup reads every slab and walks 48 rows
-      // where three small kernels use the chip; profiles/r05/loss_one_launch_above_32.txt)
-      // (32: the two-launch forward, for A/B)  one launch: the Gram and, in its last workgroup, the finish
-      FinalArgs fa;
-      fa.counter = (unsigned*)sync_words;
-      fa.distances = distances;
-      fa.labels = labels;
-      fa.lp = lp;
-      fa.coef = coef;
-      fa.loss_out = loss_out;
-      if (pw == 1)
-        launch_gram16_fused<1, true>(p, emb, ld_emb, B, E, vec_ok, w.slabs, fa, st);
-      else if (pw == 3)
-        launch_gram16_fused<3, true>(p, emb, ld_emb, B, E, vec_ok, w.slabs, fa, st);
-      else
-        launch_gram16_fused<5, true>(p, emb, ld_emb, B, E, vec_ok, w.slabs, fa, st);
+  const GramFwdPlan f = gram_fwd_plan(B, E, vec_ok, sync_words != nullptr, pins);
+  const Gram16Plan& p = f.p;
+  const GramFwdCall c = {emb, ld_emb, B, E, vec_ok, w.slabs, st};
+  switch (f.route) {
+    case GramFwd::X6p:
+      if (f.dual) launch_x6p<true, 11>(f, c);
+      else launch_x6p<false, 13>(f, c);
+      break;
+    case GramFwd::X6: launch_gram16x6<34, false>(p, f.lds, c); break;
+    case GramFwd::Fused: {
+      const FinalArgs fa = {(unsigned*)sync_words, distances, labels, lp, coef, loss_out};
+      if (f.pwmax == 1) launch_gram16_fused<1, true>(f, c, fa);
+      else if (f.pwmax == 3) launch_gram16_fused<3, true>(f, c, fa);
+      else launch_gram16_fused<5, true>(f, c, fa);
       return scl_launch_status();
-    } else if (pw == 1 && full)
-      launch_gram16<1, true>(p, emb, ld_emb, B, E, vec_ok, w.slabs, st);
-    else if (pw == 3 && full)
-      launch_gram16<3, true>(p, emb, ld_emb, B, E, vec_ok, w.slabs, st);
-    else if (pw <= 3)
-      launch_gram16<3>(p, emb, ld_emb, B, E, vec_ok, w.slabs, st);
-    else if (pw <= 5)
-      launch_gram16<5>(p, emb, ld_emb, B, E, vec_ok, w.slabs, st);
-    else if (pw <= 9)
-      launch_gram16<9>(p, emb, ld_emb, B, E, vec_ok, w.slabs, st);
-    else if (pw <= 20)
-      launch_gram16<20>(p, emb, ld_emb, B, E, vec_ok, w.slabs, st);
-    else
-      launch_gram16<34>(p, emb, ld_emb, B, E, vec_ok, w.slabs, st);
-    if (B <= 32) {
+    }
+    case GramFwd::Gram16Final32:
+    case GramFwd::Gram16:
+      if (f.full && f.pwmax == 1) launch_gram16<1, true>(f, c);
+      else if (f.full) launch_gram16<3, true>(f, c);
+      else if (f.pwmax == 3) launch_gram16<3>(f, c);
+      else if (f.pwmax == 5) launch_gram16<5>(f, c);
+      else if (f.pwmax == 9) launch_gram16<9>(f, c);
+      else if (f.pwmax == 20) launch_gram16<20>(f, c);
+      else launch_gram16<34>(f, c);
+      if (f.route == GramFwd::Gram16) break;
       SCL_LAUNCH("gram_final32_kernel", gram_final32_kernel, dim3(1), dim3(1024), 0, st,
                  (const float*)w.slabs, p.S, p.T, p.P, B, distances, labels, lp, coef, loss_out);
       return scl_launch_status();
-    }
+    case GramFwd::Tile32:
+      SCL_LAUNCH("gram_partial_kernel", gram_partial_kernel, dim3(f.p32.splits, f.p32.npairs, 1), dim3(256),
+                 0, st, emb, ld_emb, (int64_t)0, B, E, f.p32.tiles, f.p32.kchunk, vec_ok, w.slabs);
+      SCL_LAUNCH("gram_rows_kernel", gram_rows_kernel, dim3(B), dim3(kRowThreads), f.lds, st, w.slabs,
+                 f.p32.splits, f.p32.npairs, f.p32.tiles, B, distances, labels, lp, w.gn, w.gc, w.rn,
+                 w.rowloss);
+      break;
+  }
+  if (f.route != GramFwd::Tile32) {           // slab sums -> the raw Gram, then a wave per row
     SCL_LAUNCH("gram_reduce_kernel", gram_reduce_kernel, dim3(p.P), dim3(256), 0, st,
                (const float*)w.slabs, p.S, p.T, p.P, B, w.gfull);
     const dim3 rg((B + 3) / 4);
 #define SCL_ROWS(C)                                                                          \
   SCL_LAUNCH("gram_rows_wave_kernel", gram_rows_wave_kernel<C>, rg, dim3(256), 0, st,             \
              (const float*)w.gfull, B, distances, labels, lp, w.gn, w.gc, w.rn, w.rowloss)
-    if (B <= 64)
-      SCL_ROWS(1);
-    else if (B <= 128)
-      SCL_ROWS(2);
-    else if (B <= 192)
-      SCL_ROWS(3);
-    else
-      SCL_ROWS(4);
+    if (f.rows_c == 1) SCL_ROWS(1);
+    else if (f.rows_c == 2) SCL_ROWS(2);
+    else if (f.rows_c == 3) SCL_ROWS(3);
+    else SCL_ROWS(4);
 #undef SCL_ROWS
-  } else {
-    const GramPlan p = make_plan(B, E);
-    SCL_LAUNCH("gram_partial_kernel", gram_partial_kernel, dim3(p.splits, p.npairs, 1), dim3(256),
-               0, st, emb, ld_emb, (int64_t)0, B, E, p.tiles, p.kchunk, vec_ok, w.slabs);
-    const int Bp = (B + 63) / 64 * 64;
-    const size_t lds_bytes = ((size_t)rows_part_floats(B) + 5 * (size_t)Bp) * sizeof(float);
-    SCL_LAUNCH("gram_rows_kernel", gram_rows_kernel, dim3(B), dim3(kRowThreads), lds_bytes, st,
-               w.slabs, p.splits, p.npairs, p.tiles, B, distances, labels, lp, w.gn, w.gc, w.rn,
-               w.rowloss);
   }
   SCL_LAUNCH("gram_coef_kernel", gram_coef_kernel, dim3(coef ? B : 1), dim3(256), 0, st, w.gn, w.gc, w.rn,
                      w.rowloss, B, coef, loss_out);
@@ -2204,11 +2212,50 @@ __global__ __launch_bounds__(512) void gram_bwd_planes_kernel(const float* __res
   }
 }
 
-extern "C" size_t scl_gram_loss_bwd_workspace_bytes(int B, int row_count) {
-  (void)B;
-  (void)row_count;
-  return 256;                                   // (no workspace is needed any more: kept for the ABI)
+namespace {
+enum class GramBwd { Bwd32, Planes, Rows, Fast, General };
+struct GramBwdRoute {
+  GramBwd route;
+  int n;          // Planes: NRT (16-row tiles of the 32-padded rows); Fast: TILES; General: vec_ok
+  size_t lds;
+};
+constexpr int kBwdTileLds = kTile * (kMaxB | 1) * sizeof(float);    // a 32-row tile of the widest M
+
+// Many rows (>= 96; a single-process run at B = 192) on bf16 planes; one row tile (a data-parallel
+// rank's own rows) with gram_bwd_rows_kernel; everything else with the float32-MFMA kernels.
+inline GramBwdRoute gram_bwd_route(int B, int E, int64_t ld_emb, int64_t ld_grad, const float* emb,
+                                   const float* grad, const float* coef, int row_count, const GramPins& pins) {
+  if (B <= 32) return {GramBwd::Bwd32, 0, 0};
+  // float4 loads of emb rows and float4 stores of grad rows: every kernel but the general one needs them
+  const bool rows16 = (ld_emb % 4 == 0) && (ld_grad % 4 == 0) && ((uintptr_t)emb % 16 == 0) &&
+                      ((uintptr_t)grad % 16 == 0);
+  // float4 pieces of M's rows, each inside or outside the matrix as a whole: the planes kernel only
+  const bool coef16 = ((uintptr_t)coef % 16 == 0) && B % 4 == 0;
+  const size_t lds_tile = (size_t)kTile * (B | 1) * sizeof(float);
+  const int rt = (row_count + kTile - 1) / kTile, Rp = kTile * rt;
+  const size_t lds_planes = std::max(((size_t)3 * Rp * GBP_LDM + (size_t)3 * 32 * GBP_LDE) * sizeof(unsigned short),
+                                     (size_t)Rp * GBP_LDO * sizeof(float));   // a k-step's planes | the output
+  if (pins.plain()) return {GramBwd::General, rows16, lds_tile};
+  if (B > 64 && B <= 256 && row_count >= 96 && E % 128 == 0 && rows16 && coef16 && lds_planes <= 160 * 1024 &&
+      !pins.no_bwd_planes())
+    return {GramBwd::Planes, Rp / 16, lds_planes};
+  // waves per SIMD (1024 SIMDs) with 32-, 64- or 128-column waves: take the best balanced cut
+  // (ties: the wider wave, which re-reads M less).  A rank of a data-parallel run asks for its
+  // own 24 rows of 192 (parallel.wms_loss_dp): one row tile — 32-column waves are then the only
+  // cut that puts a wave on every SIMD (64-column waves left half the chip idle: 21 us for a
+  // 25 MB read).
+  if (rows16 && rt == 1 && E % 128 == 0 && B >= 64 && B <= 512 && !pins.no_bwd_rows())
+    return {GramBwd::Rows, 0, ((size_t)((kTile * (B | 1) + 3) & ~3) + 4 * kTile * GBR_LD) * sizeof(float)};
+  if (rows16 && E % 512 == 0) {
+    const long w4 = (long)(E / 128) * rt, w2 = 2 * w4, w1 = 4 * w4;
+    const long r4 = (w4 + 1023) / 1024 * 4, r2 = (w2 + 1023) / 1024 * 2, r1 = (w1 + 1023) / 1024;
+    return {GramBwd::Fast, r1 < r2 && r1 < r4 ? 1 : (r2 < r4 ? 2 : 4), lds_tile};
+  }
+  return {GramBwd::General, rows16, lds_tile};
 }
+}  // namespace
+
+extern "C" size_t scl_gram_loss_bwd_workspace_bytes(int, int) { return 256; }   // (none needed: kept for the ABI)
 
 extern "C" int scl_gram_loss_bwd(const float* emb, int64_t ld_emb, int B, int E, const float* coef,
                                  const float* grad_loss, int row_begin, int row_count,
@@ -2216,117 +2263,68 @@ extern "C" int scl_gram_loss_bwd(const float* emb, int64_t ld_emb, int B, int E,
   if (!emb || !coef || !grad_emb) return SCL_E_NULL;
   if (B < 1 || E < 1 || ld_emb < E || ld_grad < E) return SCL_E_SHAPE;
   if (row_begin < 0 || row_count < 1 || row_begin + row_count > B || B > kMaxB) return SCL_E_SHAPE;
-  if (B <= 32) {
-    SCL_LAUNCH("gram_bwd32_kernel", gram_bwd32_kernel, dim3((E + 127) / 128), dim3(256), 0,
-               (hipStream_t)stream, emb, ld_emb, B, E, coef, grad_loss, row_begin, row_count,
-               grad_emb, ld_grad);
-    return scl_launch_status();
+  const GramBwdRoute r = gram_bwd_route(B, E, ld_emb, ld_grad, emb, grad_emb, coef, row_count, gram_pins());
+  hipStream_t st = (hipStream_t)stream;
+  const int rt = (row_count + kTile - 1) / kTile, Bp = (B + 31) & ~31;
+  // every kernel raises its own dynamic-LDS limit where it is launched (scl_lds_limit: once per device)
+#define GRAM_BWD_IN emb, ld_emb, B, E, coef, grad_loss, row_begin, row_count
+#define SCL_GBP_CASE(N)                                                                               \
+  case N:                                                                                             \
+    scl_lds_limit<&gram_bwd_planes_kernel<N>>(160 * 1024);                                            \
+    SCL_LAUNCH("gram_bwd_planes_kernel", gram_bwd_planes_kernel<N>, dim3(E / 128), dim3(512), r.lds, st, \
+               emb, ld_emb, B, Bp, E, coef, row_begin, grad_loss, row_count, grad_emb, ld_grad);      \
+    break;
+  switch (r.route) {
+    case GramBwd::Bwd32:
+      SCL_LAUNCH("gram_bwd32_kernel", gram_bwd32_kernel, dim3((E + 127) / 128), dim3(256), 0, st, GRAM_BWD_IN,
+                 grad_emb, ld_grad);
+      break;
+    case GramBwd::Planes:
+      switch (r.n) {
+        SCL_GBP_CASE(6)
+        SCL_GBP_CASE(8)
+        SCL_GBP_CASE(10)
+        SCL_GBP_CASE(12)
+        SCL_GBP_CASE(14)
+        SCL_GBP_CASE(16)
+      }
+      break;
+    case GramBwd::General:
+      scl_lds_limit<&gram_bwd_kernel>(kBwdTileLds);
+      SCL_LAUNCH("gram_bwd_kernel", gram_bwd_kernel, dim3((E + 511) / 512, rt), dim3(256), r.lds, st,
+                 GRAM_BWD_IN, r.n, grad_emb, ld_grad);
+      break;
+    case GramBwd::Fast:
+      if (r.n == 1) {
+        scl_lds_limit<&gram_bwd_fast_kernel<1>>(kBwdTileLds);
+        SCL_LAUNCH("gram_bwd_fast_kernel<1>", gram_bwd_fast_kernel<1>, dim3(E / 128, rt), dim3(256), r.lds, st,
+                   GRAM_BWD_IN, grad_emb, ld_grad);
+      } else if (r.n == 2) {
+        scl_lds_limit<&gram_bwd_fast_kernel<2>>(kBwdTileLds);
+        SCL_LAUNCH("gram_bwd_fast_kernel<2>", gram_bwd_fast_kernel<2>, dim3(E / 256, rt), dim3(256), r.lds, st,
+                   GRAM_BWD_IN, grad_emb, ld_grad);
+      } else {
+        scl_lds_limit<&gram_bwd_fast_kernel<4>>(kBwdTileLds);
+        SCL_LAUNCH("gram_bwd_fast_kernel<4>", gram_bwd_fast_kernel<4>, dim3(E / 512, rt), dim3(256), r.lds, st,
+                   GRAM_BWD_IN, grad_emb, ld_grad);
+      }
+      break;
+    case GramBwd::Rows:
+      scl_lds_limit<&gram_bwd_rows_kernel>(140 * 1024);
+      SCL_LAUNCH("gram_bwd_rows_kernel", gram_bwd_rows_kernel, dim3(E / 128), dim3(256), r.lds, st, GRAM_BWD_IN,
+                 grad_emb, ld_grad);
+      break;
   }
-  {
-    // many rows (>= 128; a single-process run at B = 192) on bf16 planes; one row tile (a
-    // data-parallel rank's own rows) stays with gram_bwd_rows_kernel, everything else with the
-    // float32-MFMA kernels
-    const int Bp = (B + 31) & ~31, Rp = (row_count + 31) & ~31;
-    const size_t lds_k = ((size_t)3 * Rp * GBP_LDM + (size_t)3 * 32 * GBP_LDE) * sizeof(unsigned short);
-    const size_t lds_o = (size_t)Rp * GBP_LDO * sizeof(float);
-    const size_t lds = lds_k > lds_o ? lds_k : lds_o;
-    const bool al = (ld_emb % 4 == 0) && ((uintptr_t)emb % 16 == 0) && (ld_grad % 4 == 0) &&
-                    ((uintptr_t)grad_emb % 16 == 0) && ((uintptr_t)coef % 16 == 0) && B % 4 == 0;
-    if (B > 64 && B <= 256 && row_count >= 96 && E % 128 == 0 && al && lds <= 160 * 1024 &&
-        scl_variant() != 32 && scl_variant() != 34) {      // (34: the float32-MFMA kernels, for A/B)
-      hipStream_t st = (hipStream_t)stream;
-#define SCL_GBP_CASE(N)                                                                          \
-  if (Rp / 16 == N) {                                                                            \
-    static SclDeviceOnce once##N;                                                               \
-    scl_call_once(once##N, [] {                                                                 \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gram_bwd_planes_kernel<N>),       \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);         \
-    });                                                                                          \
-    SCL_LAUNCH("gram_bwd_planes_kernel", gram_bwd_planes_kernel<N>, dim3(E / 128), dim3(512), lds, \
-               st, emb, ld_emb, B, Bp, E, coef, row_begin, grad_loss, row_count, grad_emb,       \
-               ld_grad);                                                                         \
-    return scl_launch_status();                                                                  \
-  }
-      SCL_GBP_CASE(6)
-      SCL_GBP_CASE(8)
-      SCL_GBP_CASE(10)
-      SCL_GBP_CASE(12)
-      SCL_GBP_CASE(14)
-      SCL_GBP_CASE(16)
 #undef SCL_GBP_CASE
-    }
-  }
-  static SclDeviceOnce once;
-  scl_call_once(once, [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gram_bwd_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)(kTile * (kMaxB | 1) * sizeof(float)));
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gram_bwd_fast_kernel<1>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)(kTile * (kMaxB | 1) * sizeof(float)));
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gram_bwd_fast_kernel<2>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)(kTile * (kMaxB | 1) * sizeof(float)));
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gram_bwd_fast_kernel<4>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)(kTile * (kMaxB | 1) * sizeof(float)));
-  });
-  {
-    const bool al = (ld_emb % 4 == 0) && (ld_grad % 4 == 0) && ((uintptr_t)emb % 16 == 0) &&
-                    ((uintptr_t)grad_emb % 16 == 0);
-    const size_t ldsf = (size_t)kTile * (B | 1) * sizeof(float);
-    const int rt = (row_count + kTile - 1) / kTile;
-    // waves per SIMD (1024 SIMDs) with 32-, 64- or 128-column waves: take the best balanced cut
-    // (ties: the wider wave, which re-reads M less).  A rank of a data-parallel run asks for its
-    // own 24 rows of 192 (parallel.wms_loss_dp): one row tile — 32-column waves are then the only
-    // cut that puts a wave on every SIMD (64-column waves left half the chip idle: 21 us for a
-    // 25 MB read).
-    if (al && rt == 1 && E % 128 == 0 && B >= 64 && B <= 512 && scl_variant() != 32 &&
-        scl_variant() != 33) {                            // (33: the 32-column waves, for A/B)
-      static SclDeviceOnce once_rows;
-      scl_call_once(once_rows, [] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gram_bwd_rows_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024);
-      });
-      const size_t lds_rows = ((size_t)((kTile * (B | 1) + 3) & ~3) + 4 * kTile * GBR_LD) * sizeof(float);
-      SCL_LAUNCH("gram_bwd_rows_kernel", gram_bwd_rows_kernel, dim3(E / 128), dim3(256), lds_rows,
-                 (hipStream_t)stream, emb, ld_emb, B, E, coef, grad_loss, row_begin, row_count, grad_emb,
-                 ld_grad);
-      return scl_launch_status();
-    }
-    if (al && E % 512 == 0 && scl_variant() != 32) {
-      const long w4 = (long)(E / 128) * rt, w2 = 2 * w4, w1 = 4 * w4;
-      const long r4 = (w4 + 1023) / 1024 * 4, r2 = (w2 + 1023) / 1024 * 2, r1 = (w1 + 1023) / 1024;
-      if (r1 < r2 && r1 < r4)
-        SCL_LAUNCH("gram_bwd_fast_kernel<1>", gram_bwd_fast_kernel<1>, dim3(E / 128, rt), dim3(256), ldsf,
-                   (hipStream_t)stream, emb, ld_emb, B, E, coef, grad_loss, row_begin, row_count,
-                   grad_emb, ld_grad);
-      else if (r2 < r4)
-        SCL_LAUNCH("gram_bwd_fast_kernel<2>", gram_bwd_fast_kernel<2>, dim3(E / 256, rt), dim3(256), ldsf,
-                   (hipStream_t)stream, emb, ld_emb, B, E, coef, grad_loss, row_begin, row_count,
-                   grad_emb, ld_grad);
-      else
-        SCL_LAUNCH("gram_bwd_fast_kernel<4>", gram_bwd_fast_kernel<4>, dim3(E / 512, rt), dim3(256), ldsf,
-                   (hipStream_t)stream, emb, ld_emb, B, E, coef, grad_loss, row_begin, row_count,
-                   grad_emb, ld_grad);
-      return scl_launch_status();
-    }
-  }
-  const int vec_ok = (ld_emb % 4 == 0) && (ld_grad % 4 == 0) && ((uintptr_t)emb % 16 == 0) &&
-                     ((uintptr_t)grad_emb % 16 == 0);
-  const size_t lds = (size_t)kTile * (B | 1) * sizeof(float);
-  dim3 grid((E + 511) / 512, (row_count + kTile - 1) / kTile);
-  SCL_LAUNCH("gram_bwd_kernel", gram_bwd_kernel, grid, dim3(256), lds, (hipStream_t)stream, emb,
-             ld_emb, B, E, coef, grad_loss, row_begin, row_count, vec_ok, grad_emb, ld_grad);
+#undef GRAM_BWD_IN
   return scl_launch_status();
 }
 
 extern "C" int scl_gram_loss_bwd_w(const float* emb, int64_t ld_emb, int B, int E, const float* coef,
                                    const float* grad_loss, int row_begin, int row_count,
-                                   float* grad_emb, int64_t ld_grad, void* workspace,
-                                   size_t workspace_bytes, void* stream) {
-  (void)workspace;                              // (an earlier form pre-split M into it; not needed)
-  (void)workspace_bytes;
+                                   float* grad_emb, int64_t ld_grad, void* /*workspace*/,
+                                   size_t /*workspace_bytes*/, void* stream) {
+  // (an earlier form pre-split M into the workspace; not needed)
   return scl_gram_loss_bwd(emb, ld_emb, B, E, coef, grad_loss, row_begin, row_count, grad_emb, ld_grad,
                            stream);
 }

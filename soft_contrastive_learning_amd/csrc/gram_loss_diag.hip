@@ -335,9 +335,7 @@ void launch_gram16_persist(const Gram16Plan& p, const float* emb, int64_t ld, in
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gram16_persist_kernel<PWMAX, FULL>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, 132 * 1024);
   });
-  size_t lds = (size_t)16 * p.T * (p.kchunk + 4) * sizeof(float);
-  const size_t red = p.KS > 1 ? (size_t)p.KS * p.P * 64 * sizeof(f32x4) : 0;
-  if (red > lds) lds = red;
+  size_t lds = gram16_lds(p);
   if (lds < 8 * 1024) lds = 8 * 1024;                         // persist_tail's tables
   SCL_LAUNCH("gram16_persist_kernel", (gram16_persist_kernel<PWMAX, FULL>), dim3(p.S), dim3(256), lds, st,
              emb, ld, E, p.kchunk, p.KS, vec_ok, slabs, pa);
@@ -350,14 +348,12 @@ static bool gram_loss_fwd_diag(const float* emb, int64_t ld_emb, int B, int E, c
                                void* sync_words, int vec_ok, const GramWs& w, hipStream_t st, int* rc) {
   const int v = scl_variant();
   if (B > kFastB || (v != 37 && v != 39 && v != 40 && v != 41)) return false;
-  Gram16Plan p = make_plan16(B, E);
-  const int ps = 4 / p.KS;
-  const int pw = (p.P + ps - 1) / ps;
-  const bool full = p.P % ps == 0;
-  const bool x6 = use_x6(B, E, ld_emb, emb);
-  const bool x6p = x6 && 16 * p.T <= kX6pMaxRows;
+  // the product's plan (none of these variants is a pin): its Gram kernel decides the persistent one
+  const GramFwdPlan f = gram_fwd_plan(B, E, vec_ok, sync_words != nullptr, GramPins{});
+  const Gram16Plan& p = f.p;
+  const bool x6p = f.route == GramFwd::X6p, x6 = x6p || f.route == GramFwd::X6;
   if (v != 37) {
-    const int grid = x6 ? E / 128 : p.S;
+    const int grid = p.S;
     if (!(B > 32 && sync_words && ((uintptr_t)sync_words % 8) == 0 && (x6p || (!x6 && B <= 64)) &&
           grid <= scl_device_cus()))
       return false;
@@ -385,11 +381,11 @@ static bool gram_loss_fwd_diag(const float* emb, int64_t ld_emb, int B, int E, c
         launch_x6_persist<true, 11>(emb, ld_emb, E, w.slabs, pa, st);
       else
         launch_x6_persist<false, 13>(emb, ld_emb, E, w.slabs, pa, st);
-    } else if (pw == 3 && full)
+    } else if (f.pw == 3 && f.full)
       launch_gram16_persist<3, true>(p, emb, ld_emb, E, vec_ok, w.slabs, pa, st);
-    else if (pw <= 3)
+    else if (f.pw <= 3)
       launch_gram16_persist<3, false>(p, emb, ld_emb, E, vec_ok, w.slabs, pa, st);
-    else if (pw <= 5)
+    else if (f.pw <= 5)
       launch_gram16_persist<5, false>(p, emb, ld_emb, E, vec_ok, w.slabs, pa, st);
     else
       return false;
@@ -398,13 +394,13 @@ static bool gram_loss_fwd_diag(const float* emb, int64_t ld_emb, int B, int E, c
   }
   // 37: the bf16x6 route through gram16x6_kernel (B > 64 there), then the product's finishing launches
   if (!x6) return false;
-  p.S = E / 128;                                          // slabs of the bf16x6 kernel
-  if (pw <= 9)
-    launch_gram16x6<9, true>(p.T, p.P, emb, ld_emb, B, E, w.slabs, st);
-  else if (pw <= 20)
-    launch_gram16x6<20, true>(p.T, p.P, emb, ld_emb, B, E, w.slabs, st);
+  const GramFwdCall c = {emb, ld_emb, B, E, vec_ok, w.slabs, st};
+  if (f.pw <= 9)
+    launch_gram16x6<9, true>(p, x6_lds_bytes(p.T), c);
+  else if (f.pw <= 20)
+    launch_gram16x6<20, true>(p, x6_lds_bytes(p.T), c);
   else
-    launch_gram16x6<34, false>(p.T, p.P, emb, ld_emb, B, E, w.slabs, st);
+    launch_gram16x6<34, false>(p, x6_lds_bytes(p.T), c);
   SCL_LAUNCH("gram_reduce_kernel", gram_reduce_kernel, dim3(p.P), dim3(256), 0, st,
              (const float*)w.slabs, p.S, p.T, p.P, B, w.gfull);
   const dim3 rg((B + 3) / 4);

@@ -320,6 +320,15 @@ template <class F> static inline void scl_call_once(SclDeviceOnce& o, F&& fn) {
   if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= 64) d = 0;
   std::call_once(o.f[d], fn);
 }
+// A kernel's dynamic-LDS limit, raised where the kernel is launched: scl_lds_limit<&kernel>(bytes).
+// The once flag belongs to the instantiation, so every kernel has its own.
+template <auto Kernel> static inline void scl_lds_limit(int bytes) {
+  static SclDeviceOnce once;
+  scl_call_once(once, [bytes] {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  });
+}
 
 static inline int scl_launch_status() { return (int)hipGetLastError(); }
 static inline bool scl_aligned256(const void* p) { return (((uintptr_t)p) & 255u) == 0; }

@@ -60,9 +60,9 @@ class _GramLoss(torch.autograd.Function):
         if nbytes == 0:
             raise ValueError("unsupported batch / embedding size B=%d E=%d" % (b, e))
         ws = L.workspace(nbytes, emb.device)
-        # With the stream's zeroed sync block the forward is ONE launch: B <= 32 the finish runs in the
-        # Gram kernel's last workgroup; 32 < B <= 208 a persistent kernel with grid barriers between
-        # its phases (csrc/gram_loss.hip, persist_tail).  Bit-identical to the multi-launch forms.
+        # With the stream's zeroed sync block the forward is ONE launch for B <= 32: the finish runs in
+        # the Gram kernel's last workgroup (bit-identical to the two launches).  The block is passed
+        # above that as well because the diagnostic variants 36 and 39-41 use it, up to B = 208.
         sync = L.sync_words(emb.device) if b <= 256 else None
         L.check(lib.scl_gram_loss_fwd_s(
             L.ptr(emb), emb.stride(0), b, e, cfg['mask_kind'], L.ptr(distances),
@@ -88,11 +88,9 @@ class _GramLoss(torch.autograd.Function):
             # a data-parallel rank only needs its own rows; the rest stay zero
             grad = torch.zeros((b, e), dtype=torch.float32, device=emb.device)
             target = grad[row_begin:row_begin + row_count]
-        # (with a workspace the many-row case runs on bf16 planes: scl_gram_loss_bwd_w)
-        ws = L.workspace(lib.scl_gram_loss_bwd_workspace_bytes(b, row_count), emb.device)
-        L.check(lib.scl_gram_loss_bwd_w(L.ptr(emb), emb.stride(0), b, e, L.ptr(coef), L.ptr(g),
-                                        row_begin, row_count, L.ptr(target), grad.stride(0),
-                                        L.ptr(ws), ws.numel(), L.stream_of(emb)))
+        L.check(lib.scl_gram_loss_bwd(L.ptr(emb), emb.stride(0), b, e, L.ptr(coef), L.ptr(g),
+                                      row_begin, row_count, L.ptr(target), grad.stride(0),
+                                      L.stream_of(emb)))
         return grad, None, None, None
 
 

@@ -100,6 +100,21 @@ def test_workspace_queries_are_pure_host_functions(lib):
     assert lib.scl_netvlad_bwd_workspace_bytes(24, 1200) % 256 == 0
     assert lib.scl_gram_loss_workspace_bytes(24, 32768) > 0
     assert lib.scl_gram_loss_workspace_bytes(5000, 32768) == 0          # B above the cap
+    # both sides of every route boundary of the forward (fused | float32 Gram | strip-scheduled bf16x6 |
+    # bf16x6 | 32x32 tiles), E a multiple of the bf16x6 slice and not: the byte counts of the library
+    # before the forward's routes and this query read one plan
+    want = {
+        (32, 128): 22016, (32, 200): 28160, (32, 32768): 212480,
+        (33, 128): 32768, (33, 200): 45056, (33, 32768): 1593344,
+        (64, 128): 80384, (64, 200): 100864, (64, 32768): 2681344,
+        (65, 128): 98560, (65, 200): 129280, (65, 32768): 4000000,
+        (208, 128): 800768, (208, 200): 987136, (208, 32768): 24469504,
+        (209, 128): 849152, (209, 200): 1064192, (209, 32768): 28159232,
+        (256, 128): 1206272, (256, 200): 1484800, (256, 32768): 36579328,
+        (257, 128): 1689856, (257, 200): 2242816, (257, 32768): 5007616,
+    }
+    got = {k: lib.scl_gram_loss_workspace_bytes(*k) for k in want}
+    assert got == want
     assert lib.scl_topn_l2_workspace_bytes(100000, 10000, 256, 25) > 100000 * 4
     assert lib.scl_topn_l2_workspace_bytes(100, 10, 100, 5) == 0         # unsupported d
     assert lib.scl_topn_l2_workspace_bytes(100, 10, 64, 26) == 0         # n above the cap

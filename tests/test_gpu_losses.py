@@ -526,3 +526,97 @@ def test_gram_backward_on_bf16_planes(dev, b, row_begin, row_count, e):
     planes = 'gram_bwd_planes_kernel' in outs[0][1]
     assert planes == (64 < b <= 256 and b % 4 == 0 and row_count >= 96 and e % 128 == 0), outs[0][1]
     assert 'gram_bwd_planes_kernel' not in outs[34][1]
+
+
+# ---- the route table: which kernels serve which (B, E, alignment) --------------------------------
+_FINISH = ['gram_reduce_kernel', 'gram_rows_wave_kernel', 'gram_coef_kernel']
+_ROUTES = [
+    # wms_loss (exp / ms) forward + backward: (B, E, how, forward launches, backward launches)
+    ('fwd', 7, 100, 'default', ['gram16_fused_kernel'], ['gram_bwd32_kernel']),
+    ('fwd', 24, 256, 'c_entry_no_sync', ['gram16_kernel', 'gram_final32_kernel'], ['gram_bwd32_kernel']),
+    ('fwd', 40, 256, 'default', ['gram16_kernel'] + _FINISH, ['gram_bwd_kernel']),
+    ('fwd', 64, 256, 'default', ['gram16_kernel'] + _FINISH, ['gram_bwd_kernel']),
+    ('fwd', 72, 256, 'default', ['gram16x6p_kernel'] + _FINISH, ['gram_bwd_kernel']),
+    ('fwd', 200, 256, 'default', ['gram16x6p_kernel'] + _FINISH, ['gram_bwd_planes_kernel']),
+    ('fwd', 224, 256, 'default', ['gram16x6_kernel'] + _FINISH, ['gram_bwd_planes_kernel']),
+    ('fwd', 72, 200, 'default', ['gram16_kernel'] + _FINISH, ['gram_bwd_kernel']),
+    ('fwd', 100, 200, 'default', ['gram16_kernel'] + _FINISH, ['gram_bwd_kernel']),
+    ('fwd', 144, 200, 'default', ['gram16_kernel'] + _FINISH, ['gram_bwd_kernel']),
+    ('fwd', 256, 200, 'default', ['gram16_kernel'] + _FINISH, ['gram_bwd_kernel']),
+    ('fwd', 72, 256, 'row_stride_258', ['gram16_kernel'] + _FINISH, ['gram_bwd_kernel']),
+    ('fwd', 260, 256, 'default', ['gram_partial_kernel', 'gram_rows_kernel', 'gram_coef_kernel'],
+     ['gram_bwd_kernel']),
+    # scl_gram_loss_bwd alone: (B, E, (row_begin, row_count, output row stride), -, launches)
+    ('bwd', 24, 200, (0, 24, 200), None, ['gram_bwd32_kernel']),
+    ('bwd', 96, 128, (0, 96, 128), None, ['gram_bwd_planes_kernel']),
+    ('bwd', 96, 128, (8, 24, 128), None, ['gram_bwd_rows_kernel']),
+    ('bwd', 40, 512, (0, 40, 512), None, ['gram_bwd_fast_kernel<1>']),
+    ('bwd', 264, 4096, (0, 264, 4096), None, ['gram_bwd_fast_kernel<2>']),
+    ('bwd', 300, 32768, (0, 100, 32768), None, ['gram_bwd_fast_kernel<4>']),
+    ('bwd', 40, 200, (0, 40, 200), None, ['gram_bwd_kernel']),
+    ('bwd', 96, 128, (0, 96, 130), None, ['gram_bwd_kernel']),
+]
+
+
+@pytest.mark.parametrize('side,b,e,how,fwd_names,bwd_names', _ROUTES,
+                         ids=['%s-%d-%d-%s' % (r[0], r[1], r[2], str(r[3]).replace(' ', '')) for r in _ROUTES])
+def test_route_table(dev, side, b, e, how, fwd_names, bwd_names):
+    """Every route of the pairwise loss's two entry points, by the ordered launch labels of one call
+    (the table is what the library launched before the routes were gathered into one plan), with
+    the values checked by the file's own bounds: the loss against the oracle (REL), the gradient
+    against the float64 twin (GRAD_REL), a backward alone against float64 g * coef[rows] @ emb
+    (2e-6 of its largest entry, as test_gram_backward_on_bf16_planes)."""
+    from soft_contrastive_learning_amd import _lib as L
+    from soft_contrastive_learning_amd.model import losses
+    lib = L.load()
+    if side == 'bwd':
+        row_begin, row_count, ldg = how
+        g = torch.Generator().manual_seed(b * 1000 + e)
+        emb = torch.randn(b, e, generator=g).to(dev)
+        coef = (torch.randn(b, b, generator=g) * torch.rand(b, b, generator=g).pow(4)).to(dev)
+        gl = torch.tensor([0.37], device=dev)
+        want = 0.37 * (coef.double()[row_begin:row_begin + row_count] @ emb.double())
+        out = torch.full((row_count, ldg), 7.0, device=dev)
+        with L.KernelTimer(capacity=16) as kt:
+            L.check(lib.scl_gram_loss_bwd(L.ptr(emb), e, b, e, L.ptr(coef), L.ptr(gl), row_begin, row_count,
+                                          L.ptr(out), ldg, L.stream_of(emb)))
+            torch.cuda.synchronize()
+        names = [n for n, _ in kt.records]
+        print('route', side, b, e, how, names)
+        assert names == bwd_names
+        err = float((out[:, :e].double() - want).abs().max() / want.abs().max())
+        assert err < 2e-6, err
+        assert bool((out[:, e:] == 7.0).all())                 # the padding of a wider row is not written
+        return
+    ld = 258 if how == 'row_stride_258' else e
+    emb_np = np.ascontiguousarray(U.embeddings(b, ld)[:, :e])
+    dist = U.positions_distances(b, side=60.0 if b < 64 else 200.0)
+    want = O.wms_loss(dist[None], emb_np, 0.8, 15.0)
+    assert np.isfinite(want) and want != 0.0                   # or the relative bound would be vacuous
+    _, grad64 = _twin_grad(lambda t: TT.wms_loss(dist[None], t, 0.8, 15.0), emb_np)
+    dt = torch.tensor(dist[None], device=dev)
+    full = torch.tensor(U.embeddings(b, ld), device=dev, requires_grad=True)
+    x = full[:, :e] if ld != e else full
+    with L.KernelTimer(capacity=16) as kt:
+        if how == 'c_entry_no_sync':
+            loss = torch.empty((), device=dev)
+            coef = torch.empty((b, b), device=dev)
+            ws = L.workspace(lib.scl_gram_loss_workspace_bytes(b, e), dev)
+            L.check(lib.scl_gram_loss_fwd(
+                L.ptr(x), ld, b, e, L.MASK_WMS_EXP, L.ptr(dt), 1, 0.8, 15.0, None, 2.0, 50.0, 1.0, 0.1, 1,
+                L.SUM_MS, L.ptr(loss), L.ptr(coef), L.ptr(ws), ws.numel(), L.stream_of(dt)))
+            grad = torch.empty((b, e), device=dev)
+            L.check(lib.scl_gram_loss_bwd(L.ptr(x), ld, b, e, L.ptr(coef), None, 0, b, L.ptr(grad), e,
+                                          L.stream_of(dt)))
+        else:
+            loss = losses.wms_loss(dt, x, 0.8, 15.0)
+            loss.backward()
+            grad = full.grad[:, :e]
+        torch.cuda.synchronize()
+    names = [n for n, _ in kt.records]
+    print('route', side, b, e, how, names)
+    assert names == fwd_names + bwd_names
+    _close(loss, want)
+    assert _rel(grad.cpu().numpy(), grad64) < GRAD_REL
+    if ld != e:
+        assert float(full.grad[:, e:].abs().sum()) == 0.0
