@@ -735,6 +735,28 @@ int scl_eigen_loss_fwd(int kind, const float* z, const float* pos_w, const float
                        float* coef_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Batch assembly from device-resident uint8 frames (csrc/frames.hip; train/frame_bank.py keeps
+ * every frame the trainer has loaded on the device and builds each float32 batch there, in
+ * place of a host decode + resize + float32 upload per use).
+ *
+ *   bank    uint8 [bank_slots, frame_bytes], dense; may be NULL when bank_slots = 0
+ *   extra   uint8 [extra_slots, frame_bytes], dense; may be NULL when extra_slots = 0: the
+ *           frames of this batch that are not in the bank
+ *   slots   int32 [n] ON THE DEVICE: s >= 0 takes frame s of bank, s < 0 frame -s-1 of extra
+ *   out     float32 [n, frame_bytes]: out[k, i] = (float) source[i], exact for every byte
+ * bank, extra and the frames inside them may lie at any byte address (the kernel decides per
+ * frame between dword loads / float4 stores and a byte-wise path); out must be 4-byte aligned.
+ * A slot outside its source reads nothing and fills its output frame with NaN — the caller
+ * validates the slot list, which the launcher cannot see.
+ * Returns SCL_E_NULL for out or slots NULL, or a NULL source with a positive slot count;
+ * SCL_E_SHAPE for n outside 1..65535, frame_bytes outside 1..2^30, a slot count that is negative
+ * or >= 2^31, both slot counts 0, or a misaligned out; nothing is launched then.
+ * ------------------------------------------------------------------------- */
+int scl_frames_gather(const void* bank, long long bank_slots, const void* extra,
+                      long long extra_slots, const int* slots, int n, long long frame_bytes,
+                      void* out, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Host utility for the checkpoint bundle reader / writer (tf_bundle.py; the reference
  * restores and saves through tf.train.Saver, train/train.py:882-905, 984, 1079, 1102):
  * CRC-32C (Castagnoli, reflected 0x82F63B78) of n bytes continued from `crc` (0 to start),

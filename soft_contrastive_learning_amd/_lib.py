@@ -148,6 +148,7 @@ SIGNATURES = {
                                    _p]),
     "scl_eigen_loss_workspace_bytes": (_z, [_i, _i, _i, _i]),
     "scl_eigen_loss_fwd": (_i, [_i, _p, _p, _p, _i, _i, _i, _i, _f, _i, _p, _p, _p, _p, _z, _p]),
+    "scl_frames_gather": (_i, [_p, _l, _p, _l, _p, _i, _l, _p, _p]),
 }
 
 _libs = {}

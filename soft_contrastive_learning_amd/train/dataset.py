@@ -139,9 +139,20 @@ class CsvImageSet:
     def load_image(self, i):
         return load_frame(self.path(int(i)), self.vlad_cores, self.max_side, self.standard)
 
+    def frame_key(self, i):
+        """What decides the pixels ``load_frames_u8`` returns for row i: the file and the sizing
+        parameters.  The per-epoch lists re-order the same files, so this key carries a frame
+        across epochs and across sets (train/frame_bank.py)."""
+        return (self.path(int(i)), self.vlad_cores, self.max_side, self.standard)
+
     def load_images(self, indices):
         """float32 [n,H,W,3], 0..255 RGB (all images of a batch must come out the same size, as
         in the reference, whose feed would fail otherwise)."""
+        return self.load_frames_u8(indices).astype(np.float32)
+
+    def load_frames_u8(self, indices):
+        """uint8 [n,H,W,3]: the frames of ``load_images`` as the loader produces them, before the
+        cast to float32."""
         indices = [int(i) for i in indices]
         frames = None
         if self._procs is not None and len(indices) > 1:
@@ -157,7 +168,7 @@ class CsvImageSet:
             frames = list(self._pool.map(self.load_image, indices))
         else:
             frames = [self.load_image(i) for i in indices]
-        return np.stack(frames).astype(np.float32)
+        return np.stack(frames)
 
 
 class SyntheticImageSet:

@@ -12,6 +12,7 @@ import torch
 
 from ..evaluation import retrieval
 from ..model import nets
+from .frame_bank import to_device
 
 
 def extract_features(model, image_set, indices, images_per_pass):
@@ -26,7 +27,7 @@ def extract_features(model, image_set, indices, images_per_pass):
     outs = []
     with torch.no_grad():
         for s in range(0, len(padded), images_per_pass):
-            img = torch.from_numpy(image_set.load_images(padded[s:s + images_per_pass])).to(dev)
+            img = to_device(image_set.load_images(padded[s:s + images_per_pass]), dev)
             outs.append(nets.output(img, model=model).float())
     return torch.cat(outs, 0)[:len(idx)]
 
@@ -80,7 +81,7 @@ def eval_loss(step_loss, sampler, image_set, indices, tuples_per_batch, tuple_sh
         distances, every = sampler.get_tuple(idx[s:s + tuples_per_batch], tuple_shape, False)
         if len(every) != tuples_per_batch * sum(tuple_shape):
             continue
-        images = torch.from_numpy(image_set.load_images(every)).to(device)
+        images = to_device(image_set.load_images(every), device)
         losses.append(float(step_loss(distances, images)))
     return (float(np.mean(losses)) if losses else None), len(losses)
 

@@ -18,6 +18,13 @@ schedule (:118-121), the optimisers (:865-878) and the three checkpoint cadences
 * default: ``SyntheticTuples`` — random images with the per-loss ``distances`` payload the GPU
   thread receives (:263-275); what bench.py's workload looks like.
 
+``--frame_cache_mb MB`` (default 0: off) keeps every frame of the ``--shuffled_root`` sets on the
+device as the uint8 pixels the loader produced and assembles every batch — training, mining
+refresh, evaluation — there with one HIP kernel (train/frame_bank.py, csrc/frames.hip): a file
+is decoded, resized and uploaded once per run instead of once per use.  The batches are the same
+float32 values bit for bit; each ``epoch`` record of the log then carries the bank's counters.
+One bank per process (per rank), fill-only: frames beyond the capacity travel with their batch.
+
 Of the eigenvalue and residual-determinant families wrd, prodwrd, sumwrd, residual_trace,
 ntuplet_evmm, ntuplet_trace and ms_sum train here (model/losses.py).  Still refused:
 
@@ -119,6 +126,10 @@ def make_parser():
     p.add_argument('--loader_processes', type=int, default=0,
                    help='worker processes decoding the frames of --shuffled_root sets (0: threads only). '
                         'Created before the device is initialised; ignored when it already is')
+    p.add_argument('--frame_cache_mb', type=float, default=0.0,
+                   help='> 0: keep every frame of the --shuffled_root sets on the device as uint8, up to '
+                        'this many MiB, and assemble the batches there (train/frame_bank.py); a frame is '
+                        'then decoded, resized and uploaded once per run.  Same batches bit for bit')
     p.add_argument('--force_dist', type=int, default=0,
                    help='single process only: form a ONE-rank RCCL process group and take the data-parallel '
                         'routes through it (the collective path on a one-GPU box)')
@@ -362,24 +373,27 @@ def next_cadence(step, every, stride, world, n_anchors):
 def loc_ref_set(flags, ref_set_name):
     """The thinned reference list the localisation check runs against:
     <loc_ref_root>/<ref_set>_<eval_ref_r>.csv (train/train.py:1158)."""
-    from . import dataset
-    return dataset.CsvImageSet(os.path.join(flags.loc_ref_root,
-                                            '{}_{}.csv'.format(ref_set_name, flags.eval_ref_r)),
-                               flags.img_root, vlad_cores=flags.vlad_cores, need_yaw=False)
+    from . import dataset, frame_bank
+    return frame_bank.wrap(
+        dataset.CsvImageSet(os.path.join(flags.loc_ref_root,
+                                         '{}_{}.csv'.format(ref_set_name, flags.eval_ref_r)),
+                            flags.img_root, vlad_cores=flags.vlad_cores, need_yaw=False),
+        getattr(flags, 'frame_bank', None))
 
 
 def open_sets(flags, epoch):
     """(local_ref, local_query, other_ref, other_query) image sets of an epoch."""
-    from . import dataset
+    from . import dataset, frame_bank
     if flags.shuffled_root:
         def one(name):
             # (image size: the reference's fixed rule, train/train.py:423-430 — longer side 240 with
             # the NetVLAD head, 180 x 240 cover-and-crop without; --height / --width are the
             # synthetic set's)
-            return dataset.CsvImageSet(os.path.join(flags.shuffled_root,
-                                                    '%s_%03d.csv' % (name, epoch)),
-                                       flags.img_root, vlad_cores=flags.vlad_cores,
-                                       pool=getattr(flags, 'loader_pool', None))
+            return frame_bank.wrap(
+                dataset.CsvImageSet(os.path.join(flags.shuffled_root, '%s_%03d.csv' % (name, epoch)),
+                                    flags.img_root, vlad_cores=flags.vlad_cores,
+                                    pool=getattr(flags, 'loader_pool', None)),
+                getattr(flags, 'frame_bank', None))
         return (one(flags.local_ref_set), one(flags.local_query_set), one(flags.other_ref_set),
                 one(flags.other_query_set))
     m = flags.synthetic_dataset
@@ -410,6 +424,7 @@ def train_dataset_epoch(flags, epoch, state, log):
     extracted in shards and all-gathered, and rank 0 alone logs and writes checkpoints; the
     evaluations run on every rank alike (no collective inside them)."""
     from . import evaluate, mining
+    from .frame_bank import to_device
     from .sampler import InputPipeline, TupleSampler
     model, opt, buckets, saver, dev = (state[k] for k in ('model', 'opt', 'buckets', 'saver', 'dev'))
     group = state.get('group')
@@ -453,9 +468,12 @@ def train_dataset_epoch(flags, epoch, state, log):
     for g in opt.param_groups:
         g['lr'] = lr
     if rank == 0:
-        log({'event': 'epoch', 'epoch': epoch, 'anchors': int(len(anchors)),
-             'anchor_source': 'list' if flags.anchor_root else 'permutation',
-             'first_anchors': [int(a) for a in anchors[:4]], 'learning_rate': lr})
+        rec = {'event': 'epoch', 'epoch': epoch, 'anchors': int(len(anchors)),
+               'anchor_source': 'list' if flags.anchor_root else 'permutation',
+               'first_anchors': [int(a) for a in anchors[:4]], 'learning_rate': lr}
+        if state.get('frame_bank') is not None:          # --frame_cache_mb: the bank as the epoch finds it
+            rec['frame_bank'] = state['frame_bank'].stats
+        log(rec)
 
     def loss_of(distances, images):
         """Single-process loss (the evaluation on the other region: every rank alike)."""
@@ -490,7 +508,7 @@ def train_dataset_epoch(flags, epoch, state, log):
             return                                              # 'Faulty training batch'
         distances, images, indices = item
         buckets.zero()
-        loss = train_loss(distances, torch.from_numpy(images).to(dev), indices)
+        loss = train_loss(distances, to_device(images, dev), indices)
         loss.backward()
         buckets.finish()
         opt.step()
@@ -693,8 +711,14 @@ def main(argv=None):
                 b.flush()
 
     if flags.synthetic_dataset > 0 or flags.shuffled_root:
+        # one bank per process for the whole run: the per-epoch lists re-order the same files
+        flags.frame_bank = None
+        if flags.frame_cache_mb > 0 and flags.shuffled_root:
+            from .frame_bank import FrameBank
+            flags.frame_bank = FrameBank(int(flags.frame_cache_mb * 2 ** 20), dev)
         state = dict(model=model, opt=opt, buckets=buckets, saver=saver, dev=dev,
-                     tuple_shape=tuple_shape, step=step, group=group, boards=boards)
+                     tuple_shape=tuple_shape, step=step, group=group, boards=boards,
+                     frame_bank=flags.frame_bank)
 
         def write(rec):
             if log is not None:
@@ -710,6 +734,9 @@ def main(argv=None):
                 b.close()
             if flags.loader_pool is not None:
                 flags.loader_pool.shutdown()
+            if flags.frame_bank is not None:
+                state['frame_bank_stats'] = flags.frame_bank.stats
+                flags.frame_bank.close()
         return state
 
     for epoch in range(flags.max_epoch):
