@@ -757,6 +757,86 @@ int scl_frames_gather(const void* bank, long long bank_slots, const void* extra,
                       void* out, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * The parameter update (csrc/optim.hip; train/optim.py HipAdam / HipMomentum): TensorFlow's
+ * ApplyAdam and ApplyMomentum (non-Nesterov) for a whole LIST of float32 parameters in one launch,
+ * every operation a float32 operation rounded on its own (no contraction into fused multiply-adds,
+ * IEEE division and square root, denormals kept): the bits of oracle/adam_np.py.
+ *
+ *   scl_apply_adam, per element, with the powers as they are on entry:
+ *     one_minus_b1 = 1 - beta1;  one_minus_b2 = 1 - beta2
+ *     alpha = (lr * sqrt(1 - beta2_power)) / (1 - beta1_power)
+ *     m   = m + (g - m) * one_minus_b1
+ *     v   = v + (g * g - v) * one_minus_b2
+ *     var = var - (m * alpha) / (sqrt(v) + epsilon)
+ *   and, once per call, after every element has been updated:
+ *     beta1_power *= beta1;  beta2_power *= beta2;  step += 1
+ *   scl_apply_momentum, per element:
+ *     accum = accum * momentum + g;  var = var - lr * accum
+ *
+ *   segs   [nseg] SclOptimSeg ON THE DEVICE, owned by the caller and alive until the call has
+ *          run.  Row s: var, grad, slot0 (Adam m | the momentum accumulator), slot1 (Adam v;
+ *          ignored by momentum), the element count n >= 1 and first_chunk.  A segment is served by
+ *          chunks(n) = max(1, ceil(floor(n / 4) / SCL_OPTIM_CHUNK_GROUPS)) workgroups;
+ *          first_chunk is the sum of chunks() over the rows in front of it (0 for row 0), and
+ *          total_chunks that sum over all rows: the launch has total_chunks workgroups, each of
+ *          which finds its row by first_chunk.  A row whose first_chunk claims fewer chunks than
+ *          chunks(n) leaves elements without an update; no workgroup ever touches an element at
+ *          or beyond n.  The four arrays of a row may start at any 4-byte aligned address, each
+ *          at its own alignment (gradients are views into one flat buffer): the values in front
+ *          of var's first 16-byte boundary and the last n mod 4 go one by one, the rest as
+ *          16-byte vectors.  Rows must not overlap one another.
+ *   state  SclOptimState ON THE DEVICE, owned by the caller, who initialises it to
+ *          {beta1, beta2, 0, 0}: the two float32 power accumulators of TensorFlow's optimizer,
+ *          the number of calls applied and a ticket word that is 0 on entry and 0 on return
+ *          (the workgroup that draws the last ticket advances the state; nothing waits)
+ *   lr     device float32: read by the kernel, so a captured graph sees a new value on replay
+ *   skip   device word or NULL.  Where it points to a non-zero word the call changes no var, no
+ *          slot, neither power and not the step (the ticket still returns to 0).
+ *          scl_grad_stats writes such a word.
+ * Return SCL_E_NULL for segs, state or lr NULL; SCL_E_SHAPE for nseg outside 1..2^20 or
+ * total_chunks outside nseg..2^24; nothing is launched then.
+ * ------------------------------------------------------------------------- */
+#define SCL_OPTIM_CHUNK_GROUPS 1024   /* 16-byte groups (four float32) per workgroup */
+typedef struct SclOptimSeg {
+  void* var;
+  const void* grad;
+  void* slot0;
+  void* slot1;
+  long long n;
+  long long first_chunk;
+} SclOptimSeg;
+typedef struct SclOptimState {
+  float beta1_power;
+  float beta2_power;
+  int step;
+  unsigned ticket;
+} SclOptimState;
+int scl_apply_adam(const SclOptimSeg* segs, int nseg, long long total_chunks, SclOptimState* state,
+                   const float* lr, float beta1, float beta2, float epsilon, const unsigned* skip,
+                   void* stream);
+int scl_apply_momentum(const SclOptimSeg* segs, int nseg, long long total_chunks, const float* lr,
+                       float momentum, const unsigned* skip, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * One pass over a float32 gradient buffer (csrc/optim.hip): its squared norm and whether it
+ * holds anything that is not a number.
+ *
+ *   g      float32 [n], any 4-byte aligned address, 1 <= n <= 2^40
+ *   out    device float64 [2]: out[0] = sum of squares of the FINITE entries, out[1] = the number
+ *          of non-finite entries (NaN, +inf, -inf)
+ *   flag   device word: 1 where out[1] > 0, else 0; written by every call (the `skip` word of
+ *          scl_apply_adam / scl_apply_momentum)
+ * Squares and sums are float64 (a float32 squared is exact in it); the order of summation is
+ * fixed by n alone — per-workgroup partials in the workspace, then one fixed-order finish, no
+ * floating-point atomics — so two calls on the same data give the same bits.
+ * workspace: scl_grad_stats_workspace_bytes(n) bytes, 256-byte aligned (0 for n < 1 or above the cap).
+ * Returns SCL_E_NULL, SCL_E_SHAPE (n, a misaligned g), SCL_E_WORKSPACE; nothing is launched then.
+ * ------------------------------------------------------------------------- */
+size_t scl_grad_stats_workspace_bytes(long long n);
+int scl_grad_stats(const float* g, long long n, double* out, unsigned* flag, void* workspace,
+                   size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Host utility for the checkpoint bundle reader / writer (tf_bundle.py; the reference
  * restores and saves through tf.train.Saver, train/train.py:882-905, 984, 1079, 1102):
  * CRC-32C (Castagnoli, reflected 0x82F63B78) of n bytes continued from `crc` (0 to start),

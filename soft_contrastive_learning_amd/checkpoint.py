@@ -61,7 +61,9 @@ def _from_tf(a, is_conv, like):
 def optimizer_slots(model, optimizer):
     """torch.optim.Adam state under TF's slot-variable names (AdamOptimizer creates
     ``<var>/Adam`` = m, ``<var>/Adam_1`` = v and the two ``beta*_power`` accumulators, which
-    hold beta^(t+1) after t updates); SGD momentum uses ``<var>/Momentum``."""
+    hold beta^(t+1) after t updates — computed from the step count for torch's Adam, the float32
+    accumulators themselves where the optimizer keeps them: train/optim.py HipAdam); SGD momentum
+    uses ``<var>/Momentum``."""
     out = {}
     steps = 0
     beta1 = beta2 = None
@@ -76,7 +78,12 @@ def optimizer_slots(model, optimizer):
     for g in optimizer.param_groups:
         if 'betas' in g:
             beta1, beta2 = g['betas']
-    if beta1 is not None:
+    if beta1 is not None and hasattr(optimizer, 'beta_powers'):
+        # train/optim.py HipAdam: the float32 accumulators themselves, as a TensorFlow run saves them
+        b1p, b2p, _ = optimizer.beta_powers()
+        out['beta1_power'] = np.asarray(b1p, dtype=np.float32)
+        out['beta2_power'] = np.asarray(b2p, dtype=np.float32)
+    elif beta1 is not None:
         out['beta1_power'] = np.asarray(beta1 ** (steps + 1), dtype=np.float32)
         out['beta2_power'] = np.asarray(beta2 ** (steps + 1), dtype=np.float32)
     return out
@@ -111,6 +118,10 @@ def restore_optimizer(model, optimizer, variables):
             optimizer.state[p]['momentum_buffer'] = _from_tf(variables[name + '/Momentum'],
                                                              is_conv, p)
             done += 1
+    if hasattr(optimizer, 'set_beta_powers') and 'beta1_power' in variables and 'beta2_power' in variables:
+        # the stored accumulators verbatim (and the step words of the slots restored above)
+        optimizer.set_beta_powers(np.float32(np.asarray(variables['beta1_power'])),
+                                  np.float32(np.asarray(variables['beta2_power'])), steps)
     return done
 
 

@@ -25,6 +25,15 @@ is decoded, resized and uploaded once per run instead of once per use.  The batc
 float32 values bit for bit; each ``epoch`` record of the log then carries the bank's counters.
 One bank per process (per rank), fill-only: frames beyond the capacity travel with their batch.
 
+``--optimizer_impl hip`` (default ``torch``) takes the parameter update from this package's own
+kernel instead of torch's fused one (train/optim.py HipAdam / HipMomentum, csrc/optim.hip): one
+launch over every parameter, TensorFlow's float32 sequence bit for bit, the two beta powers
+float32 accumulators on the device, which the checkpoints then store as they are.  Float32
+parameters only.  With it, ``--skip_nonfinite 1`` runs one pass over the flat gradient buffer
+before the update (scl_grad_stats) and hands its flag to the kernel: a step whose gradients hold
+a NaN or an infinity changes no weight, no slot and not the step count, and says so in one line;
+every step record then carries ``grad_norm`` and ``skipped``.
+
 Of the eigenvalue and residual-determinant families wrd, prodwrd, sumwrd, residual_trace,
 ntuplet_evmm, ntuplet_trace and ms_sum train here (model/losses.py).  Still refused:
 
@@ -54,7 +63,7 @@ import torch.distributed as dist
 
 from .. import checkpoint, parallel, pointnetvlad_cls
 from ..model import losses, nets, reduction
-from .optim import make_optimizer
+from .optim import GradStats, make_optimizer
 
 
 def make_parser():
@@ -94,6 +103,12 @@ def make_parser():
     p.add_argument('--lr_down_frequency', type=float, default=1)
     p.add_argument('--momentum', type=float, default=0.9)
     p.add_argument('--optimizer', default='adam', help='adam, momentum')
+    p.add_argument('--optimizer_impl', default='torch', choices=['torch', 'hip'],
+                   help="torch: the update on torch's fused kernels (TFAdam / SGD); hip: this package's "
+                        'update kernel, TensorFlow\'s float32 sequence bit for bit (train/optim.py)')
+    p.add_argument('--skip_nonfinite', type=int, default=0,
+                   help='1 (needs --optimizer_impl hip): a step whose gradients hold a NaN or an infinity '
+                        'changes nothing; every step record carries grad_norm and skipped')
     # head (:1283-1289): none, or a dense reduction head 1fc|2fc|3fc of --out_dim units
     # (model/reduction.py); spp and the training-time pca need reference modules that do not exist
     p.add_argument('--out_dim', default=512, type=int)
@@ -199,6 +214,27 @@ SUPPORTED_LOSSES = ('triplet', 'lazy_triplet', 'evil_triplet', 'quadruplet', 'la
 # losses that take the reference's default ``dimensions = 10`` singular values of EACH side
 SIDE_DIMENSIONS_LOSSES = ('residual_trace', 'ms_sum')
 SIDE_DIMENSIONS = 10
+
+
+def guarded_step(opt, guard):
+    """The update of one step, after buckets.finish().  With --skip_nonfinite, one pass over the flat
+    gradient buffer first (scl_grad_stats): its flag is the optimizer's skip word, so a step with a
+    non-finite gradient leaves weights, slots and step count as they were — decided on the device,
+    nothing waits here."""
+    if guard is not None:
+        guard.run()
+    opt.step()
+
+
+def guard_fields(guard, step=None):
+    """grad_norm / skipped of the step record (read where the loop waits for the loss anyway); a
+    skipped step prints one line."""
+    if guard is None:
+        return {}
+    sumsq, bad = guard.read()
+    if bad:
+        print('Skipped step{}: {} non-finite gradient values'.format('' if step is None else ' %d' % step, bad))
+    return {'grad_norm': float(np.sqrt(sumsq)), 'skipped': int(bad > 0)}
 
 
 def check_tuple_sizes(flags):
@@ -427,6 +463,7 @@ def train_dataset_epoch(flags, epoch, state, log):
     from .frame_bank import to_device
     from .sampler import InputPipeline, TupleSampler
     model, opt, buckets, saver, dev = (state[k] for k in ('model', 'opt', 'buckets', 'saver', 'dev'))
+    guard = state.get('guard')
     group = state.get('group')
     world = dist.get_world_size(group) if group is not None else 1
     rank = dist.get_rank(group) if group is not None else 0
@@ -511,10 +548,11 @@ def train_dataset_epoch(flags, epoch, state, log):
         loss = train_loss(distances, to_device(images, dev), indices)
         loss.backward()
         buckets.finish()
-        opt.step()
+        guarded_step(opt, guard)
         state['step'] += 1
         rec = {'step': state['step'], 'epoch': epoch, 'loss': float(loss.detach()),
                'learning_rate': lr}
+        rec.update(guard_fields(guard, state['step']))
         if rank == 0:
             print('Train batch loss: {}'.format(rec['loss']))      # :289
             log(rec)
@@ -644,6 +682,9 @@ def main(argv=None):
     if flags.vlad_cores not in (0, 64) or flags.reduction not in ('none',) + reduction.KINDS:
         raise SystemExit('only --vlad_cores 64 | 0 with --reduction none|1fc|2fc|3fc is on the hot path')
     check_tuple_sizes(flags)
+    if flags.skip_nonfinite and flags.optimizer_impl != 'hip':
+        raise SystemExit('--skip_nonfinite 1 needs --optimizer_impl hip: the skip is decided on the device, '
+                         'inside the update kernel')
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
     local_rank = int(os.environ.get('LOCAL_RANK', '0'))
@@ -677,7 +718,11 @@ def main(argv=None):
     nets.GRAD_SINK = buckets       # conv weight / bias gradients go straight into the flat buffer
     # train/train.py:865-870: MomentumOptimizer / AdamOptimizer — TF's Adam (epsilon outside the bias
     # correction), not torch's: train/optim.py
-    opt = make_optimizer(flags.optimizer, params, flags.base_lr, flags.momentum)
+    opt = make_optimizer(flags.optimizer, params, flags.base_lr, flags.momentum, impl=flags.optimizer_impl)
+    guard = None
+    if flags.skip_nonfinite:             # one pass over the flat gradients; its flag is the skip word
+        guard = GradStats(buckets.flat)
+        opt.skip_flag = guard.flag
     # restore_weights (:882-905) + the slot variables a tf.train.Saver checkpoint carries
     step = restore(flags, model, opt, verbose=rank == 0)
     out_dir = os.path.join(flags.out_root, flags.out_folder or flags.loss)
@@ -718,7 +763,7 @@ def main(argv=None):
             flags.frame_bank = FrameBank(int(flags.frame_cache_mb * 2 ** 20), dev)
         state = dict(model=model, opt=opt, buckets=buckets, saver=saver, dev=dev,
                      tuple_shape=tuple_shape, step=step, group=group, boards=boards,
-                     frame_bank=flags.frame_bank)
+                     frame_bank=flags.frame_bank, guard=guard)
 
         def write(rec):
             if log is not None:
@@ -751,11 +796,12 @@ def main(argv=None):
             loss = compute_loss(flags, tuple_shape, output, distances, group=group)
             loss.backward()
             buckets.finish()
-            opt.step()
+            guarded_step(opt, guard)
             step += 1
             if rank == 0:
                 rec = {'step': step, 'epoch': epoch, 'loss': float(loss.detach()),
                        'learning_rate': lr, 'sec': round(time.time() - t0, 4)}
+                rec.update(guard_fields(guard, step))
                 print('Train batch loss: {}'.format(rec['loss']))   # :289
                 log.write(json.dumps(rec) + '\n')
                 log.flush()
