@@ -287,6 +287,30 @@ int scl_topn_l2_cert(const float* ref, int R, const float* query, int Q, int d, 
                      unsigned char* uncertified, double* bound_sq, void* workspace,
                      size_t workspace_bytes, int flags, void* stream);
 
+/* A prepared index over a FIXED reference set, for callers that query it many times (a localiser:
+ * frames arrive one or a few at a time).  The index block holds what scl_topn_l2_cert computes
+ * before it scans — the norm-bound word (always), refnorm[R] and, with SCL_TOPN_SCORE_BF16X3, the
+ * two bf16 planes — in caller-owned device memory of scl_topn_index_bytes (0: unsupported shape or
+ * flag; d in {32, 64, 128, 256}).  It is read-only during a query: several streams may query one
+ * index at once, each with its own workspace.  `ref` must be the rows the index was built from.
+ *
+ * scl_topn_index_query returns what scl_topn_l2_cert returns for the same operands (uncertified /
+ * bound_sq: both or neither).  More than SCL_TOPN_STREAM_MAX_Q queries run that call's scan and
+ * re-rank from the index, without its preparation.  Up to SCL_TOPN_STREAM_MAX_Q queries take the
+ * stream route: one pass over the float32 rows by every CU (scores refnorm[r] - 2 q.r on the
+ * float32 matrix cores whatever the score flag says — the certificate's float32 bound), the 32
+ * smallest (score, index) pairs per query selected from the [Q][R] score matrix in the workspace,
+ * then the same float64 re-rank and certificate. */
+#define SCL_TOPN_STREAM_MAX_Q 32
+size_t scl_topn_index_bytes(int R, int d, int flags);
+int scl_topn_index_build(const float* ref, int R, int d, void* index, size_t index_bytes, int flags,
+                         void* stream);
+size_t scl_topn_index_query_workspace_bytes(int R, int Q, int d, int n, int flags);
+int scl_topn_index_query(const float* ref, int R, int d, const void* index, size_t index_bytes,
+                         const float* query, int Q, int n, int64_t idx_offset, int64_t* idx_out,
+                         double* dist_out, unsigned char* uncertified, double* bound_sq,
+                         void* workspace, size_t workspace_bytes, int flags, void* stream);
+
 /* Exact resolution of uncertified queries: for each listed query, float64 sum (q - r)^2 against
  * EVERY reference row (d <= 256, d % 4 == 0); rows with squared distance <= bound_sq[query] are
  * appended (unordered) to that query's candidate list.  The true top-n are the n smallest

@@ -31,6 +31,7 @@ TUPLE_QUADRUPLET, TUPLE_LAZY_QUADRUPLET, TUPLE_EVIL_QUADRUPLET = 3, 4, 5
 VLAD_D, VLAD_K = 512, 64
 VLAD_SAVE_ROWS = 514      # save_vlad rows per image: U, asum, sync words of the backward pass
 TOPN_SCORE_F32, TOPN_SCORE_BF16X3 = 0, 1
+TOPN_STREAM_MAX_Q = 32     # scl_topn_index_query: at most this many queries take the stream route
 SPECTRAL_WRD, SPECTRAL_PRODWRD, SPECTRAL_SUMWRD = 0, 1, 2
 SPECTRAL_MAX_S = 32        # others (positives + negatives) per tuple of scl_spectral_loss_fwd
 EIGEN_RESIDUAL_DET, EIGEN_RESIDUAL_TRACE, EIGEN_SWRD = 0, 1, 2
@@ -92,6 +93,10 @@ SIGNATURES = {
     "scl_topn_l2_ex_workspace_bytes": (_z, [_i, _i, _i, _i, _i]),
     "scl_topn_l2_ex": (_i, [_p, _i, _p, _i, _i, _i, _l, _p, _p, _p, _z, _i, _p]),
     "scl_topn_l2_cert": (_i, [_p, _i, _p, _i, _i, _i, _l, _p, _p, _p, _p, _p, _z, _i, _p]),
+    "scl_topn_index_bytes": (_z, [_i, _i, _i]),
+    "scl_topn_index_build": (_i, [_p, _i, _i, _p, _z, _i, _p]),
+    "scl_topn_index_query_workspace_bytes": (_z, [_i, _i, _i, _i, _i]),
+    "scl_topn_index_query": (_i, [_p, _i, _i, _p, _z, _p, _i, _i, _l, _p, _p, _p, _p, _p, _z, _i, _p]),
     "scl_topn_exact_filter": (_i, [_p, _i, _p, _i, _p, _i, _p, _i, _p, _p, _p, _p]),
     "scl_topn_dots": (_i, [_p, _i, _p, _i, _i, _i, _p, _p]),
     "scl_vgg_workspace_bytes": (_z, [_i]),

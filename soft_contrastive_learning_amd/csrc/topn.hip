@@ -16,6 +16,11 @@
 //                      sum (q - r)^2, sorts by (distance, index) and emits the first n
 // The f32 pass only nominates candidates (n <= 25 of 32 kept); the emitted
 // order and distances are float64-exact.
+// A prepared index (scl_topn_index_build / scl_topn_index_query) keeps the norms, their bound and
+// the bf16 planes between calls; at most 32 queries then take
+//   topn_stream_score_kernel   one pass of every CU over the float32 rows -> scores [Q][R]
+//   topn_stream_select_kernel  the 32 smallest (score, index) pairs per (query, split)
+// in front of the same re-rank.
 #include <limits.h>
 #include <math.h>
 
@@ -835,6 +840,289 @@ __global__ __launch_bounds__(256) void topn_exact_filter_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------------------
+// The STREAM route of scl_topn_index_query: at most 32 queries against a prepared index.
+//
+// topn_stream_score_kernel: scores[q][j] = refnorm[j] - 2 q.r_j for every reference, one pass over
+// the float32 rows.  The product is skinny ([Q <= 32, d] x ref^T), so nothing is shared between
+// waves and nothing goes through LDS: a WAVE owns 32-reference tiles (tile w, w + W, w + 2 W, .. of
+// the W waves of the grid), lane (r, h) loads row r's elements 8 t + 4 h .. + 3 straight into the B
+// operands of v_mfma_f32_32x32x2_f32 and keeps the query fragment of topn_scan_kernel (BF = 0)
+// resident.  A tile's registers come in two halves; each half is refilled for the wave's next tile
+// as soon as its products are issued, so half a tile (16 KB per wave) is always in flight.
+// Arithmetic: the same instruction on the same operands as the float32 scan — a float32 chain of
+// d products per score and one subtraction from the float32 norm — so the certificate's eps_q /
+// eps_r ("f32 MFMA chain of d terms") cover it unchanged.
+// The last tile may be ragged: rows past R re-read row R - 1 and are not written.  Query rows
+// past Q are zero and not written.  No scratch, no LDS.
+template <int D8>
+__global__ __launch_bounds__(256) void topn_stream_score_kernel(const float* __restrict__ ref,
+                                                                const float* __restrict__ refnorm,
+                                                                int R, const float* __restrict__ query,
+                                                                int Q, float* __restrict__ scores) {
+  constexpr int d = D8 * 8, H = D8 / 2;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int r = lane & 31, h = lane >> 5;
+  const int ntiles = (R + 31) / 32;
+  const int nw = gridDim.x * 4;
+  int t = blockIdx.x * 4 + wid;
+  if (t >= ntiles) return;                                   // wave-uniform
+  f32x4 qf[D8];
+  {
+    const float* qp = query + (int64_t)(r < Q ? r : 0) * d + 4 * h;
+#pragma unroll
+    for (int u = 0; u < D8; ++u) {
+      qf[u] = *reinterpret_cast<const f32x4*>(qp + 8 * u);
+      if (r >= Q) qf[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+  }
+  auto row_of = [&](int tile) {
+    const int row = tile * 32 + r;
+    return ref + (int64_t)(row < R ? row : R - 1) * d + 4 * h;
+  };
+  f32x4 a[H], b[H];
+  {
+    const float* p = row_of(t);
+#pragma unroll
+    for (int u = 0; u < H; ++u) a[u] = *reinterpret_cast<const f32x4*>(p + 8 * u);
+#pragma unroll
+    for (int u = 0; u < H; ++u) b[u] = *reinterpret_cast<const f32x4*>(p + 8 * (H + u));
+  }
+  for (; t < ntiles; t += nw) {
+    const bool more = t + nw < ntiles;                       // wave-uniform
+    const float* pn = row_of(more ? t + nw : t);
+    const int ridx = t * 32 + r;
+    const float rn = refnorm[ridx < R ? ridx : R - 1];
+    f32x16 acc = zero16();
+#pragma unroll
+    for (int u = 0; u < H; ++u)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) acc = mfma32(qf[u][c], a[u][c], acc);
+    if (more) {
+#pragma unroll
+      for (int u = 0; u < H; ++u) a[u] = *reinterpret_cast<const f32x4*>(pn + 8 * u);
+    }
+#pragma unroll
+    for (int u = 0; u < H; ++u)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) acc = mfma32(qf[H + u][c], b[u][c], acc);
+    if (more) {
+#pragma unroll
+      for (int u = 0; u < H; ++u) b[u] = *reinterpret_cast<const f32x4*>(pn + 8 * (H + u));
+    }
+    if (ridx < R) {
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        const int row = acc_row(q, h);
+        if (row < Q) scores[(int64_t)row * R + ridx] = rn - 2.0f * acc[q];
+      }
+    }
+  }
+}
+
+// order-preserving image of a float32 score in the unsigned integers, and back
+__device__ __forceinline__ unsigned score_key(float v) {
+  const unsigned bits = __float_as_uint(v);
+  return bits ^ ((bits >> 31) ? 0xffffffffu : 0x80000000u);
+}
+__device__ __forceinline__ float key_score(unsigned key) {
+  return __uint_as_float((key & 0x80000000u) ? (key ^ 0x80000000u) : ~key);
+}
+
+// topn_stream_select_kernel: one WAVE per (query, split of the reference axis) picks the KEEP
+// smallest (score, index) pairs of its contiguous split of the score matrix and writes them as one
+// list of the re-rank's [Q][splits][KEEP] input (-1 = empty slot).  grid (ceil(S / 4), Q), block 256.
+// The wave walks its split 64 * kSelNE scores at a time; the best KEEP so far ride along as one
+// more slot (lanes 0 .. 31).  Per step: a pre-filter that leaves a few dozen of the step's scores
+// (stream_select_step), radix select of the KEEP-th smallest key (32 bit-steps of per-lane
+// counts and ballots — no cross-lane shuffles), then compaction through 32 LDS
+// slots: first what lies strictly below the threshold, then the ties at it, both in the order
+// (carried entries, then ascending reference index).  By induction entries of equal score stay in
+// ascending index order, so ties at the threshold go to the lower index, and a full list's last
+// entry is its largest score (what topn_rerank_kernel takes as the split's exclusion threshold).
+constexpr int kSelNE = 16;
+
+constexpr int kSelBuf = 96;       // survivors of a step's pre-filter that the short selection takes
+
+// The kth smallest of NS * 64 keys (a slot per register; all ones = empty): 32 bit-steps.  The
+// counts of a bit-step are kept per lane (pure vector work) and summed over the wave bit-sliced:
+// a lane's count is at most NS < 32, five ballots + population counts give the sum.  Fewer than
+// kth non-empty keys: all ones.
+template <int NS>
+__device__ __forceinline__ unsigned radix_kth(const unsigned (&key)[NS], int kth) {
+  unsigned prefix = 0;
+  int need = kth;
+  for (int bit = 31; bit >= 0; --bit) {
+    // keys that agree with the prefix above `bit` and have a 0 there
+    unsigned c = 0;
+#pragma unroll
+    for (int k = 0; k < NS; ++k) c += (((key[k] ^ prefix) >> bit) == 0u) ? 1u : 0u;
+    int c0 = 0;
+#pragma unroll
+    for (int b = 0; b < 5; ++b)
+      if ((NS >> b) != 0) c0 += __popcll(__ballot((c >> b) & 1u)) << b;
+    if (need > c0) {
+      need -= c0;
+      prefix |= 1u << bit;
+    }
+  }
+  return prefix;
+}
+
+// The KEEP smallest (key, position) pairs of NS slots (position = slot-major, then lane; idx < 0 =
+// empty) become the wave's carried list: what lies strictly below the KEEP-th smallest key first,
+// then the ties at it, both in position order, through lk / li[KEEP].
+template <int NS>
+__device__ __forceinline__ void select_finish(const unsigned (&key)[NS], const int (&idx)[NS], int lane,
+                                              unsigned* lk, int* li, unsigned& ck, int& ci) {
+  const unsigned long long lt = (1ull << lane) - 1ull;
+  int nvalid = 0;
+#pragma unroll
+  for (int k = 0; k < NS; ++k) nvalid += __popcll(__ballot(idx[k] >= 0));
+  // at most KEEP entries: all of them win
+  const unsigned tau_key = nvalid > KEEP ? radix_kth<NS>(key, KEEP) : 0xffffffffu;
+  if (lane < KEEP) {
+    lk[lane] = 0xffffffffu;
+    li[lane] = -1;
+  }
+  __builtin_amdgcn_wave_barrier();
+  int filled = 0;
+#pragma unroll
+  for (int k = 0; k < NS; ++k) {                             // strictly below the threshold
+    const bool sel = idx[k] >= 0 && key[k] < tau_key;
+    const unsigned long long m = __ballot(sel);
+    if (m) {                                                 // (wave-uniform)
+      const int pos = filled + __popcll(m & lt);
+      if (sel && pos < KEEP) {                               // (fewer than KEEP lie below the KEEP-th)
+        lk[pos] = key[k];
+        li[pos] = idx[k];
+      }
+      filled += __popcll(m);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < NS; ++k) {                             // ties at the threshold fill the rest
+    const bool sel = idx[k] >= 0 && key[k] == tau_key;
+    const unsigned long long m = __ballot(sel);
+    if (m) {
+      const int pos = filled + __popcll(m & lt);
+      if (sel && pos < KEEP) {
+        lk[pos] = key[k];
+        li[pos] = idx[k];
+      }
+      filled += __popcll(m);
+    }
+  }
+  __builtin_amdgcn_wave_barrier();
+  if (lane < KEEP) {
+    ck = lk[lane];
+    ci = li[lane];
+  }
+  __builtin_amdgcn_wave_barrier();
+}
+
+// One step of the selection wave over NE * 64 scores from `base` (NE = 16 for whole steps; the
+// ragged last step of a split takes the smallest of 1, 2, 4, 8, 16 that covers it).
+template <int NE>
+__device__ __forceinline__ void stream_select_step(const float* __restrict__ sc, int base, int end,
+                                                   int lane, unsigned* lk, int* li, unsigned& ck,
+                                                   int& ci) {
+  unsigned key[NE + 1];
+  int idx[NE + 1];
+  key[0] = ck;
+  idx[0] = ci;
+#pragma unroll
+  for (int k = 0; k < NE; ++k) {
+    const int e = base + k * 64 + lane;
+    const bool ok = e < end;
+    const float v = ok ? sc[e] : 0.f;
+    key[k + 1] = ok ? score_key(v) : 0xffffffffu;
+    idx[k + 1] = ok ? e : -1;
+  }
+  if constexpr (NE >= 4) {
+    // Pre-filter.  tub = the KEEP-th smallest of the 64 lanes' minima (every lane holds NE >= 4
+    // scores here): at least KEEP NEW scores are <= tub, so the KEEP-th smallest of (carried + new)
+    // is too, and every new entry of the next list is among the survivors "key <= tub" — about
+    // 2 KEEP of the 64 NE.  At most kSelBuf survivors: they go through LDS, in index order, behind
+    // the carried list into TWO slots and the selection runs on those; more (many equal scores):
+    // the selection runs on all NE + 1 slots.
+    unsigned mn[1] = {key[1]};
+#pragma unroll
+    for (int k = 2; k <= NE; ++k) mn[0] = key[k] < mn[0] ? key[k] : mn[0];
+    const unsigned tub = radix_kth<1>(mn, KEEP);
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    int ns = 0;
+#pragma unroll
+    for (int k = 1; k <= NE; ++k) ns += __popcll(__ballot(idx[k] >= 0 && key[k] <= tub));
+    if (ns <= kSelBuf) {                                     // (wave-uniform)
+      int filled = 0;
+#pragma unroll
+      for (int k = 1; k <= NE; ++k) {
+        const bool sel = idx[k] >= 0 && key[k] <= tub;
+        const unsigned long long m = __ballot(sel);
+        if (m) {
+          if (sel) {
+            const int pos = filled + __popcll(m & lt);       // < ns <= kSelBuf
+            lk[pos] = key[k];
+            li[pos] = idx[k];
+          }
+          filled += __popcll(m);
+        }
+      }
+      __builtin_amdgcn_wave_barrier();
+      // slot 0: the carried list (lanes 0 .. 31) and survivors 0 .. 31; slot 1: survivors 32 .. 95
+      unsigned k2[2];
+      int i2[2];
+      const int p0 = lane - KEEP, p1 = lane + KEEP;
+      const bool v0 = lane >= KEEP && p0 < ns, v1 = p1 < ns;
+      k2[0] = lane < KEEP ? ck : (v0 ? lk[v0 ? p0 : 0] : 0xffffffffu);
+      i2[0] = lane < KEEP ? ci : (v0 ? li[v0 ? p0 : 0] : -1);
+      k2[1] = v1 ? lk[v1 ? p1 : 0] : 0xffffffffu;
+      i2[1] = v1 ? li[v1 ? p1 : 0] : -1;
+      __builtin_amdgcn_wave_barrier();
+      select_finish<2>(k2, i2, lane, lk, li, ck, ci);
+      return;
+    }
+  }
+  select_finish<NE + 1>(key, idx, lane, lk, li, ck, ci);
+}
+
+__global__ __launch_bounds__(256) void topn_stream_select_kernel(const float* __restrict__ scores,
+                                                                 int R, int S, int per,
+                                                                 float* __restrict__ cand_sc,
+                                                                 int* __restrict__ cand_ix) {
+  __shared__ unsigned lkey[4][kSelBuf];
+  __shared__ int lidx[4][kSelBuf];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int s = blockIdx.x * 4 + wid, qi = blockIdx.y;
+  if (s >= S) return;                                        // wave-uniform; no block barriers below
+  const float* sc = scores + (int64_t)qi * R;
+  const int begin = s * per;
+  const int end = begin + per < R ? begin + per : R;
+  unsigned ck = 0xffffffffu;                                 // carried entry of lanes 0 .. KEEP - 1
+  int ci = -1;
+  for (int base = begin; base < end; base += 64 * kSelNE) {
+    const int rem = end - base;                              // wave-uniform
+#define SCL_SEL_STEP(NE) stream_select_step<NE>(sc, base, end, lane, lkey[wid], lidx[wid], ck, ci)
+    if (rem > 512)
+      SCL_SEL_STEP(16);
+    else if (rem > 256)
+      SCL_SEL_STEP(8);
+    else if (rem > 128)
+      SCL_SEL_STEP(4);
+    else if (rem > 64)
+      SCL_SEL_STEP(2);
+    else
+      SCL_SEL_STEP(1);
+#undef SCL_SEL_STEP
+  }
+  if (lane < KEEP) {
+    const int64_t o = ((int64_t)qi * S + s) * KEEP + lane;
+    cand_sc[o] = ci >= 0 ? key_score(ck) : INFINITY;
+    cand_ix[o] = ci;
+  }
+}
+
 struct TopnPlan {
   int qtiles, splits, refs_per_split;
 };
@@ -982,14 +1270,53 @@ inline bool topn_shape_ok(int R, int Q, int d, int n) {
   return R >= 1 && Q >= 1 && d_ok && n >= 1 && n <= kMaxN && n <= R;
 }
 
-}  // namespace
+// |approximate - exact score| <= eps_q |q| Rmax + eps_r Rmax^2 (u = 2^-24; factor 2 of
+// safety on rigorous worst-case bounds):
+//   ||r||^2 by f32 FMAs + the final f32 subtraction        (d + 16) u (Rmax^2 + 2 |q| Rmax)
+//   -2 q.r, f32 MFMA chain of d terms                       2 d u |q| Rmax
+//   -2 q.r, bf16x3: dropped q_lo.r_lo + split residues      2 * 3 * 2^-18 |q| Rmax
+//                   + f32 accumulation of 3 d products      2 * 3 d u |q| Rmax
+struct TopnEps {
+  float q, r;
+};
+inline TopnEps topn_eps(int d, int bf) {
+  const double u = 5.9604644775390625e-8;
+  const double eps_r = 2.0 * (d + 16) * u;
+  const double eps_q = 2.0 * (2.0 * (d + 16) * u +
+                              (bf ? 6.0 / 262144.0 + 6.0 * d * u : 2.0 * d * u));
+  return TopnEps{(float)eps_q, (float)eps_r};
+}
 
-extern "C" size_t scl_topn_l2_ex_workspace_bytes(int R, int Q, int d, int n, int flags) {
-  if (!topn_shape_ok(R, Q, d, n) || (flags & ~SCL_TOPN_SCORE_BF16X3)) return 0;
-  const int bf = flags & SCL_TOPN_SCORE_BF16X3;
+inline size_t rerank_lds_bytes(int M) { return (size_t)4 * (2 * M + 3 * KEEP + 4 + 66) * sizeof(float); }
+
+// the re-rank over sorted-or-not lists [Q][splits][KEEP] (-1 = empty slot), splits <= 32
+void launch_rerank(const float* ref, const float* query, int Q, int d, int splits, int n,
+                   int64_t idx_offset, const float* cs, const int* ci, int64_t* idx_out, double* dist_out,
+                   const unsigned* rmax_bits, TopnEps eps, unsigned char* uncertified, double* bound_sq,
+                   hipStream_t st) {
+  const int M = splits * KEEP;
+  const size_t lds = rerank_lds_bytes(M);
+  const dim3 rgrid((Q + 3) / 4);
+#define SCL_RERANK(NE)                                                                           \
+  SCL_LAUNCH("topn_rerank_kernel", topn_rerank_kernel<NE>, rgrid, dim3(256), lds, st, ref, query, \
+             Q, d, splits, n, idx_offset, cs, ci, idx_out, dist_out, rmax_bits, eps.q, eps.r,     \
+             uncertified, bound_sq)
+  if (M <= 256)
+    SCL_RERANK(4);
+  else if (M <= 512)
+    SCL_RERANK(8);
+  else
+    SCL_RERANK(16);
+#undef SCL_RERANK
+}
+
+
+// Bytes of the candidate lists behind the norms: the sorted-list scan's [Q][splits][KEEP] x 2, or
+// the threshold scheme's buffers where R allows it (whichever is larger serves both).
+inline size_t topn_lists_bytes(int R, int Q, int bf) {
   const TopnPlan p = topn_plan(R, Q, bf);
   size_t lists = 2 * scl_round256((size_t)Q * p.splits * KEEP * sizeof(float));
-  if (R >= kTauMinRefs) {             // the threshold scheme's buffers (whichever is larger serves both)
+  if (R >= kTauMinRefs) {
     const TauPlan t = tau_plan(R, Q);
     const size_t tau_bytes = scl_round256((size_t)Q * t.pre_splits * 64 * sizeof(float)) +
                              2 * scl_round256((size_t)Q * t.main_splits * kTauCapSplit * sizeof(float)) +
@@ -997,38 +1324,26 @@ extern "C" size_t scl_topn_l2_ex_workspace_bytes(int R, int Q, int d, int n, int
                              scl_round256((size_t)Q * t.main_splits * sizeof(int));
     if (tau_bytes > lists) lists = tau_bytes;
   }
-  return 256 + scl_round256((size_t)R * sizeof(float)) + lists +
-         (bf ? 2 * scl_round256((size_t)R * d * sizeof(unsigned short)) : 0);
+  return lists;
+}
+inline size_t topn_planes_bytes(int R, int d, int bf) {
+  return bf ? 2 * scl_round256((size_t)R * d * sizeof(unsigned short)) : 0;
 }
 
-extern "C" size_t scl_topn_l2_workspace_bytes(int R, int Q, int d, int n) {
-  return scl_topn_l2_ex_workspace_bytes(R, Q, d, n, 0);
-}
-
-extern "C" int scl_topn_l2_cert(const float* ref, int R, const float* query, int Q, int d, int n,
-                                int64_t idx_offset, int64_t* idx_out, double* dist_out,
-                                unsigned char* uncertified, double* bound_sq, void* workspace,
-                                size_t workspace_bytes, int flags, void* stream) {
-  if (!ref || !query || !idx_out || !dist_out || !workspace) return SCL_E_NULL;
-  if ((uncertified == nullptr) != (bound_sq == nullptr)) return SCL_E_NULL;
-  if (!topn_shape_ok(R, Q, d, n)) return SCL_E_SHAPE;
-  if (flags & ~SCL_TOPN_SCORE_BF16X3) return SCL_E_KIND;
-  if (((uintptr_t)ref % 16) || ((uintptr_t)query % 16)) return SCL_E_SHAPE;
-  if (!scl_aligned256(workspace) ||
-      workspace_bytes < scl_topn_l2_ex_workspace_bytes(R, Q, d, n, flags))
-    return SCL_E_WORKSPACE;
-  const int bf = flags & SCL_TOPN_SCORE_BF16X3;
+// What follows the preparation (norms, norm bound, bf16 planes) in scl_topn_l2_cert and in the
+// scan route of scl_topn_index_query: scan (or pre-pass, thresholds, threshold scan) into the
+// candidate lists at `lists` (topn_lists_bytes), then the float64 re-rank with the certificate.
+int topn_scan_rerank(const float* ref, int R, const float* query, int Q, int d, int n,
+                     int64_t idx_offset, int64_t* idx_out, double* dist_out,
+                     unsigned char* uncertified, double* bound_sq, const unsigned* rmax_bits,
+                     const float* refnorm, const void* scan_ref, const void* scan_lo, char* lists,
+                     int bf, hipStream_t st) {
   const TopnPlan p = topn_plan(R, Q, bf);
-  char* base = (char*)workspace;
-  unsigned* rmax_bits = (unsigned*)base;
-  base += 256;
-  float* refnorm = (float*)base;
-  base += scl_round256((size_t)R * sizeof(float));
-  hipStream_t st = (hipStream_t)stream;
   const bool tau_mode = use_tau(R, uncertified != nullptr, bf);
   const TauPlan tp = tau_mode ? tau_plan(R, Q) : TauPlan{};
   // sorted-list scan: cs / ci [Q][splits][KEEP].  threshold scheme: pre-pass values [Q][S'][64],
   // candidate regions [Q][S][kTauCapSplit] x 2, tau [Q], counts [Q][S]
+  char* base = lists;
   float *cs, *pre = nullptr, *tau = nullptr;
   int *ci, *cnt = nullptr;
   if (tau_mode) {
@@ -1048,13 +1363,93 @@ extern "C" int scl_topn_l2_cert(const float* ref, int R, const float* query, int
     ci = (int*)base;
     base += scl_round256((size_t)Q * p.splits * KEEP * sizeof(float));
   }
-  // (the bf16 planes lie behind whichever of the two layouts is larger)
-  {
-    const size_t used = (size_t)(base - (char*)workspace);
-    const size_t planes = bf ? 2 * scl_round256((size_t)R * d * sizeof(unsigned short)) : 0;
-    base = (char*)workspace + (scl_topn_l2_ex_workspace_bytes(R, Q, d, n, flags) - planes);
-    if ((size_t)(base - (char*)workspace) < used) return SCL_E_WORKSPACE;
+  if ((size_t)(base - lists) > topn_lists_bytes(R, Q, bf)) return SCL_E_WORKSPACE;
+  if (tau_mode) {
+    // pre-pass over every kTauStride-th tile (interleaved splits) -> tau_q -> threshold scan
+    TopnPlan pp;
+    pp.qtiles = tp.qtiles;
+    pp.refs_per_split = 0;                                   // interleaved
+    pp.splits = tp.pre_splits;
+    launch_scan_d<2>(d, bf, pp, scan_ref, scan_lo, refnorm, R, query, Q, pre, (int*)nullptr, st,
+                     tau_stride() * tp.pre_splits, nullptr, nullptr, 0, tau_stride());
+    SCL_LAUNCH("topn_tau_kernel", topn_tau_kernel, dim3((Q + 3) / 4), dim3(256), 0, st, (const float*)pre, Q,
+               tp.pre_splits, tau);
+    pp.splits = tp.main_splits;
+    launch_scan_d<1>(d, bf, pp, scan_ref, scan_lo, refnorm, R, query, Q, cs, ci, st, tp.main_splits, tau, cnt,
+                     kTauCapSplit, 1);
+  } else {
+    launch_scan_d<0>(d, bf, p, scan_ref, scan_lo, refnorm, R, query, Q, cs, ci, st);
   }
+  const TopnEps eps = topn_eps(d, bf);
+  const int M = tau_mode ? kTauCompact : p.splits * KEEP;
+  if (tau_mode) {
+    static SclDeviceOnce once;
+    scl_call_once(once, [] {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&topn_rerank_kernel<kTauCompact / 64, true>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
+    });
+    SCL_LAUNCH("topn_rerank_kernel<append>", (topn_rerank_kernel<kTauCompact / 64, true>), dim3((Q + 3) / 4),
+               dim3(256), rerank_lds_bytes(M), st, ref,
+               query, Q, d, tp.main_splits, n, idx_offset, (const float*)cs, (const int*)ci, idx_out, dist_out,
+               rmax_bits, eps.q, eps.r, uncertified, bound_sq,
+               (const int*)cnt, (const float*)tau, kTauCapSplit);
+    return scl_launch_status();
+  }
+  launch_rerank(ref, query, Q, d, p.splits, n, idx_offset, cs, ci, idx_out, dist_out, rmax_bits, eps,
+                uncertified, bound_sq, st);
+  return scl_launch_status();
+}
+
+// The stream route's split of the reference axis: at most 32 lists per query (the re-rank keeps
+// 32 * KEEP candidates per query in LDS), each over at least one step of the selection wave.
+struct StreamPlan {
+  int splits, per;
+};
+inline StreamPlan stream_plan(int R) {
+  StreamPlan p;
+  int s = (R + 64 * kSelNE - 1) / (64 * kSelNE);
+  if (s > 32) s = 32;
+  p.per = (R + s - 1) / s;
+  p.splits = (R + p.per - 1) / p.per;
+  return p;
+}
+inline bool topn_flags_ok(int flags) { return !(flags & ~SCL_TOPN_SCORE_BF16X3); }
+
+}  // namespace
+
+extern "C" size_t scl_topn_l2_ex_workspace_bytes(int R, int Q, int d, int n, int flags) {
+  if (!topn_shape_ok(R, Q, d, n) || (flags & ~SCL_TOPN_SCORE_BF16X3)) return 0;
+  const int bf = flags & SCL_TOPN_SCORE_BF16X3;
+  return 256 + scl_round256((size_t)R * sizeof(float)) + topn_lists_bytes(R, Q, bf) +
+         topn_planes_bytes(R, d, bf);
+}
+
+extern "C" size_t scl_topn_l2_workspace_bytes(int R, int Q, int d, int n) {
+  return scl_topn_l2_ex_workspace_bytes(R, Q, d, n, 0);
+}
+
+extern "C" int scl_topn_l2_cert(const float* ref, int R, const float* query, int Q, int d, int n,
+                                int64_t idx_offset, int64_t* idx_out, double* dist_out,
+                                unsigned char* uncertified, double* bound_sq, void* workspace,
+                                size_t workspace_bytes, int flags, void* stream) {
+  if (!ref || !query || !idx_out || !dist_out || !workspace) return SCL_E_NULL;
+  if ((uncertified == nullptr) != (bound_sq == nullptr)) return SCL_E_NULL;
+  if (!topn_shape_ok(R, Q, d, n)) return SCL_E_SHAPE;
+  if (flags & ~SCL_TOPN_SCORE_BF16X3) return SCL_E_KIND;
+  if (((uintptr_t)ref % 16) || ((uintptr_t)query % 16)) return SCL_E_SHAPE;
+  if (!scl_aligned256(workspace) ||
+      workspace_bytes < scl_topn_l2_ex_workspace_bytes(R, Q, d, n, flags))
+    return SCL_E_WORKSPACE;
+  const int bf = flags & SCL_TOPN_SCORE_BF16X3;
+  // workspace: norm-bound word | refnorm[R] | candidate lists | (bf16x3) the two planes
+  char* base = (char*)workspace;
+  unsigned* rmax_bits = (unsigned*)base;
+  base += 256;
+  float* refnorm = (float*)base;
+  base += scl_round256((size_t)R * sizeof(float));
+  char* lists = base;
+  base += topn_lists_bytes(R, Q, bf);
+  hipStream_t st = (hipStream_t)stream;
   if (uncertified) {
     const hipError_t e = hipMemsetAsync(rmax_bits, 0, 16, st);
     if (e != hipSuccess) return (int)e;
@@ -1073,59 +1468,8 @@ extern "C" int scl_topn_l2_cert(const float* ref, int R, const float* query, int
     scan_ref = hi;
     scan_lo = lo;
   }
-  if (tau_mode) {
-    // pre-pass over every kTauStride-th tile (interleaved splits) -> tau_q -> threshold scan
-    TopnPlan pp;
-    pp.qtiles = tp.qtiles;
-    pp.refs_per_split = 0;                                   // interleaved
-    pp.splits = tp.pre_splits;
-    launch_scan_d<2>(d, bf, pp, scan_ref, scan_lo, refnorm, R, query, Q, pre, (int*)nullptr, st,
-                     tau_stride() * tp.pre_splits, nullptr, nullptr, 0, tau_stride());
-    SCL_LAUNCH("topn_tau_kernel", topn_tau_kernel, dim3((Q + 3) / 4), dim3(256), 0, st, (const float*)pre, Q,
-               tp.pre_splits, tau);
-    pp.splits = tp.main_splits;
-    launch_scan_d<1>(d, bf, pp, scan_ref, scan_lo, refnorm, R, query, Q, cs, ci, st, tp.main_splits, tau, cnt,
-                     kTauCapSplit, 1);
-  } else {
-    launch_scan_d<0>(d, bf, p, scan_ref, scan_lo, refnorm, R, query, Q, cs, ci, st);
-  }
-  // |approximate - exact score| <= eps_q |q| Rmax + eps_r Rmax^2 (u = 2^-24; factor 2 of
-  // safety on rigorous worst-case bounds):
-  //   ||r||^2 by f32 FMAs + the final f32 subtraction        (d + 16) u (Rmax^2 + 2 |q| Rmax)
-  //   -2 q.r, f32 MFMA chain of d terms                       2 d u |q| Rmax
-  //   -2 q.r, bf16x3: dropped q_lo.r_lo + split residues      2 * 3 * 2^-18 |q| Rmax
-  //                   + f32 accumulation of 3 d products      2 * 3 d u |q| Rmax
-  const double u = 5.9604644775390625e-8;
-  const double eps_r = 2.0 * (d + 16) * u;
-  const double eps_q = 2.0 * (2.0 * (d + 16) * u +
-                              (bf ? 6.0 / 262144.0 + 6.0 * d * u : 2.0 * d * u));
-  const int M = tau_mode ? kTauCompact : p.splits * KEEP;
-  const size_t lds = (size_t)4 * (2 * M + 3 * KEEP + 4 + 66) * sizeof(float);
-  const dim3 rgrid((Q + 3) / 4);
-  if (tau_mode) {
-    static SclDeviceOnce once;
-    scl_call_once(once, [] {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&topn_rerank_kernel<kTauCompact / 64, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-    });
-    SCL_LAUNCH("topn_rerank_kernel<append>", (topn_rerank_kernel<kTauCompact / 64, true>), rgrid, dim3(256), lds, st, ref,
-               query, Q, d, tp.main_splits, n, idx_offset, (const float*)cs, (const int*)ci, idx_out, dist_out,
-               (const unsigned*)rmax_bits, (float)eps_q, (float)eps_r, uncertified, bound_sq,
-               (const int*)cnt, (const float*)tau, kTauCapSplit);
-    return scl_launch_status();
-  }
-#define SCL_RERANK(NE)                                                                           \
-  SCL_LAUNCH("topn_rerank_kernel", topn_rerank_kernel<NE>, rgrid, dim3(256), lds, st, ref, query, \
-             Q, d, p.splits, n, idx_offset, (const float*)cs, (const int*)ci, idx_out, dist_out,  \
-             (const unsigned*)rmax_bits, (float)eps_q, (float)eps_r, uncertified, bound_sq)
-  if (M <= 256)
-    SCL_RERANK(4);
-  else if (M <= 512)
-    SCL_RERANK(8);
-  else
-    SCL_RERANK(16);
-#undef SCL_RERANK
-  return scl_launch_status();
+  return topn_scan_rerank(ref, R, query, Q, d, n, idx_offset, idx_out, dist_out, uncertified, bound_sq,
+                          rmax_bits, refnorm, scan_ref, scan_lo, lists, bf, st);
 }
 
 extern "C" int scl_topn_l2_ex(const float* ref, int R, const float* query, int Q, int d, int n,
@@ -1140,6 +1484,103 @@ extern "C" int scl_topn_l2(const float* ref, int R, const float* query, int Q, i
                            size_t workspace_bytes, void* stream) {
   return scl_topn_l2_ex(ref, R, query, Q, d, n, idx_offset, idx_out, dist_out, workspace,
                         workspace_bytes, 0, stream);
+}
+
+// ---- the prepared index: what scl_topn_l2_cert computes before it scans, kept between calls ----
+// index block: norm-bound word (256 bytes) | refnorm[R] | (bf16x3) high plane | low plane
+extern "C" size_t scl_topn_index_bytes(int R, int d, int flags) {
+  if (!topn_shape_ok(R, 1, d, 1) || !topn_flags_ok(flags)) return 0;
+  return 256 + scl_round256((size_t)R * sizeof(float)) +
+         topn_planes_bytes(R, d, flags & SCL_TOPN_SCORE_BF16X3);
+}
+
+extern "C" int scl_topn_index_build(const float* ref, int R, int d, void* index, size_t index_bytes,
+                                    int flags, void* stream) {
+  if (!ref || !index) return SCL_E_NULL;
+  if (!topn_shape_ok(R, 1, d, 1) || ((uintptr_t)ref % 16)) return SCL_E_SHAPE;
+  const int bf = flags & SCL_TOPN_SCORE_BF16X3;
+  if (!scl_aligned256(index) || index_bytes < scl_topn_index_bytes(R, d, bf)) return SCL_E_WORKSPACE;
+  if (!topn_flags_ok(flags)) return SCL_E_KIND;
+  hipStream_t st = (hipStream_t)stream;
+  unsigned* rmax_bits = (unsigned*)index;
+  float* refnorm = (float*)((char*)index + 256);
+  const hipError_t e = hipMemsetAsync(rmax_bits, 0, 16, st);
+  if (e != hipSuccess) return (int)e;
+  SCL_LAUNCH("refnorm_kernel", refnorm_kernel, dim3((R + 63) / 64), dim3(256), 0, st, ref, R, d,
+             refnorm, rmax_bits);
+  if (bf) {
+    u32x4* hi = (u32x4*)((char*)refnorm + scl_round256((size_t)R * sizeof(float)));
+    u32x4* lo = (u32x4*)((char*)hi + scl_round256((size_t)R * d * sizeof(unsigned short)));
+    const int64_t n8 = (int64_t)R * d / 8;
+    SCL_LAUNCH("ref_split_kernel", ref_split_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256),
+               0, st, ref, n8, hi, lo);
+  }
+  return scl_launch_status();
+}
+
+// Q <= SCL_TOPN_STREAM_MAX_Q: score matrix [Q][R] | lists [Q][S][KEEP] x 2.  More queries: the
+// candidate lists of the scan (topn_lists_bytes) — norms and planes come from the index.
+extern "C" size_t scl_topn_index_query_workspace_bytes(int R, int Q, int d, int n, int flags) {
+  if (!topn_shape_ok(R, Q, d, n) || !topn_flags_ok(flags)) return 0;
+  if (Q > SCL_TOPN_STREAM_MAX_Q) return topn_lists_bytes(R, Q, flags & SCL_TOPN_SCORE_BF16X3);
+  const StreamPlan sp = stream_plan(R);
+  return scl_round256((size_t)Q * R * sizeof(float)) +
+         2 * scl_round256((size_t)Q * sp.splits * KEEP * sizeof(float));
+}
+
+extern "C" int scl_topn_index_query(const float* ref, int R, int d, const void* index,
+                                    size_t index_bytes, const float* query, int Q, int n,
+                                    int64_t idx_offset, int64_t* idx_out, double* dist_out,
+                                    unsigned char* uncertified, double* bound_sq, void* workspace,
+                                    size_t workspace_bytes, int flags, void* stream) {
+  if (!ref || !index || !query || !idx_out || !dist_out || !workspace) return SCL_E_NULL;
+  if ((uncertified == nullptr) != (bound_sq == nullptr)) return SCL_E_NULL;
+  if (!topn_shape_ok(R, Q, d, n)) return SCL_E_SHAPE;
+  if (((uintptr_t)ref % 16) || ((uintptr_t)query % 16)) return SCL_E_SHAPE;
+  const int bf = flags & SCL_TOPN_SCORE_BF16X3;
+  if (!scl_aligned256(index) || index_bytes < scl_topn_index_bytes(R, d, bf)) return SCL_E_WORKSPACE;
+  if (!scl_aligned256(workspace) ||
+      workspace_bytes < scl_topn_index_query_workspace_bytes(R, Q, d, n, bf))
+    return SCL_E_WORKSPACE;
+  if (!topn_flags_ok(flags)) return SCL_E_KIND;
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned* rmax_bits = (const unsigned*)index;
+  const float* refnorm = (const float*)((const char*)index + 256);
+  if (Q > SCL_TOPN_STREAM_MAX_Q) {
+    const void* scan_ref = ref;
+    const void* scan_lo = nullptr;
+    if (bf) {
+      scan_ref = (const char*)refnorm + scl_round256((size_t)R * sizeof(float));
+      scan_lo = (const char*)scan_ref + scl_round256((size_t)R * d * sizeof(unsigned short));
+    }
+    return topn_scan_rerank(ref, R, query, Q, d, n, idx_offset, idx_out, dist_out, uncertified,
+                            bound_sq, rmax_bits, refnorm, scan_ref, scan_lo, (char*)workspace, bf, st);
+  }
+  // stream route: always scores from the float32 rows (the score flag only sizes the index)
+  const StreamPlan sp = stream_plan(R);
+  float* scores = (float*)workspace;
+  float* cs = (float*)((char*)workspace + scl_round256((size_t)Q * R * sizeof(float)));
+  int* ci = (int*)((char*)cs + scl_round256((size_t)Q * sp.splits * KEEP * sizeof(float)));
+  // one wave per 32-reference tile until the chip is full: 4 waves per CU at d = 256 (a wave holds
+  // the query fragment and a tile: 332 registers), 8 at d = 128 (204), 12 at d = 64 (140), 16 at 32
+  const int ntiles = (R + 31) / 32;
+  const int max_wg = d == 256 ? 256 : (d == 128 ? 512 : (d == 64 ? 768 : 1024));
+  const int wgs = (ntiles + 3) / 4 < max_wg ? (ntiles + 3) / 4 : max_wg;
+#define SCL_STREAM(D8)                                                                              \
+  SCL_LAUNCH("topn_stream_score_kernel", topn_stream_score_kernel<D8>, dim3(wgs), dim3(256), 0, st, \
+             ref, refnorm, R, query, Q, scores)
+  switch (d) {
+    case 32: SCL_STREAM(4); break;
+    case 64: SCL_STREAM(8); break;
+    case 128: SCL_STREAM(16); break;
+    default: SCL_STREAM(32); break;
+  }
+#undef SCL_STREAM
+  SCL_LAUNCH("topn_stream_select_kernel", topn_stream_select_kernel, dim3((sp.splits + 3) / 4, Q),
+             dim3(256), 0, st, (const float*)scores, R, sp.splits, sp.per, cs, ci);
+  launch_rerank(ref, query, Q, d, sp.splits, n, idx_offset, cs, ci, idx_out, dist_out, rmax_bits,
+                topn_eps(d, 0), uncertified, bound_sq, st);
+  return scl_launch_status();
 }
 
 extern "C" int scl_topn_exact_filter(const float* ref, int R, const float* query, int d,

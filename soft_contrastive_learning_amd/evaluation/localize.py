@@ -1,0 +1,190 @@
+"""Frame in, position out: localisation of single frames against a resident reference index.
+
+``evaluation/top_n.py`` answers whole query sets in one call, like the reference's
+``evaluation/top-n.py``.  A trained localiser is used the other way round: the reference database
+is fixed, frames arrive one or a few at a time, and each wants its position.  ``Localizer`` thins
+the references (``top_n.thin_reference``, evaluation/top-n.py:91-94), whitens them row by row
+(``PCAWhitening.transform_rows``: a frame's bits do not depend on its batch), prepares them once
+(``retrieval.RetrievalIndex``) and then answers every call with one streaming pass of
+csrc/topn.hip over the index.  The lists are the certified exact ones of ``retrieval.topn_l2``.
+
+The command feeds a query set through a ``Localizer`` ``--batch`` frames at a time and writes the
+pickle ``top_n.main`` writes (evaluation/top-n.py:119), so the two can be compared file by file.
+"""
+import numpy as np
+import torch
+
+from . import retrieval
+from .top_n import out_pickle_path, thin_reference
+
+
+class Localizer:
+    """``Localizer(ref_desc, ref_xy, pca=None, model=None, n=5, l=0.0, score='f32', device='cuda')``
+
+    ref_desc [M, E] descriptors of the reference frames (``evaluation/inference.py``'s pickle),
+    ref_xy [M, 2] their positions, ``pca`` a fitted ``PCAWhitening`` (None: the descriptors are
+    used as they are), ``model`` the network of ``locate`` (None: ``nets.default_model()``), ``n``
+    hits per frame, ``l`` the thinning distance in metres.
+
+    ``query_fn(ref_f, query_f, n) -> (dist [Q,n], idx [Q,n])`` on NumPy arrays replaces the index
+    in the CPU tests of the bookkeeping around it; the product path has no such argument and no
+    CPU fallback."""
+
+    def __init__(self, ref_desc, ref_xy, pca=None, model=None, n=5, l=0.0, score='f32', device='cuda',
+                 query_fn=None):
+        self.ref_xy = np.asarray(ref_xy, dtype=np.float64)
+        self.ref_idx = thin_reference(self.ref_xy, l)
+        self.n = int(n)
+        if len(self.ref_idx) < self.n:
+            raise ValueError('%d references survive the thinning at l=%g, fewer than n=%d'
+                             % (len(self.ref_idx), l, self.n))
+        self._orig = np.asarray(self.ref_idx, dtype=np.int64)       # thinned row -> original index
+        self.pca = pca
+        self.model = model
+        self._query_fn = query_fn
+        self.uncertified = 0                                          # over all calls so far
+        rows = np.asarray(ref_desc, dtype=np.float32)[self._orig]
+        if query_fn is not None:
+            self.device = None
+            self._ref_f = self._whiten(rows)
+            self._index = None
+            return
+        self.device = torch.device(device)
+        self._index = retrieval.RetrievalIndex(self._whiten(rows), 0, score)
+
+    def _whiten(self, rows):
+        """[m, E] NumPy or tensor -> what the index holds: device float32 rows (NumPy with query_fn)."""
+        if self.pca is not None:
+            rows = self.pca.transform_rows(rows)
+        if self._query_fn is not None:
+            return rows.cpu().numpy() if isinstance(rows, torch.Tensor) else np.asarray(rows, np.float32)
+        t = rows if isinstance(rows, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(rows))
+        return t.to(self.device, torch.float32).contiguous()
+
+    def query_thinned(self, desc):
+        """desc [Q, E] -> (feature_dist [Q, n] float64, rows of the THINNED list [Q, n] int64), NumPy."""
+        f = self._whiten(desc if isinstance(desc, torch.Tensor) else np.asarray(desc, dtype=np.float32))
+        if self._query_fn is not None:
+            dist, idx = self._query_fn(self._ref_f, f, self.n)
+            return np.asarray(dist, dtype=np.float64), np.asarray(idx, dtype=np.int64)
+        stats = {}
+        dist, idx = self._index.query(f, self.n, stats=stats)
+        self.uncertified += stats.get('uncertified') or 0
+        return dist.cpu().numpy(), idx.cpu().numpy()
+
+    def locate_descriptors(self, desc):
+        """desc [Q, E] -> (idx [Q, n] original reference indices, feature_dist [Q, n] float64,
+        xy [Q, n, 2]); ``xy[:, 0]`` is the position estimate."""
+        dist, local = self.query_thinned(desc)
+        idx = self._orig[local]
+        return idx, dist, self.ref_xy[idx]
+
+    def locate(self, images):
+        """images [B, H, W, {1|3}] raw 0..255 -> ``locate_descriptors`` of ``nets.output``."""
+        from ..model import nets
+        model = self.model or nets.default_model()
+        with torch.no_grad():
+            t = images if isinstance(images, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(images))
+            desc = nets.output(t.to(next(model.parameters()).device), model=model).float()
+        return self.locate_descriptors(desc)
+
+    def payload(self, local_idx, feature_dist, full_xy_dists):
+        """``top_n.retrieve``'s output list [top_i, top_g_dists, top_f_dists, gt_i, gt_g_dist, ref_idx]
+        (evaluation/top-n.py:110-119) from the hits of ``query_thinned`` for every query, in order, and
+        the queries' geographic distances to ALL references [Q, M]."""
+        ref_idx = self.ref_idx
+        xy_dists = np.asarray(full_xy_dists)[:, ref_idx]
+        top_i = np.asarray(local_idx).astype(int)
+        num_q = top_i.shape[0]
+        top_g_dists = [[xy_dists[q, r] for r in top_i[q, :]] for q in range(num_q)]
+        gt_i = np.argmin(xy_dists, axis=1)
+        gt_g_dist = np.min(xy_dists, axis=1)
+        top_i = [[ref_idx[r] for r in top_i[q, :]] for q in range(num_q)]
+        gt_i = [ref_idx[r] for r in gt_i]
+        return [top_i, top_g_dists, np.asarray(feature_dist, dtype=np.float64), gt_i, gt_g_dist, ref_idx]
+
+
+def localize_set(loc, query_f, full_xy_dists, batch=1):
+    """Feed the rows of query_f through ``loc`` in list order, ``batch`` at a time -> the payload."""
+    batch = max(int(batch), 1)
+    dists, idxs = [], []
+    for s in range(0, len(query_f), batch):
+        d, i = loc.query_thinned(query_f[s:s + batch])
+        dists.append(d)
+        idxs.append(i)
+    return loc.payload(np.concatenate(idxs), np.concatenate(dists), full_xy_dists)
+
+
+class _SklearnRows:
+    """scikit-learn's PCA behind the ``transform_rows`` interface (``--pca_backend sklearn``)."""
+
+    def __init__(self, pca):
+        self._pca = pca
+
+    def transform_rows(self, x):
+        x = x.cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+        return self._pca.transform(x).astype(np.float32)
+
+
+def main(argv=None, query_fn=None):
+    """The flags of ``top_n.main`` with a single --L and --D (0: no whitening), plus --batch: the
+    query descriptors go through a ``Localizer`` in list order, --batch at a time; the payload of
+    ``top_n.main`` goes to ``top_n.out_pickle_path``.  Prints queries per second and how many
+    queries needed the exact fallback.  Returns the path written (None: fewer than N references)."""
+    import argparse
+    import os
+    import time
+    from sklearn.metrics import pairwise_distances
+    from ..util import io
+    from ..util.meta import get_xy
+    from .pca import PCAWhitening
+    p = argparse.ArgumentParser()
+    p.add_argument('--pca_lv_pickle', required=True)
+    p.add_argument('--query_lv_pickle', required=True)
+    p.add_argument('--ref_lv_pickle', required=True)
+    p.add_argument('--query_csv', required=True)
+    p.add_argument('--ref_csv', required=True)
+    p.add_argument('--N', default=25, type=int)
+    p.add_argument('--out_root', default='./scl_top_n')
+    p.add_argument('--L', default=0.0, type=float, help='thinning distance in metres')
+    p.add_argument('--D', default=256, type=int, help='PCA dimension (0: no whitening)')
+    p.add_argument('--pca_backend', default='device', choices=['device', 'sklearn'])
+    p.add_argument('--score', default='bf16x3', choices=['f32', 'bf16x3'],
+                   help='nomination arithmetic of queries beyond the stream route (the lists are exact either way)')
+    p.add_argument('--batch', default=1, type=int, help='frames per call')
+    flags = p.parse_args(argv)
+    out = out_pickle_path(flags.out_root, flags.query_lv_pickle, flags.L, flags.D)
+    if os.path.exists(out):
+        print('{} already exists. Skipping.'.format(out))
+        return out
+    full_ref_xy = get_xy(io.load_csv(flags.ref_csv))
+    full_query_xy = get_xy(io.load_csv(flags.query_csv))
+    full_ref_f = np.array(io.load_pickle(flags.ref_lv_pickle), dtype=np.float32)
+    full_query_f = np.array(io.load_pickle(flags.query_lv_pickle), dtype=np.float32)
+    full_xy_dists = pairwise_distances(full_query_xy, full_ref_xy, metric='euclidean')
+    pca = None
+    if flags.D > 0:
+        pca_f = np.array(io.load_pickle(flags.pca_lv_pickle), dtype=np.float32)
+        if flags.pca_backend == 'device':
+            pca = PCAWhitening(flags.D, device='cuda').fit(pca_f)
+        else:
+            from sklearn.decomposition import PCA
+            pca = _SklearnRows(PCA(whiten=True, n_components=flags.D).fit(pca_f))
+    if len(thin_reference(full_ref_xy, flags.L)) < flags.N:       # (evaluation/top-n.py:96-97)
+        return None
+    loc = Localizer(full_ref_f, full_ref_xy, pca=pca, n=flags.N, l=flags.L, score=flags.score,
+                    query_fn=query_fn)
+    if query_fn is None:
+        torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    payload = localize_set(loc, full_query_f, full_xy_dists, flags.batch)
+    dt = time.perf_counter() - t0
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    io.save_pickle(payload, out)
+    print('{} queries, {} per call: {:.1f} queries/s, uncertified {}'.format(
+        len(full_query_f), max(flags.batch, 1), len(full_query_f) / max(dt, 1e-9), loc.uncertified))
+    return out
+
+
+if __name__ == '__main__':
+    main()

@@ -95,3 +95,23 @@ class PCAWhitening:
             blk = host[r:r + batch].to(self._proj.device, torch.float32)
             out[r:r + batch] = blk @ self._proj - self._offset
         return out
+
+    def transform_rows(self, x, batch=4096):
+        """The projection of ``transform`` through the package's dense kernel
+        (``reduction.dense_fwd`` with W = ``_proj``, b = -``_offset``).  That kernel's output rows
+        do not depend on what else shares the call, so a frame whitened alone and the same frame
+        whitened inside a batch give the same bits — which the library GEMM behind ``transform``
+        does not promise.  HIP device only."""
+        from ..model import reduction
+        if self._proj is None:
+            raise RuntimeError('PCAWhitening.transform_rows called before fit')
+        host = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
+        if host.dim() != 2 or host.shape[1] != self._proj.shape[0]:
+            raise ValueError('expected [m, %d] features, got %s' % (self._proj.shape[0], tuple(host.shape)))
+        bias = (-self._offset).contiguous()
+        out = torch.empty(host.shape[0], self.n_components, dtype=torch.float32,
+                          device=self._proj.device)
+        for r in range(0, host.shape[0], batch):
+            blk = host[r:r + batch].to(self._proj.device, torch.float32).contiguous()
+            out[r:r + batch] = reduction.dense_fwd(blk, self._proj, bias, False)
+        return out

@@ -1,7 +1,8 @@
 """Exact L2 top-n retrieval, the replacement for the KDTree query of
 ``evaluation/top-n.py:103-108`` (also ``train/train.py:1181-1182``).
 
-``topn_l2`` runs csrc/topn.hip on one device; ``merge_topn`` combines per-shard results
+``topn_l2`` runs csrc/topn.hip on one device; ``RetrievalIndex`` prepares a fixed reference set
+once and answers many small queries against it; ``merge_topn`` combines per-shard results
 when the reference set is split over ranks (shard the reference set,
 replicate the queries, all-gather the [Q,n] candidates, merge).
 """
@@ -80,6 +81,97 @@ def topn_l2(ref, query, n, idx_offset=0, score='f32', certify=True, stats=None):
     if bad.numel():
         _resolve_exactly(ref, query, n, int(idx_offset), bad, bound, dist, idx)
     return dist, idx
+
+
+_WIDTHS = (32, 64, 128, 256)
+
+
+class RetrievalIndex:
+    """A fixed reference set prepared once for many ``topn_l2`` calls (a localiser: frames arrive
+    one or a few at a time).  ``RetrievalIndex(ref, idx_offset, score).query(query, n, certify,
+    stats)`` returns what ``topn_l2(ref, query, n, idx_offset, score, certify, stats)`` returns, in
+    both tensors, for any data.
+
+    Built once (``scl_topn_index_build``): the reference norms, their maximum and, with
+    ``score='bf16x3'``, the two bf16 planes — what ``topn_l2`` recomputes per call.  A query of at
+    most ``_lib.TOPN_STREAM_MAX_Q`` rows takes the stream route of ``scl_topn_index_query`` (one pass
+    over the float32 rows on every CU); more rows run the scan of ``topn_l2`` from the index.
+    ``stats`` also receives ``route``: 'stream', 'scan', or 'delegate' for what the index does not
+    cover (descriptors wider than 256, n > 25: ``topn_l2`` on the stored rows).  A width that is not
+    32, 64, 128 or 256 is zero-padded, once here and per query.  The index block and the workspace
+    are tensors owned by the object; use one object per stream."""
+
+    def __init__(self, ref, idx_offset=0, score='f32'):
+        if score not in SCORE_MODES:
+            raise ValueError("score must be one of %s, got %r" % (sorted(SCORE_MODES), score))
+        L.require_device(ref)
+        ref = ref.float().contiguous()
+        if ref.dim() != 2 or ref.shape[0] < 1:
+            raise ValueError("ref %s must be [R,d] with R >= 1" % (tuple(ref.shape),))
+        self.idx_offset = int(idx_offset)
+        self.score = score
+        self.width = ref.shape[1]                      # of the rows as given
+        self._flags = SCORE_MODES[score]
+        self._ws = None
+        self._index = None
+        if self.width > 256:
+            self.ref = ref                             # (topn_l2's wide path; nothing to prepare)
+            return
+        if self.width not in _WIDTHS:
+            pad = next(c for c in _WIDTHS if self.width <= c)
+            ref = torch.nn.functional.pad(ref, (0, pad - self.width))
+        self.ref = ref
+        lib = L.load()
+        r, d = ref.shape
+        nbytes = lib.scl_topn_index_bytes(r, d, self._flags)
+        if nbytes == 0:
+            raise ValueError("unsupported index shape R=%d d=%d" % (r, d))
+        self._index = L.workspace(nbytes, ref.device)
+        L.check(lib.scl_topn_index_build(L.ptr(ref), r, d, L.ptr(self._index), self._index.numel(),
+                                         self._flags, L.stream_of(ref)))
+
+    def query(self, query, n, certify=True, stats=None):
+        """query [Q, width] float32 on the index's device -> (dist [Q,n] float64, idx [Q,n] int64)."""
+        L.require_device(query)
+        query = query.float().contiguous()
+        if query.dim() != 2 or query.shape[1] != self.width:
+            raise ValueError("query %s must be [Q,%d]" % (tuple(query.shape), self.width))
+        ref = self.ref
+        r, d = ref.shape
+        q = query.shape[0]
+        if n > r or n < 1:
+            raise ValueError("n must be in [1, R], got n=%d R=%d" % (n, r))
+        if self._index is None or n > MAX_N:
+            if stats is not None:
+                stats['route'] = 'delegate'
+            return topn_l2(ref[:, :self.width], query, n, self.idx_offset, self.score, certify, stats)
+        if d != self.width:
+            query = torch.nn.functional.pad(query, (0, d - self.width))
+        lib = L.load()
+        nbytes = lib.scl_topn_index_query_workspace_bytes(r, q, d, n, self._flags)
+        if nbytes == 0:
+            raise ValueError("unsupported retrieval shape R=%d Q=%d d=%d n=%d" % (r, q, d, n))
+        if self._ws is None or self._ws.numel() < nbytes:
+            self._ws = L.workspace(nbytes, ref.device)
+        ws = self._ws
+        if stats is not None:
+            stats['route'] = 'stream' if q <= L.TOPN_STREAM_MAX_Q else 'scan'
+        idx = torch.empty((q, n), dtype=torch.int64, device=ref.device)
+        dist = torch.empty((q, n), dtype=torch.float64, device=ref.device)
+        flag = torch.empty(q, dtype=torch.uint8, device=ref.device) if certify else None
+        bound = torch.empty(q, dtype=torch.float64, device=ref.device) if certify else None
+        L.check(lib.scl_topn_index_query(L.ptr(ref), r, d, L.ptr(self._index), self._index.numel(),
+                                         L.ptr(query), q, n, self.idx_offset, L.ptr(idx), L.ptr(dist),
+                                         L.ptr(flag), L.ptr(bound), L.ptr(ws), ws.numel(),
+                                         self._flags, L.stream_of(ref)))
+        if not certify:
+            return dist, idx
+        bad = torch.nonzero(flag).reshape(-1)                      # (synchronises; usually empty)
+        if stats is not None:
+            stats['uncertified'] = int(bad.numel())
+        if bad.numel():
+            _resolve_exactly(ref, query, n, self.idx_offset, bad, bound, dist, idx)
+        return dist, idx
 
 
 _FILTER_CAP = 2048      # candidates within the bound kept per uncertified query
