@@ -781,6 +781,35 @@ int scl_frames_gather(const void* bank, long long bank_slots, const void* extra,
                       void* out, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * The 8-bit bilinear resize of the loaders (csrc/frames.hip; util/cv.py resize_plan /
+ * apply_plan, util/device_cv.py DeviceResizer): OpenCV's unfiltered INTER_LINEAR on uint8 as
+ * util/cv.py restates it, with the float32 coordinate computation done by the HOST — the device
+ * applies four int32 tables per axis, so its pixels are apply_plan's by construction.
+ *
+ *   src     uint8 [n, sh, sw, c], dense, c = 1 or 3
+ *   xtab    int32 [4][ow] ON THE DEVICE: x0, x1 (source columns), a0, a1 (11-bit weights)
+ *   ytab    int32 [4][oh] ON THE DEVICE: y0, y1 (source rows), b0, b1
+ *   out     [n, oh, ow, c], uint8 (SCL_FRAMES_U8) or float32 (SCL_FRAMES_F32: the float32 of
+ *           that byte, what .astype(np.float32) makes)
+ * Per output value, in int32 (products modulo 2^32, shifts arithmetic):
+ *   S0 = src[y0][x0] a0 + src[y0][x1] a1;   S1 the same on row y1
+ *   v  = (((b0 (S0 >> 4)) >> 16) + ((b1 (S1 >> 4)) >> 16) + 2) >> 2, clipped to 0..255
+ * A cropped result is a call with shorter tables (ResizePlan.window): oh and ow are the lengths
+ * of the tables, not a function of sh and sw.
+ * The launcher cannot see the tables: the kernel clamps every index it reads from one to
+ * [0, sw-1] or [0, sh-1], so a wrong table gives wrong pixels but never a read outside src.
+ * src, a uint8 out, and every frame and row inside them may lie at any byte address (byte
+ * loads and stores); a float32 out must be 4-byte aligned.  Frame offsets are 64-bit.
+ * Returns SCL_E_NULL for src, xtab, ytab or out NULL; SCL_E_SHAPE for n outside 1..65535, c not
+ * 1 or 3, sh, sw, oh or ow outside 1..16384, an unknown out_kind, or a float32 out that is not
+ * 4-byte aligned; nothing is launched then.
+ * ------------------------------------------------------------------------- */
+#define SCL_FRAMES_U8 0
+#define SCL_FRAMES_F32 1
+int scl_frames_resize(const void* src, int n, int sh, int sw, int c, const int* xtab, int ow,
+                      const int* ytab, int oh, int out_kind, void* out, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * The parameter update (csrc/optim.hip; train/optim.py HipAdam / HipMomentum): TensorFlow's
  * ApplyAdam and ApplyMomentum (non-Nesterov) for a whole LIST of float32 parameters in one launch,
  * every operation a float32 operation rounded on its own (no contraction into fused multiply-adds,

@@ -39,7 +39,8 @@ EIGEN_NTUPLET_EVMM, EIGEN_NTUPLET_TRACE, EIGEN_NEG_EIGENVALUE = 3, 4, 5
 CONV_TRANSPOSED, W_F32, W_PACKED = 1, 2, 4   # flag word of the convolution entry points
 PACK_VLAD_W = 16           # SclPackJob.flags: the job writes the NetVLAD plane images of assign_w
 OPTIM_CHUNK_GROUPS = 1024  # SCL_OPTIM_CHUNK_GROUPS: 16-byte groups per workgroup of scl_apply_*
-OPTIM_SEG_WORDS = 6        # SclOptimSeg as int64 words: var, grad, slot0, slot1, n, first_chunk
+FRAMES_U8, FRAMES_F32 = 0, 1   # out_kind of scl_frames_resize
+OPTIM_SEG_WORDS = 6       # SclOptimSeg as int64 words: var, grad, slot0, slot1, n, first_chunk
 
 _p = ctypes.c_void_p
 _i = ctypes.c_int
@@ -156,6 +157,7 @@ SIGNATURES = {
     "scl_eigen_loss_workspace_bytes": (_z, [_i, _i, _i, _i]),
     "scl_eigen_loss_fwd": (_i, [_i, _p, _p, _p, _i, _i, _i, _i, _f, _i, _p, _p, _p, _p, _z, _p]),
     "scl_frames_gather": (_i, [_p, _l, _p, _l, _p, _i, _l, _p, _p]),
+    "scl_frames_resize": (_i, [_p, _i, _i, _i, _i, _p, _i, _p, _i, _i, _p, _p]),
     "scl_apply_adam": (_i, [_p, _i, _l, _p, _p, _f, _f, _f, _p, _p]),
     "scl_apply_momentum": (_i, [_p, _i, _l, _p, _f, _p, _p]),
     "scl_grad_stats_workspace_bytes": (_z, [_l]),

@@ -17,6 +17,9 @@
 //     one by one — still 256 contiguous bytes per wave instruction — and stored as a float4.
 // A slot outside its source (a bookkeeping bug above this layer) reads nothing and fills its
 // output frame with NaN.
+//
+// Further down: scl_frames_resize, the loaders' 8-bit bilinear resize applied from host-made
+// tables (util/cv.py resize_plan; util/device_cv.py).
 #include "scl_common.h"
 
 namespace {
@@ -95,7 +98,79 @@ __global__ __launch_bounds__(kThreads) void frames_gather_kernel(
   }
 }
 
+// ---- the 8-bit bilinear resize of util/cv.py (resize_plan / apply_plan) ----------------------
+// The host splits OpenCV's float32 coordinate computation into four int32 tables per axis (two
+// source indices, two 11-bit weights); the device only applies them, in the int32 arithmetic of
+// apply_plan, so its pixels are the host's by construction:
+//   S0 = src[y0][x0] a0 + src[y0][x1] a1,  S1 the same on row y1,
+//   v  = clip((((b0 (S0 >> 4)) >> 16) + ((b1 (S1 >> 4)) >> 16) + 2) >> 2, 0, 255).
+// One work-item per output pixel, all channels: the stores of a wave are contiguous (768 bytes of
+// float32 at c = 3).  The loads are a sparse gather — at 1280 x 960 -> 240 x 180 an output value
+// touches 2 x 2 source pixels of every 5.3 x 5.3 — served by L2; plain byte loads, any alignment.
+// grid = (chunks of a frame's pixels, n).
+// The tables are device memory the launcher cannot see: every index read from one is clamped to
+// [0, sw-1] or [0, sh-1], so a wrong table gives wrong pixels but never a read outside the frame
+// (products are taken modulo 2^32 like NumPy's int32, so a wrong weight is no undefined
+// behaviour either).
+__device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
+__device__ __forceinline__ int wrap_mul(int a, int b) { return (int)((unsigned)a * (unsigned)b); }
+
+template <int C, typename Out>
+__global__ __launch_bounds__(kThreads) void frames_resize_kernel(
+    const unsigned char* __restrict__ src, int sh, int sw, const int* __restrict__ xtab, int ow,
+    const int* __restrict__ ytab, int oh, Out* __restrict__ out) {
+  const int pix = blockIdx.x * kThreads + threadIdx.x;       // oh ow <= 2^28
+  if (pix >= oh * ow) return;
+  const int oy = pix / ow, ox = pix - oy * ow;
+  const int x0 = clampi(xtab[ox], sw - 1) * C, x1 = clampi(xtab[ow + ox], sw - 1) * C;
+  const int a0 = xtab[2 * ow + ox], a1 = xtab[3 * ow + ox];
+  const int y0 = clampi(ytab[oy], sh - 1), y1 = clampi(ytab[oh + oy], sh - 1);
+  const int b0 = ytab[2 * oh + oy], b1 = ytab[3 * oh + oy];
+  const long long row = (long long)sw * C;
+  const unsigned char* frame = src + (long long)blockIdx.y * sh * row;
+  const unsigned char* r0 = frame + y0 * row;
+  const unsigned char* r1 = frame + y1 * row;
+  Out* dst = out + ((long long)blockIdx.y * oh * ow + pix) * C;
+#pragma unroll
+  for (int ch = 0; ch < C; ++ch) {
+    const int s0 = wrap_mul(r0[x0 + ch], a0) + wrap_mul(r0[x1 + ch], a1);
+    const int s1 = wrap_mul(r1[x0 + ch], a0) + wrap_mul(r1[x1 + ch], a1);
+    const int v = ((wrap_mul(b0, s0 >> 4) >> 16) + (wrap_mul(b1, s1 >> 4) >> 16) + 2) >> 2;
+    dst[ch] = (Out)clampi(v, 255);
+  }
+}
+
+template <int C, typename Out>
+void launch_resize(const void* src, int n, int sh, int sw, const int* xtab, int ow, const int* ytab,
+                   int oh, void* out, hipStream_t stream) {
+  const dim3 grid((unsigned)(((long long)oh * ow + kThreads - 1) / kThreads), (unsigned)n);
+  SCL_LAUNCH("frames_resize_kernel", (frames_resize_kernel<C, Out>), grid, dim3(kThreads), 0, stream,
+             static_cast<const unsigned char*>(src), sh, sw, xtab, ow, ytab, oh,
+             static_cast<Out*>(out));
+}
+
 }  // namespace
+
+extern "C" int scl_frames_resize(const void* src, int n, int sh, int sw, int c, const int* xtab,
+                                 int ow, const int* ytab, int oh, int out_kind, void* out,
+                                 void* stream) {
+  if (!src || !xtab || !ytab || !out) return SCL_E_NULL;
+  const int side_cap = 16384;
+  if (n < 1 || n > 65535 || (c != 1 && c != 3)) return SCL_E_SHAPE;
+  if (sh < 1 || sw < 1 || sh > side_cap || sw > side_cap) return SCL_E_SHAPE;
+  if (oh < 1 || ow < 1 || oh > side_cap || ow > side_cap) return SCL_E_SHAPE;
+  if (out_kind != SCL_FRAMES_U8 && out_kind != SCL_FRAMES_F32) return SCL_E_SHAPE;
+  if (out_kind == SCL_FRAMES_F32 && (((uintptr_t)out) & 3u)) return SCL_E_SHAPE;
+  const hipStream_t st = (hipStream_t)stream;
+  if (out_kind == SCL_FRAMES_U8) {
+    if (c == 1) launch_resize<1, unsigned char>(src, n, sh, sw, xtab, ow, ytab, oh, out, st);
+    else launch_resize<3, unsigned char>(src, n, sh, sw, xtab, ow, ytab, oh, out, st);
+  } else {
+    if (c == 1) launch_resize<1, float>(src, n, sh, sw, xtab, ow, ytab, oh, out, st);
+    else launch_resize<3, float>(src, n, sh, sw, xtab, ow, ytab, oh, out, st);
+  }
+  return scl_launch_status();
+}
 
 extern "C" int scl_frames_gather(const void* bank, long long bank_slots, const void* extra,
                                  long long extra_slots, const int* slots, int n,

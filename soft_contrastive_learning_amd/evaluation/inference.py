@@ -12,7 +12,8 @@ util/io.py restated in ``soft_contrastive_learning_amd/util``): 'oxs' sets read 
 ``.png``, 'achen' sets are portrait (cover ``large_side x small_side``), with the NetVLAD head the
 longer side becomes ``large_side`` unless ``--rescale`` is off, without it the frame is brought to
 ``small_side x large_side``.  Six loader threads feed the device (:155-160).  ``--set synthetic``:
-random images, no files.
+random images, no files.  ``--device_resize 1`` leaves the sizing of the decoded frames to the device
+(util/device_cv.py, csrc/frames.hip: the same pixels, the same pickle).
 """
 import argparse
 import os
@@ -32,11 +33,26 @@ def pad_indices(num, images_per_pass):
     return np.concatenate((np.arange(num), np.array(padding, dtype=int))).astype(int)
 
 
-def extract_features(model, loader, num, images_per_pass=4, device=None, loader_threads=6):
+def size_on_host(img, rule, kw):
+    """One decoded frame through a sizing rule of ``csv_loader`` on the host (util/cv.py)."""
+    from ..util import cv
+    if rule == 'none':
+        return img
+    return getattr(cv, rule)(img, **kw)
+
+
+def extract_features(model, loader, num, images_per_pass=4, device=None, loader_threads=6,
+                     device_resize=False):
     """Returns ``list`` of ``num`` float32 vectors (length 32768 with the NetVLAD head, H' W' 512
     without: ``ops['full_out']``, evaluation/inference.py:89-92; ``out_dim`` with a dense reduction
     head: ``ops['output']``, :97-109), in index order.  ``loader`` is
-    called from ``loader_threads`` threads (cpu_thread, :28-38), one batch ahead of the device."""
+    called from ``loader_threads`` threads (cpu_thread, :28-38), one batch ahead of the device.
+
+    ``device_resize``: ``loader`` returns ``(decoded uint8 frame, rule, parameters)``
+    (``csv_loader(device_resize=True)``) and every batch is sized on the device
+    (util/device_cv.py: the host's pixels bit for bit).  A batch whose frames do not share one
+    source shape is sized on the host, frame by frame, as without the flag; such batches are
+    counted and the count is printed at the end."""
     from concurrent.futures import ThreadPoolExecutor
     device = device or next(model.parameters()).device
     order = pad_indices(num, images_per_pass)
@@ -45,7 +61,16 @@ def extract_features(model, loader, num, images_per_pass=4, device=None, loader_
 
     def load_batch(s):
         idx = order[s:s + images_per_pass]
-        return np.stack([np.asarray(loader(int(i)), dtype=np.float32) for i in idx])
+        if not device_resize:
+            return np.stack([np.asarray(loader(int(i)), dtype=np.float32) for i in idx])
+        raw = [loader(int(i)) for i in idx]
+        if len({(img.shape, rule, tuple(sorted(kw.items()))) for img, rule, kw in raw}) == 1:
+            return np.stack([img for img, _, _ in raw]), raw[0][1], raw[0][2]
+        return np.stack([np.asarray(size_on_host(*r), dtype=np.float32) for r in raw])
+    on_host = 0                       # batches of mixed source shapes (device_resize only)
+    if device_resize:
+        from ..util.device_cv import DeviceResizer
+        resizer = DeviceResizer(device)
     with torch.no_grad(), ThreadPoolExecutor(max_workers=max(int(loader_threads), 1)) as pool:
         ahead = max(int(loader_threads), 1)
         pending = [pool.submit(load_batch, s) for s in starts[:ahead]]
@@ -53,17 +78,29 @@ def extract_features(model, loader, num, images_per_pass=4, device=None, loader_
             batch = pending.pop(0).result()
             if k + ahead < len(starts):
                 pending.append(pool.submit(load_batch, starts[k + ahead]))
-            out = nets.output(torch.from_numpy(batch).to(device), model=model)
+            if isinstance(batch, tuple):
+                frames, rule, kw = batch
+                batch = resizer.apply(frames, rule, torch.float32, **kw)
+            else:
+                on_host += int(device_resize)
+                batch = torch.from_numpy(batch).to(device)
+            out = nets.output(batch, model=model)
             out = out.float().cpu().numpy()
             for slot, f in zip(range(s, s + len(out)), out):
                 feats[slot] = f
+    if device_resize:
+        print('device_resize: {} of {} batches sized on the host (mixed source shapes)'.format(
+            on_host, len(starts)))
     return feats[:num]
 
 
-def csv_loader(set_name, csv_root, img_root, vlad_cores=64, rescale=True, small_side=180, large_side=240):
+def csv_loader(set_name, csv_root, img_root, vlad_cores=64, rescale=True, small_side=180, large_side=240,
+               device_resize=False):
     """(loader, num) over ``<csv_root>/<set>.csv`` (column ``path``): evaluation/inference.py:52-72,
-    168-170."""
-    from ..util import cv, io
+    168-170.  ``device_resize``: the loader returns ``(decoded uint8 frame, rule, parameters)`` —
+    the frame as decoded and the sizing it would have applied (``size_on_host``,
+    ``DeviceResizer.apply``) — for ``extract_features(device_resize=True)``."""
+    from ..util import io
     meta = io.load_csv(os.path.join(csv_root, '{}.csv'.format(set_name)))
     if not isinstance(meta, dict) or 'path' not in meta:
         raise ValueError('%s.csv needs a "path" column and at least one row' % set_name)
@@ -74,11 +111,13 @@ def csv_loader(set_name, csv_root, img_root, vlad_cores=64, rescale=True, small_
         if 'oxs' in set_name:
             rel = rel.replace('.png', '.jpg')
         img = io.load_img(os.path.join(img_root, rel))
-        if 'achen' in set_name:
-            return cv.standard_size(img, h=large_side, w=small_side)           # portrait images
-        if vlad_cores > 0:
-            return cv.resize_img(img, large_side) if rescale else img
-        return cv.standard_size(img, h=small_side, w=large_side)
+        return (img, rule, kw) if device_resize else size_on_host(img, rule, kw)
+    if 'achen' in set_name:
+        rule, kw = 'standard_size', dict(h=large_side, w=small_side)        # portrait images
+    elif vlad_cores > 0:
+        rule, kw = ('resize_img', dict(max_size=large_side)) if rescale else ('none', {})
+    else:
+        rule, kw = 'standard_size', dict(h=small_side, w=large_side)
     return load, len(paths)
 
 
@@ -94,7 +133,7 @@ def synthetic_loader(height, width, seed=42):
     return load
 
 
-def main(argv=None):
+def build_parser():
     p = argparse.ArgumentParser()
     # flag names of evaluation/inference.py:204-230
     p.add_argument('--rescale', default=True,
@@ -112,7 +151,14 @@ def main(argv=None):
     p.add_argument('--out_root', default='./scl_lv')
     p.add_argument('--images_per_pass', type=int, default=4)
     p.add_argument('--num_images', type=int, default=10, help='synthetic set size')
-    flags = p.parse_args(argv)
+    p.add_argument('--device_resize', type=int, default=0,
+                   help='1: size the decoded frames of a CSV set on the device (csrc/frames.hip; '
+                        'the pickle is the same)')
+    return p
+
+
+def main(argv=None):
+    flags = build_parser().parse_args(argv)
     # --reduction pca writes the RAW descriptors, like the reference: "Don't actually do PCA
     # here - doing it after" (evaluation/inference.py:94-95; its projection branch at :111-116
     # is unreachable).  The whitening runs in evaluation/top_n.py.
@@ -127,12 +173,15 @@ def main(argv=None):
                          width=flags.large_side)
     if flags.checkpoint:
         checkpoint.load(model, flags.checkpoint)     # every variable, the head included (:122-131)
+    device_resize = False
     if flags.set == 'synthetic' and not flags.csv_root:
         loader, num = synthetic_loader(flags.small_side, flags.large_side), flags.num_images
     else:
+        device_resize = bool(flags.device_resize)
         loader, num = csv_loader(flags.set, flags.csv_root, flags.img_root, flags.vlad_cores,
-                                 flags.rescale, flags.small_side, flags.large_side)
-    feats = extract_features(model, loader, num, flags.images_per_pass)
+                                 flags.rescale, flags.small_side, flags.large_side,
+                                 device_resize=device_resize)
+    feats = extract_features(model, loader, num, flags.images_per_pass, device_resize=device_resize)
     os.makedirs(flags.out_root, exist_ok=True)
     out = os.path.join(flags.out_root, '{}_{}.pickle'.format(flags.set, flags.out_name))
     save_pickle(feats, out)

@@ -43,6 +43,7 @@ class Localizer:
         self.model = model
         self._query_fn = query_fn
         self.uncertified = 0                                          # over all calls so far
+        self._resizer = None                                          # prepare_raw's, made on first use
         rows = np.asarray(ref_desc, dtype=np.float32)[self._orig]
         if query_fn is not None:
             self.device = None
@@ -87,6 +88,23 @@ class Localizer:
             t = images if isinstance(images, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(images))
             desc = nets.output(t.to(next(model.parameters()).device), model=model).float()
         return self.locate_descriptors(desc)
+
+    def prepare_raw(self, frames, rule='resize_img', **kw):
+        """Frames as the camera or the decoder delivers them (uint8 [SH,SW,C] or [n,SH,SW,C],
+        NumPy or tensor, host or device) -> the float32 device batch the network sees, sized on the
+        device by the loaders' rule (util/device_cv.py; bit for bit the host's util/cv.py):
+        ``'resize_img'`` (``max_size=240``), ``'standard_size'`` (``h=180, w=240``) or ``'none'``
+        (widened only)."""
+        from ..util.device_cv import DeviceResizer
+        if self._resizer is None:
+            model = self.model
+            device = self.device if model is None else next(model.parameters()).device
+            self._resizer = DeviceResizer('cpu' if device is None else device)   # a CPU device raises
+        return self._resizer.apply(frames, rule, torch.float32, **kw)
+
+    def locate_raw(self, frames, rule='resize_img', **kw):
+        """``locate`` of ``prepare_raw(frames, rule, **kw)``."""
+        return self.locate(self.prepare_raw(frames, rule, **kw))
 
     def payload(self, local_idx, feature_dist, full_xy_dists):
         """``top_n.retrieve``'s output list [top_i, top_g_dists, top_f_dists, gt_i, gt_g_dist, ref_idx]

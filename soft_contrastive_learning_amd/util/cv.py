@@ -51,16 +51,44 @@ def _axis(dn, sn, inv_scale, zero_outside):
     return s0, s1, w0, w1
 
 
-def resize_linear(img, fx=None, fy=None, dsize=None):
-    """``cv2.resize(img, (0, 0), fx=fx, fy=fy)`` — or ``cv2.resize(img, dsize)`` with ``dsize`` =
-    (width, height), where the sampling scale is the ratio of the sizes — for a uint8 image [H,W] or
-    [H,W,C]."""
-    img = np.asarray(img)
-    if img.dtype != np.uint8 or img.ndim not in (2, 3):
-        raise ValueError("resize_linear takes a uint8 image [H,W] or [H,W,C]")
-    flat = img.ndim == 2
-    src = img[:, :, None] if flat else img
-    sh, sw = src.shape[:2]
+class ResizePlan:
+    """Everything ``resize_linear`` derives from the sizes alone, for a source of ``sh x sw``: the
+    destination size ``dh x dw`` and, per destination column, the two source columns ``x0, x1`` and
+    their fixed-point weights ``a0, a1`` (per row: ``y0, y1, b0, b1``), all int32.  What is left
+    for the pixels is integer arithmetic (``apply_plan``; on the device csrc/frames.hip
+    ``scl_frames_resize``, which takes the tables as they are here)."""
+    __slots__ = ('sh', 'sw', 'dh', 'dw', 'x0', 'x1', 'a0', 'a1', 'y0', 'y1', 'b0', 'b1')
+
+    def __init__(self, sh, sw, xs, ys):
+        self.sh, self.sw = int(sh), int(sw)
+        self.x0, self.x1, self.a0, self.a1 = (np.ascontiguousarray(t, dtype=np.int32) for t in xs)
+        self.y0, self.y1, self.b0, self.b1 = (np.ascontiguousarray(t, dtype=np.int32) for t in ys)
+        self.dh, self.dw = len(self.y0), len(self.x0)
+
+    def window(self, top, left, h, w):
+        """The plan of ``result[top:top + h, left:left + w]``: a crop only shortens the tables."""
+        top, left, h, w = int(top), int(left), int(h), int(w)
+        if top < 0 or left < 0 or h < 1 or w < 1 or top + h > self.dh or left + w > self.dw:
+            raise ValueError("window %d:%d, %d:%d is not inside the %d x %d result"
+                             % (top, top + h, left, left + w, self.dh, self.dw))
+        return ResizePlan(self.sh, self.sw,
+                          [t[left:left + w] for t in (self.x0, self.x1, self.a0, self.a1)],
+                          [t[top:top + h] for t in (self.y0, self.y1, self.b0, self.b1)])
+
+    def xtab(self):
+        """int32 [4, dw]: x0, x1, a0, a1 — the layout ``scl_frames_resize`` reads."""
+        return np.stack([self.x0, self.x1, self.a0, self.a1])
+
+    def ytab(self):
+        """int32 [4, dh]: y0, y1, b0, b1."""
+        return np.stack([self.y0, self.y1, self.b0, self.b1])
+
+
+def resize_plan(sh, sw, fx=None, fy=None, dsize=None):
+    """The plan of ``resize_linear(img, fx, fy, dsize)`` for an image of ``sh x sw``."""
+    sh, sw = int(sh), int(sw)
+    if sh < 1 or sw < 1:
+        raise ValueError("resize_plan: empty source (%d x %d)" % (sw, sh))
     if dsize is not None:
         dw, dh = int(dsize[0]), int(dsize[1])
         fx, fy = dw / float(sw), dh / float(sh)
@@ -68,23 +96,60 @@ def resize_linear(img, fx=None, fy=None, dsize=None):
         dw, dh = int(np.rint(sw * float(fx))), int(np.rint(sh * float(fy)))
     if dw < 1 or dh < 1:
         raise ValueError("resize_linear: empty destination (%d x %d)" % (dw, dh))
-    x0, x1, a0, a1 = _axis(dw, sw, float(fx), True)
-    y0, y1, b0, b1 = _axis(dh, sh, float(fy), False)
+    return ResizePlan(sh, sw, _axis(dw, sw, float(fx), True), _axis(dh, sh, float(fy), False))
+
+
+def plan_resize_img(sh, sw, max_size):
+    """The plan of ``resize_img``: the longer side becomes ``max_size``."""
+    scale = max_size / float(max(sh, sw))
+    return resize_plan(sh, sw, scale, scale)
+
+
+def plan_standard_size(sh, sw, h=180, w=240):
+    """The plan of ``standard_size``: cover h x w, windowed to the centre crop."""
+    scale = max(h / sh, w / sw)
+    full = resize_plan(sh, sw, scale, scale)
+    top = math.floor((full.dh - h) / 2.0)
+    left = math.floor((full.dw - w) / 2.0)
+    return full.window(top, left, h, w)
+
+
+def apply_plan(img, plan):
+    """The pixels of ``plan`` for a uint8 image [H,W] or [H,W,C] of the plan's source size."""
+    img = np.asarray(img)
+    if img.dtype != np.uint8 or img.ndim not in (2, 3):
+        raise ValueError("resize_linear takes a uint8 image [H,W] or [H,W,C]")
+    if img.shape[:2] != (plan.sh, plan.sw):
+        raise ValueError("the plan is for a %d x %d image, not %d x %d"
+                         % (plan.sw, plan.sh, img.shape[1], img.shape[0]))
+    flat = img.ndim == 2
+    src = img[:, :, None] if flat else img
+    x0, x1, a0, a1 = plan.x0, plan.x1, plan.a0, plan.a1
+    b0, b1 = plan.b0, plan.b1
 
     def hpass(rows):                       # uint8 [dh, W, C] -> int32 [dh, dw, C], values scaled by 2048
         # (only the pixels that are sampled are widened: a 1280 x 960 frame coming down to 240 x 180
         # touches 2 x 2 of every 5.3 x 5.3 pixels)
         return rows[:, x0].astype(np.int32) * a0[None, :, None] + rows[:, x1].astype(np.int32) * a1[None, :, None]
-    s0, s1 = hpass(src[y0]), hpass(src[y1])
+    s0, s1 = hpass(src[plan.y0]), hpass(src[plan.y1])
     out = (((b0[:, None, None] * (s0 >> 4)) >> 16) + ((b1[:, None, None] * (s1 >> 4)) >> 16) + 2) >> 2
     out = np.clip(out, 0, 255).astype(np.uint8)
     return out[:, :, 0] if flat else out
 
 
+def resize_linear(img, fx=None, fy=None, dsize=None):
+    """``cv2.resize(img, (0, 0), fx=fx, fy=fy)`` — or ``cv2.resize(img, dsize)`` with ``dsize`` =
+    (width, height), where the sampling scale is the ratio of the sizes — for a uint8 image [H,W] or
+    [H,W,C]."""
+    img = np.asarray(img)
+    if img.dtype != np.uint8 or img.ndim not in (2, 3):
+        raise ValueError("resize_linear takes a uint8 image [H,W] or [H,W,C]")
+    return apply_plan(img, resize_plan(img.shape[0], img.shape[1], fx, fy, dsize))
+
+
 def resize_img(img, max_size):
     """util/cv.py:7-9: the longer side becomes ``max_size`` (both axes by the same factor)."""
-    scale = max_size / float(max(img.shape[0], img.shape[1]))
-    return resize_linear(img, scale, scale)
+    return apply_plan(img, plan_resize_img(img.shape[0], img.shape[1], max_size))
 
 
 def standard_size(img, h=180, w=240):
