@@ -2274,17 +2274,6 @@ void launch_rowtile(const RowTileArgs& a, hipStream_t st) {
 // float32-MFMA kernels instead (A/B timing and parity runs)
 inline bool use_fused() { return scl_variant() < 1 || scl_variant() > 8; }
 
-struct Carver {
-  char* base;
-  size_t off = 0;
-  explicit Carver(void* p) : base((char*)p) {}
-  float* take(size_t floats) {
-    float* ptr = (float*)(base + off);
-    off += scl_round256(floats * sizeof(float));
-    return ptr;
-  }
-};
-
 // Slices of the fused kernels: steps of 32 locations per workgroup so that B * S workgroups
 // cover the chip once (one workgroup per CU, 512 registers per lane).
 struct VladPlan {

@@ -5,6 +5,7 @@
 #include <stdlib.h>
 #include <atomic>
 #include <mutex>
+#include <type_traits>
 
 #include "scl_hip.h"
 #include "scl_cdna4.h"   // vector types, MFMA wrappers, LDS-DMA, transposed LDS reads
@@ -333,3 +334,18 @@ template <auto Kernel> static inline void scl_lds_limit(int bytes) {
 static inline int scl_launch_status() { return (int)hipGetLastError(); }
 static inline bool scl_aligned256(const void* p) { return (((uintptr_t)p) & 255u) == 0; }
 static inline size_t scl_round256(size_t n) { return (n + 255u) & ~(size_t)255u; }
+
+// A workspace cut into consecutive pieces, each rounded up to 256 bytes: every take returns the
+// next piece, `off` is what has been taken.  Over nullptr it only measures (a layout's size is
+// then the `off` its carving function ends with; the pointers are not to be used).
+struct Carver {
+  char* base;
+  size_t off = 0;
+  explicit Carver(void* p) : base((char*)p) {}
+  template <class T> T* take(size_t count) {
+    T* ptr = (T*)(base + off);
+    off += scl_round256(count * sizeof(T));
+    return ptr;
+  }
+  float* take(size_t floats) { return take<float>(floats); }
+};

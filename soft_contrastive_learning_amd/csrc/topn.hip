@@ -1126,6 +1126,10 @@ __global__ __launch_bounds__(256) void topn_stream_select_kernel(const float* __
 struct TopnPlan {
   int qtiles, splits, refs_per_split;
 };
+// scl_variant() as the scan reads it: below 8000, 1000 * the scan kernel's `dbg` word + (100 + s:
+// force s splits); 9000 + bits: `bits` is the `dbg` word (use_tau); other values: other kernels
+inline int topn_scan_variant() { return scl_variant() < 8000 ? scl_variant() : 0; }
+inline int topn_dbg_word() { return scl_variant() / 1000 == 9 ? scl_variant() % 1000 : topn_scan_variant() / 1000; }
 inline TopnPlan topn_plan(int R, int Q, int bf) {
   TopnPlan p;
   p.qtiles = (Q + 32 * QW - 1) / (32 * QW);
@@ -1150,7 +1154,7 @@ inline TopnPlan topn_plan(int R, int Q, int bf) {
       best = s;
     }
   }
-  const int tv = scl_variant() < 8000 ? scl_variant() : 0;   // larger values: other kernels
+  const int tv = topn_scan_variant();
   if (tv % 1000 >= 100) {   // tuning override (microbench.py --topn-splits)
     best = tv % 1000 - 100;
     if (best > 32) best = 32;
@@ -1236,33 +1240,24 @@ void launch_scan(const TopnPlan& p, const void* ref, const void* ref_lo, const f
                         : (BF ? "topn_scan_kernel<BF=1>" : "topn_scan_kernel<BF=0>"),
              (topn_scan_kernel<D8, BF, SEL>), dim3(p.qtiles, p.splits), dim3(256),
              scan_lds_bytes(D8 * 8, BF, SEL), st, ref, ref_lo, refnorm, R, query, Q, p.refs_per_split,
-             scl_variant() < 8000 ? scl_variant() / 1000 : (scl_variant() / 1000 == 9 ? scl_variant() % 1000 : 0),
-             cs, ci, tile_stride, tau, cnt, cap, tile_first);
+             topn_dbg_word(), cs, ci, tile_stride, tau, cnt, cap, tile_first);
 }
-template <int SEL>
-void launch_scan_d(int d, int bf, const TopnPlan& p, const void* ref, const void* ref_lo,
-                   const float* refnorm, int R, const float* query, int Q, float* cs, int* ci,
-                   hipStream_t st, int tile_stride = 1, const float* tau = nullptr, int* cnt = nullptr,
-                   int cap = 0, int tile_first = 0) {
-#define SCL_SCAN(D8, BF)                                                                                  \
-  launch_scan<D8, BF, SEL>(p, ref, ref_lo, refnorm, R, query, Q, cs, ci, st, tile_stride, tau, cnt, cap, \
-                           tile_first)
-  if (bf) {
-    switch (d) {
-      case 32: SCL_SCAN(4, 1); break;
-      case 64: SCL_SCAN(8, 1); break;
-      case 128: SCL_SCAN(16, 1); break;
-      default: SCL_SCAN(32, 1); break;
-    }
-  } else {
-    switch (d) {
-      case 32: SCL_SCAN(4, 0); break;
-      case 64: SCL_SCAN(8, 0); break;
-      case 128: SCL_SCAN(16, 0); break;
-      default: SCL_SCAN(32, 0); break;
-    }
+// f(std::integral_constant<int, d / 8>): the kernels take the width as the template argument D8
+template <class F>
+void for_width(int d, F&& f) {
+  switch (d) {
+    case 32: f(std::integral_constant<int, 4>{}); break;
+    case 64: f(std::integral_constant<int, 8>{}); break;
+    case 128: f(std::integral_constant<int, 16>{}); break;
+    default: f(std::integral_constant<int, 32>{}); break;
   }
-#undef SCL_SCAN
+}
+template <int SEL, class... Args>   // launch_scan's arguments behind (d, bf)
+void launch_scan_d(int d, int bf, const Args&... args) {
+  if (bf)
+    for_width(d, [&](auto d8) { launch_scan<decltype(d8)::value, 1, SEL>(args...); });
+  else
+    for_width(d, [&](auto d8) { launch_scan<decltype(d8)::value, 0, SEL>(args...); });
 }
 
 inline bool topn_shape_ok(int R, int Q, int d, int n) {
@@ -1310,94 +1305,36 @@ void launch_rerank(const float* ref, const float* query, int Q, int d, int split
 #undef SCL_RERANK
 }
 
-
-// Bytes of the candidate lists behind the norms: the sorted-list scan's [Q][splits][KEEP] x 2, or
-// the threshold scheme's buffers where R allows it (whichever is larger serves both).
-inline size_t topn_lists_bytes(int R, int Q, int bf) {
-  const TopnPlan p = topn_plan(R, Q, bf);
-  size_t lists = 2 * scl_round256((size_t)Q * p.splits * KEEP * sizeof(float));
-  if (R >= kTauMinRefs) {
-    const TauPlan t = tau_plan(R, Q);
-    const size_t tau_bytes = scl_round256((size_t)Q * t.pre_splits * 64 * sizeof(float)) +
-                             2 * scl_round256((size_t)Q * t.main_splits * kTauCapSplit * sizeof(float)) +
-                             scl_round256((size_t)Q * sizeof(float)) +
-                             scl_round256((size_t)Q * t.main_splits * sizeof(int));
-    if (tau_bytes > lists) lists = tau_bytes;
-  }
-  return lists;
+// The index block, what the scan needs of the references besides their float32 rows: filled by
+// topn_prepare, kept between calls by scl_topn_index_build, the head of scl_topn_l2_cert's workspace.
+struct TopnIndex {
+  unsigned* rmax_bits;   // norm-bound word (max |r|^2 as float bits), a 256-byte piece of its own
+  float* refnorm;        // [R]
+  u32x4 *hi, *lo;        // bf16x3 only: the two bf16 planes of the rows, [R][d] each
+  size_t bytes;
+};
+inline TopnIndex topn_index_at(const void* block, int R, int d, int bf) {   // nullptr: for .bytes
+  Carver c(const_cast<void*>(block));
+  TopnIndex x{};
+  x.rmax_bits = c.take<unsigned>(64);
+  x.refnorm = c.take(R);
+  if (bf) x.hi = c.take<u32x4>((size_t)R * d / 8);
+  if (bf) x.lo = c.take<u32x4>((size_t)R * d / 8);
+  x.bytes = c.off;
+  return x;
 }
-inline size_t topn_planes_bytes(int R, int d, int bf) {
-  return bf ? 2 * scl_round256((size_t)R * d * sizeof(unsigned short)) : 0;
-}
-
-// What follows the preparation (norms, norm bound, bf16 planes) in scl_topn_l2_cert and in the
-// scan route of scl_topn_index_query: scan (or pre-pass, thresholds, threshold scan) into the
-// candidate lists at `lists` (topn_lists_bytes), then the float64 re-rank with the certificate.
-int topn_scan_rerank(const float* ref, int R, const float* query, int Q, int d, int n,
-                     int64_t idx_offset, int64_t* idx_out, double* dist_out,
-                     unsigned char* uncertified, double* bound_sq, const unsigned* rmax_bits,
-                     const float* refnorm, const void* scan_ref, const void* scan_lo, char* lists,
-                     int bf, hipStream_t st) {
-  const TopnPlan p = topn_plan(R, Q, bf);
-  const bool tau_mode = use_tau(R, uncertified != nullptr, bf);
-  const TauPlan tp = tau_mode ? tau_plan(R, Q) : TauPlan{};
-  // sorted-list scan: cs / ci [Q][splits][KEEP].  threshold scheme: pre-pass values [Q][S'][64],
-  // candidate regions [Q][S][kTauCapSplit] x 2, tau [Q], counts [Q][S]
-  char* base = lists;
-  float *cs, *pre = nullptr, *tau = nullptr;
-  int *ci, *cnt = nullptr;
-  if (tau_mode) {
-    pre = (float*)base;
-    base += scl_round256((size_t)Q * tp.pre_splits * 64 * sizeof(float));
-    cs = (float*)base;
-    base += scl_round256((size_t)Q * tp.main_splits * kTauCapSplit * sizeof(float));
-    ci = (int*)base;
-    base += scl_round256((size_t)Q * tp.main_splits * kTauCapSplit * sizeof(float));
-    tau = (float*)base;
-    base += scl_round256((size_t)Q * sizeof(float));
-    cnt = (int*)base;
-    base += scl_round256((size_t)Q * tp.main_splits * sizeof(int));
-  } else {
-    cs = (float*)base;
-    base += scl_round256((size_t)Q * p.splits * KEEP * sizeof(float));
-    ci = (int*)base;
-    base += scl_round256((size_t)Q * p.splits * KEEP * sizeof(float));
-  }
-  if ((size_t)(base - lists) > topn_lists_bytes(R, Q, bf)) return SCL_E_WORKSPACE;
-  if (tau_mode) {
-    // pre-pass over every kTauStride-th tile (interleaved splits) -> tau_q -> threshold scan
-    TopnPlan pp;
-    pp.qtiles = tp.qtiles;
-    pp.refs_per_split = 0;                                   // interleaved
-    pp.splits = tp.pre_splits;
-    launch_scan_d<2>(d, bf, pp, scan_ref, scan_lo, refnorm, R, query, Q, pre, (int*)nullptr, st,
-                     tau_stride() * tp.pre_splits, nullptr, nullptr, 0, tau_stride());
-    SCL_LAUNCH("topn_tau_kernel", topn_tau_kernel, dim3((Q + 3) / 4), dim3(256), 0, st, (const float*)pre, Q,
-               tp.pre_splits, tau);
-    pp.splits = tp.main_splits;
-    launch_scan_d<1>(d, bf, pp, scan_ref, scan_lo, refnorm, R, query, Q, cs, ci, st, tp.main_splits, tau, cnt,
-                     kTauCapSplit, 1);
-  } else {
-    launch_scan_d<0>(d, bf, p, scan_ref, scan_lo, refnorm, R, query, Q, cs, ci, st);
-  }
-  const TopnEps eps = topn_eps(d, bf);
-  const int M = tau_mode ? kTauCompact : p.splits * KEEP;
-  if (tau_mode) {
-    static SclDeviceOnce once;
-    scl_call_once(once, [] {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&topn_rerank_kernel<kTauCompact / 64, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-    });
-    SCL_LAUNCH("topn_rerank_kernel<append>", (topn_rerank_kernel<kTauCompact / 64, true>), dim3((Q + 3) / 4),
-               dim3(256), rerank_lds_bytes(M), st, ref,
-               query, Q, d, tp.main_splits, n, idx_offset, (const float*)cs, (const int*)ci, idx_out, dist_out,
-               rmax_bits, eps.q, eps.r, uncertified, bound_sq,
-               (const int*)cnt, (const float*)tau, kTauCapSplit);
-    return scl_launch_status();
-  }
-  launch_rerank(ref, query, Q, d, p.splits, n, idx_offset, cs, ci, idx_out, dist_out, rmax_bits, eps,
-                uncertified, bound_sq, st);
-  return scl_launch_status();
+// the norm bound only where a certificate will read it (zeroed, then raised by refnorm_kernel)
+hipError_t topn_prepare(const TopnIndex& x, const float* ref, int R, int d, int bf, bool want_bound,
+                        hipStream_t st) {
+  const hipError_t e = want_bound ? hipMemsetAsync(x.rmax_bits, 0, 16, st) : hipSuccess;
+  if (e != hipSuccess) return e;
+  SCL_LAUNCH("refnorm_kernel", refnorm_kernel, dim3((R + 63) / 64), dim3(256), 0, st, ref, R, d,
+             x.refnorm, want_bound ? x.rmax_bits : (unsigned*)nullptr);
+  const int64_t n8 = (int64_t)R * d / 8;
+  if (bf)
+    SCL_LAUNCH("ref_split_kernel", ref_split_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256),
+               0, st, ref, n8, x.hi, x.lo);
+  return hipSuccess;
 }
 
 // The stream route's split of the reference axis: at most 32 lists per query (the re-rank keeps
@@ -1413,15 +1350,101 @@ inline StreamPlan stream_plan(int R) {
   p.splits = (R + p.per - 1) / p.per;
   return p;
 }
+
+// The candidate lists of a route and what it computes on the way to them:
+//   kSorted  (sorted-list scan)  cs | ci [Q][splits][KEEP]
+//   kTau     (threshold scheme)  pre-pass values [Q][S'][64] | cs | ci [Q][S][kTauCapSplit] | tau [Q] | cnt [Q][S]
+//   kStream  (stream route)      score matrix [Q][R] | cs | ci [Q][splits][KEEP]
+enum TopnRoute { kSorted, kTau, kStream };
+struct TopnLists {
+  float *scores, *cs, *tau;   // scores: the pre-pass values or the score matrix
+  int *ci, *cnt;
+  size_t bytes;
+};
+inline TopnLists topn_lists_at(void* base, int R, int Q, int bf, TopnRoute route) {
+  Carver c(base);
+  TopnLists l{};
+  if (route == kTau) {
+    const TauPlan t = tau_plan(R, Q);
+    l.scores = c.take((size_t)Q * t.pre_splits * 64);
+    l.cs = c.take((size_t)Q * t.main_splits * kTauCapSplit);
+    l.ci = c.take<int>((size_t)Q * t.main_splits * kTauCapSplit);
+    l.tau = c.take(Q);
+    l.cnt = c.take<int>((size_t)Q * t.main_splits);
+  } else {
+    if (route == kStream) l.scores = c.take((size_t)Q * R);
+    const int splits = route == kStream ? stream_plan(R).splits : topn_plan(R, Q, bf).splits;
+    l.cs = c.take((size_t)Q * splits * KEEP);
+    l.ci = c.take<int>((size_t)Q * splits * KEEP);
+  }
+  l.bytes = c.off;
+  return l;
+}
+// The scan's: the larger of its two modes where R allows both (use_tau) — which one a call takes
+// depends on whether it certifies, and the size query is not told.
+inline size_t topn_lists_bytes(int R, int Q, int bf) {
+  const size_t sorted = topn_lists_at(nullptr, R, Q, bf, kSorted).bytes;
+  const size_t tau = R >= kTauMinRefs ? topn_lists_at(nullptr, R, Q, bf, kTau).bytes : 0;
+  return tau > sorted ? tau : sorted;
+}
+
+// What follows the preparation in scl_topn_l2_cert and in the scan route of scl_topn_index_query:
+// scan (or pre-pass, thresholds, threshold scan) from the index block `x` into the candidate lists
+// at `lists` (topn_lists_bytes), then the float64 re-rank with the certificate.
+int topn_scan_rerank(const float* ref, int R, const float* query, int Q, int d, int n,
+                     int64_t idx_offset, int64_t* idx_out, double* dist_out,
+                     unsigned char* uncertified, double* bound_sq, const TopnIndex& x, void* lists,
+                     int bf, hipStream_t st) {
+  const TopnPlan p = topn_plan(R, Q, bf);
+  const bool tau_mode = use_tau(R, uncertified != nullptr, bf);
+  const TauPlan tp = tau_mode ? tau_plan(R, Q) : TauPlan{};
+  const TopnLists l = topn_lists_at(lists, R, Q, bf, tau_mode ? kTau : kSorted);
+  const void* scan_ref = bf ? (const void*)x.hi : ref;   // bf16x3 scans the planes
+  if (tau_mode) {
+    // pre-pass over every kTauStride-th tile (interleaved splits) -> tau_q -> threshold scan
+    TopnPlan pp;
+    pp.qtiles = tp.qtiles;
+    pp.refs_per_split = 0;                                   // interleaved
+    pp.splits = tp.pre_splits;
+    launch_scan_d<2>(d, bf, pp, scan_ref, x.lo, x.refnorm, R, query, Q, l.scores, (int*)nullptr, st,
+                     tau_stride() * tp.pre_splits, nullptr, nullptr, 0, tau_stride());
+    SCL_LAUNCH("topn_tau_kernel", topn_tau_kernel, dim3((Q + 3) / 4), dim3(256), 0, st, (const float*)l.scores, Q,
+               tp.pre_splits, l.tau);
+    pp.splits = tp.main_splits;
+    launch_scan_d<1>(d, bf, pp, scan_ref, x.lo, x.refnorm, R, query, Q, l.cs, l.ci, st, tp.main_splits,
+                     l.tau, l.cnt, kTauCapSplit, 1);
+  } else {
+    launch_scan_d<0>(d, bf, p, scan_ref, x.lo, x.refnorm, R, query, Q, l.cs, l.ci, st);
+  }
+  const TopnEps eps = topn_eps(d, bf);
+  const int M = tau_mode ? kTauCompact : p.splits * KEEP;
+  if (tau_mode) {
+    static SclDeviceOnce once;
+    scl_call_once(once, [] {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&topn_rerank_kernel<kTauCompact / 64, true>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
+    });
+    SCL_LAUNCH("topn_rerank_kernel<append>", (topn_rerank_kernel<kTauCompact / 64, true>), dim3((Q + 3) / 4),
+               dim3(256), rerank_lds_bytes(M), st, ref,
+               query, Q, d, tp.main_splits, n, idx_offset, (const float*)l.cs, (const int*)l.ci, idx_out, dist_out,
+               (const unsigned*)x.rmax_bits, eps.q, eps.r, uncertified, bound_sq,
+               (const int*)l.cnt, (const float*)l.tau, kTauCapSplit);
+    return scl_launch_status();
+  }
+  launch_rerank(ref, query, Q, d, p.splits, n, idx_offset, l.cs, l.ci, idx_out, dist_out, x.rmax_bits, eps,
+                uncertified, bound_sq, st);
+  return scl_launch_status();
+}
+
 inline bool topn_flags_ok(int flags) { return !(flags & ~SCL_TOPN_SCORE_BF16X3); }
 
 }  // namespace
 
+// workspace of the one-shot calls: index block | candidate lists
 extern "C" size_t scl_topn_l2_ex_workspace_bytes(int R, int Q, int d, int n, int flags) {
-  if (!topn_shape_ok(R, Q, d, n) || (flags & ~SCL_TOPN_SCORE_BF16X3)) return 0;
+  if (!topn_shape_ok(R, Q, d, n) || !topn_flags_ok(flags)) return 0;
   const int bf = flags & SCL_TOPN_SCORE_BF16X3;
-  return 256 + scl_round256((size_t)R * sizeof(float)) + topn_lists_bytes(R, Q, bf) +
-         topn_planes_bytes(R, d, bf);
+  return topn_index_at(nullptr, R, d, bf).bytes + topn_lists_bytes(R, Q, bf);
 }
 
 extern "C" size_t scl_topn_l2_workspace_bytes(int R, int Q, int d, int n) {
@@ -1435,41 +1458,18 @@ extern "C" int scl_topn_l2_cert(const float* ref, int R, const float* query, int
   if (!ref || !query || !idx_out || !dist_out || !workspace) return SCL_E_NULL;
   if ((uncertified == nullptr) != (bound_sq == nullptr)) return SCL_E_NULL;
   if (!topn_shape_ok(R, Q, d, n)) return SCL_E_SHAPE;
-  if (flags & ~SCL_TOPN_SCORE_BF16X3) return SCL_E_KIND;
+  if (!topn_flags_ok(flags)) return SCL_E_KIND;
   if (((uintptr_t)ref % 16) || ((uintptr_t)query % 16)) return SCL_E_SHAPE;
   if (!scl_aligned256(workspace) ||
       workspace_bytes < scl_topn_l2_ex_workspace_bytes(R, Q, d, n, flags))
     return SCL_E_WORKSPACE;
   const int bf = flags & SCL_TOPN_SCORE_BF16X3;
-  // workspace: norm-bound word | refnorm[R] | candidate lists | (bf16x3) the two planes
-  char* base = (char*)workspace;
-  unsigned* rmax_bits = (unsigned*)base;
-  base += 256;
-  float* refnorm = (float*)base;
-  base += scl_round256((size_t)R * sizeof(float));
-  char* lists = base;
-  base += topn_lists_bytes(R, Q, bf);
   hipStream_t st = (hipStream_t)stream;
-  if (uncertified) {
-    const hipError_t e = hipMemsetAsync(rmax_bits, 0, 16, st);
-    if (e != hipSuccess) return (int)e;
-  }
-  SCL_LAUNCH("refnorm_kernel", refnorm_kernel, dim3((R + 63) / 64), dim3(256), 0, st, ref, R, d,
-             refnorm, uncertified ? rmax_bits : (unsigned*)nullptr);
-  const void* scan_ref = ref;
-  const void* scan_lo = nullptr;
-  if (bf) {
-    u32x4* hi = (u32x4*)base;
-    base += scl_round256((size_t)R * d * sizeof(unsigned short));
-    u32x4* lo = (u32x4*)base;
-    const int64_t n8 = (int64_t)R * d / 8;
-    SCL_LAUNCH("ref_split_kernel", ref_split_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256),
-               0, st, ref, n8, hi, lo);
-    scan_ref = hi;
-    scan_lo = lo;
-  }
+  const TopnIndex x = topn_index_at(workspace, R, d, bf);
+  const hipError_t e = topn_prepare(x, ref, R, d, bf, uncertified != nullptr, st);
+  if (e != hipSuccess) return (int)e;
   return topn_scan_rerank(ref, R, query, Q, d, n, idx_offset, idx_out, dist_out, uncertified, bound_sq,
-                          rmax_bits, refnorm, scan_ref, scan_lo, lists, bf, st);
+                          x, (char*)workspace + x.bytes, bf, st);
 }
 
 extern "C" int scl_topn_l2_ex(const float* ref, int R, const float* query, int Q, int d, int n,
@@ -1487,11 +1487,10 @@ extern "C" int scl_topn_l2(const float* ref, int R, const float* query, int Q, i
 }
 
 // ---- the prepared index: what scl_topn_l2_cert computes before it scans, kept between calls ----
-// index block: norm-bound word (256 bytes) | refnorm[R] | (bf16x3) high plane | low plane
+// (the block: topn_index_at)
 extern "C" size_t scl_topn_index_bytes(int R, int d, int flags) {
   if (!topn_shape_ok(R, 1, d, 1) || !topn_flags_ok(flags)) return 0;
-  return 256 + scl_round256((size_t)R * sizeof(float)) +
-         topn_planes_bytes(R, d, flags & SCL_TOPN_SCORE_BF16X3);
+  return topn_index_at(nullptr, R, d, flags & SCL_TOPN_SCORE_BF16X3).bytes;
 }
 
 extern "C" int scl_topn_index_build(const float* ref, int R, int d, void* index, size_t index_bytes,
@@ -1499,33 +1498,18 @@ extern "C" int scl_topn_index_build(const float* ref, int R, int d, void* index,
   if (!ref || !index) return SCL_E_NULL;
   if (!topn_shape_ok(R, 1, d, 1) || ((uintptr_t)ref % 16)) return SCL_E_SHAPE;
   const int bf = flags & SCL_TOPN_SCORE_BF16X3;
-  if (!scl_aligned256(index) || index_bytes < scl_topn_index_bytes(R, d, bf)) return SCL_E_WORKSPACE;
+  const TopnIndex x = topn_index_at(index, R, d, bf);
+  if (!scl_aligned256(index) || index_bytes < x.bytes) return SCL_E_WORKSPACE;
   if (!topn_flags_ok(flags)) return SCL_E_KIND;
-  hipStream_t st = (hipStream_t)stream;
-  unsigned* rmax_bits = (unsigned*)index;
-  float* refnorm = (float*)((char*)index + 256);
-  const hipError_t e = hipMemsetAsync(rmax_bits, 0, 16, st);
-  if (e != hipSuccess) return (int)e;
-  SCL_LAUNCH("refnorm_kernel", refnorm_kernel, dim3((R + 63) / 64), dim3(256), 0, st, ref, R, d,
-             refnorm, rmax_bits);
-  if (bf) {
-    u32x4* hi = (u32x4*)((char*)refnorm + scl_round256((size_t)R * sizeof(float)));
-    u32x4* lo = (u32x4*)((char*)hi + scl_round256((size_t)R * d * sizeof(unsigned short)));
-    const int64_t n8 = (int64_t)R * d / 8;
-    SCL_LAUNCH("ref_split_kernel", ref_split_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256),
-               0, st, ref, n8, hi, lo);
-  }
-  return scl_launch_status();
+  const hipError_t e = topn_prepare(x, ref, R, d, bf, true, (hipStream_t)stream);
+  return e != hipSuccess ? (int)e : scl_launch_status();
 }
 
-// Q <= SCL_TOPN_STREAM_MAX_Q: score matrix [Q][R] | lists [Q][S][KEEP] x 2.  More queries: the
-// candidate lists of the scan (topn_lists_bytes) — norms and planes come from the index.
+// the candidate lists of the route (topn_lists_at) — norms and planes come from the index
 extern "C" size_t scl_topn_index_query_workspace_bytes(int R, int Q, int d, int n, int flags) {
   if (!topn_shape_ok(R, Q, d, n) || !topn_flags_ok(flags)) return 0;
   if (Q > SCL_TOPN_STREAM_MAX_Q) return topn_lists_bytes(R, Q, flags & SCL_TOPN_SCORE_BF16X3);
-  const StreamPlan sp = stream_plan(R);
-  return scl_round256((size_t)Q * R * sizeof(float)) +
-         2 * scl_round256((size_t)Q * sp.splits * KEEP * sizeof(float));
+  return topn_lists_at(nullptr, R, Q, 0, kStream).bytes;
 }
 
 extern "C" int scl_topn_index_query(const float* ref, int R, int d, const void* index,
@@ -1538,47 +1522,31 @@ extern "C" int scl_topn_index_query(const float* ref, int R, int d, const void* 
   if (!topn_shape_ok(R, Q, d, n)) return SCL_E_SHAPE;
   if (((uintptr_t)ref % 16) || ((uintptr_t)query % 16)) return SCL_E_SHAPE;
   const int bf = flags & SCL_TOPN_SCORE_BF16X3;
-  if (!scl_aligned256(index) || index_bytes < scl_topn_index_bytes(R, d, bf)) return SCL_E_WORKSPACE;
+  const TopnIndex x = topn_index_at(index, R, d, bf);   // read-only here
+  if (!scl_aligned256(index) || index_bytes < x.bytes) return SCL_E_WORKSPACE;
   if (!scl_aligned256(workspace) ||
       workspace_bytes < scl_topn_index_query_workspace_bytes(R, Q, d, n, bf))
     return SCL_E_WORKSPACE;
   if (!topn_flags_ok(flags)) return SCL_E_KIND;
   hipStream_t st = (hipStream_t)stream;
-  const unsigned* rmax_bits = (const unsigned*)index;
-  const float* refnorm = (const float*)((const char*)index + 256);
-  if (Q > SCL_TOPN_STREAM_MAX_Q) {
-    const void* scan_ref = ref;
-    const void* scan_lo = nullptr;
-    if (bf) {
-      scan_ref = (const char*)refnorm + scl_round256((size_t)R * sizeof(float));
-      scan_lo = (const char*)scan_ref + scl_round256((size_t)R * d * sizeof(unsigned short));
-    }
+  if (Q > SCL_TOPN_STREAM_MAX_Q)
     return topn_scan_rerank(ref, R, query, Q, d, n, idx_offset, idx_out, dist_out, uncertified,
-                            bound_sq, rmax_bits, refnorm, scan_ref, scan_lo, (char*)workspace, bf, st);
-  }
+                            bound_sq, x, workspace, bf, st);
   // stream route: always scores from the float32 rows (the score flag only sizes the index)
   const StreamPlan sp = stream_plan(R);
-  float* scores = (float*)workspace;
-  float* cs = (float*)((char*)workspace + scl_round256((size_t)Q * R * sizeof(float)));
-  int* ci = (int*)((char*)cs + scl_round256((size_t)Q * sp.splits * KEEP * sizeof(float)));
+  const TopnLists w = topn_lists_at(workspace, R, Q, 0, kStream);
   // one wave per 32-reference tile until the chip is full: 4 waves per CU at d = 256 (a wave holds
   // the query fragment and a tile: 332 registers), 8 at d = 128 (204), 12 at d = 64 (140), 16 at 32
   const int ntiles = (R + 31) / 32;
   const int max_wg = d == 256 ? 256 : (d == 128 ? 512 : (d == 64 ? 768 : 1024));
   const int wgs = (ntiles + 3) / 4 < max_wg ? (ntiles + 3) / 4 : max_wg;
-#define SCL_STREAM(D8)                                                                              \
-  SCL_LAUNCH("topn_stream_score_kernel", topn_stream_score_kernel<D8>, dim3(wgs), dim3(256), 0, st, \
-             ref, refnorm, R, query, Q, scores)
-  switch (d) {
-    case 32: SCL_STREAM(4); break;
-    case 64: SCL_STREAM(8); break;
-    case 128: SCL_STREAM(16); break;
-    default: SCL_STREAM(32); break;
-  }
-#undef SCL_STREAM
+  for_width(d, [&](auto d8) {
+    SCL_LAUNCH("topn_stream_score_kernel", topn_stream_score_kernel<decltype(d8)::value>, dim3(wgs),
+               dim3(256), 0, st, ref, (const float*)x.refnorm, R, query, Q, w.scores);
+  });
   SCL_LAUNCH("topn_stream_select_kernel", topn_stream_select_kernel, dim3((sp.splits + 3) / 4, Q),
-             dim3(256), 0, st, (const float*)scores, R, sp.splits, sp.per, cs, ci);
-  launch_rerank(ref, query, Q, d, sp.splits, n, idx_offset, cs, ci, idx_out, dist_out, rmax_bits,
+             dim3(256), 0, st, (const float*)w.scores, R, sp.splits, sp.per, w.cs, w.ci);
+  launch_rerank(ref, query, Q, d, sp.splits, n, idx_offset, w.cs, w.ci, idx_out, dist_out, x.rmax_bits,
                 topn_eps(d, 0), uncertified, bound_sq, st);
   return scl_launch_status();
 }

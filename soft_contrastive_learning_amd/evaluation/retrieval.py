@@ -16,6 +16,57 @@ MAX_N = 25          # what ONE kernel pass returns per query (32 nominated, 25 c
 SCORE_MODES = {'f32': L.TOPN_SCORE_F32, 'bf16x3': L.TOPN_SCORE_BF16X3}
 
 
+_WIDTHS = (32, 64, 128, 256)      # descriptor widths the kernels of csrc/topn.hip take
+
+
+def _pad_width(t, width=None):
+    """Rows zero-padded to ``width`` (default: the next one in ``_WIDTHS``); no distance changes."""
+    width = width or next(c for c in _WIDTHS if t.shape[1] <= c)
+    return t if t.shape[1] == width else torch.nn.functional.pad(t, (0, width - t.shape[1]))
+
+
+def _checked(ref, query, n, width=None):
+    """(ref, query) as contiguous float32 [R,d] / [Q,d] on a HIP device, with n in [1, R].
+    ``width``: of the rows a RetrievalIndex was given (its ``ref`` is those rows, padded)."""
+    L.require_device(ref, query)
+    query = query.float().contiguous()
+    if width is not None and (query.dim() != 2 or query.shape[1] != width):
+        raise ValueError("query %s must be [Q,%d]" % (tuple(query.shape), width))
+    if width is None:
+        ref = ref.float().contiguous()
+        if ref.dim() != 2 or query.dim() != 2 or ref.shape[1] != query.shape[1]:
+            raise ValueError("ref %s / query %s must be [R,d] / [Q,d]" % (tuple(ref.shape), tuple(query.shape)))
+    if n > ref.shape[0] or n < 1:
+        raise ValueError("n must be in [1, R], got n=%d R=%d" % (n, ref.shape[0]))
+    return ref, query
+
+
+def _sized(nbytes, r, q, d, n, hint=''):
+    if nbytes == 0:
+        raise ValueError("unsupported retrieval shape R=%d Q=%d d=%d n=%d%s" % (r, q, d, n, hint))
+    return nbytes
+
+
+def _run(ref, query, n, idx_offset, certify, stats, call):
+    """One kernel pass over ``ref`` [R, d in _WIDTHS], n <= MAX_N: pads the query to d, allocates the
+    outputs, has ``call(query, idx, dist, flag, bound)`` make the C call (flag, bound: None without
+    ``certify``) and resolves exactly the queries that the call could not certify."""
+    query = _pad_width(query, ref.shape[1])
+    q, dev = query.shape[0], ref.device
+    idx = torch.empty((q, n), dtype=torch.int64, device=dev)
+    dist = torch.empty((q, n), dtype=torch.float64, device=dev)
+    flag = torch.empty(q, dtype=torch.uint8, device=dev) if certify else None
+    bound = torch.empty(q, dtype=torch.float64, device=dev) if certify else None
+    call(query, idx, dist, flag, bound)
+    if certify:
+        bad = torch.nonzero(flag).reshape(-1)                      # (synchronises; usually empty)
+        if stats is not None:
+            stats['uncertified'] = int(bad.numel())
+        if bad.numel():
+            _resolve_exactly(ref, query, n, int(idx_offset), bad, bound, dist, idx)
+    return dist, idx
+
+
 def topn_l2(ref, query, n, idx_offset=0, score='f32', certify=True, stats=None):
     """ref [R,d], query [Q,d] float32 on a HIP device -> (dists [Q,n] float64 ascending,
     idx [Q,n] int64), like ``KDTree(ref).query(query, k=n, sort_results=True)``.
@@ -36,54 +87,25 @@ def topn_l2(ref, query, n, idx_offset=0, score='f32', certify=True, stats=None):
     lib = L.load()
     if score not in SCORE_MODES:
         raise ValueError("score must be one of %s, got %r" % (sorted(SCORE_MODES), score))
-    L.require_device(ref, query)
-    ref = ref.float().contiguous()
-    query = query.float().contiguous()
-    if ref.dim() != 2 or query.dim() != 2 or ref.shape[1] != query.shape[1]:
-        raise ValueError("ref %s / query %s must be [R,d] / [Q,d]" % (tuple(ref.shape),
-                                                                     tuple(query.shape)))
+    ref, query = _checked(ref, query, n)
     r, d = ref.shape
-    q = query.shape[0]
-    if n > r or n < 1:
-        raise ValueError("n must be in [1, R], got n=%d R=%d" % (n, r))
     if d > 256:
-        return _topn_wide(ref.contiguous(), query.contiguous(), n, idx_offset, certify, stats)
+        return _topn_wide(ref, query, n, idx_offset, certify, stats)
     if n > MAX_N:
         # evaluation/top-n.py:135 leaves --N free; one kernel pass certifies 25 per query
         return _topn_many(ref, query, n, idx_offset, score, stats)
-    if d not in (32, 64, 128, 256):
-        # zero-padding the feature axis leaves every distance unchanged
-        pad = next(c for c in (32, 64, 128, 256) if d <= c)
-        ref = torch.nn.functional.pad(ref, (0, pad - d))
-        query = torch.nn.functional.pad(query, (0, pad - d))
-        d = pad
-    flags = SCORE_MODES[score]
-    nbytes = lib.scl_topn_l2_ex_workspace_bytes(r, q, d, n, flags)
-    if nbytes == 0:
-        raise ValueError("unsupported retrieval shape R=%d Q=%d d=%d n=%d "
-                         "(d in {32,64,128,256}, n <= %d, n <= R)" % (r, q, d, n, MAX_N))
-    idx = torch.empty((q, n), dtype=torch.int64, device=ref.device)
-    dist = torch.empty((q, n), dtype=torch.float64, device=ref.device)
-    ws = L.workspace(nbytes, ref.device)
-    if not certify:
-        L.check(lib.scl_topn_l2_ex(L.ptr(ref), r, L.ptr(query), q, d, n, int(idx_offset),
-                                   L.ptr(idx), L.ptr(dist), L.ptr(ws), ws.numel(), flags,
-                                   L.stream_of(ref)))
-        return dist, idx
-    flag = torch.empty(q, dtype=torch.uint8, device=ref.device)
-    bound = torch.empty(q, dtype=torch.float64, device=ref.device)
-    L.check(lib.scl_topn_l2_cert(L.ptr(ref), r, L.ptr(query), q, d, n, int(idx_offset), L.ptr(idx),
-                                 L.ptr(dist), L.ptr(flag), L.ptr(bound), L.ptr(ws), ws.numel(),
-                                 flags, L.stream_of(ref)))
-    bad = torch.nonzero(flag).reshape(-1)                      # (synchronises; usually empty)
-    if stats is not None:
-        stats['uncertified'] = int(bad.numel())
-    if bad.numel():
-        _resolve_exactly(ref, query, n, int(idx_offset), bad, bound, dist, idx)
-    return dist, idx
+    ref = _pad_width(ref)
+    d, flags = ref.shape[1], SCORE_MODES[score]
 
-
-_WIDTHS = (32, 64, 128, 256)
+    def call(query, idx, dist, flag, bound):
+        q = query.shape[0]
+        nbytes = _sized(lib.scl_topn_l2_ex_workspace_bytes(r, q, d, n, flags), r, q, d, n,
+                        " (d in {32,64,128,256}, n <= %d, n <= R)" % MAX_N)
+        ws = L.workspace(nbytes, ref.device)
+        L.check(lib.scl_topn_l2_cert(L.ptr(ref), r, L.ptr(query), q, d, n, int(idx_offset), L.ptr(idx),
+                                     L.ptr(dist), L.ptr(flag), L.ptr(bound), L.ptr(ws), ws.numel(),
+                                     flags, L.stream_of(ref)))
+    return _run(ref, query, n, idx_offset, certify, stats, call)
 
 
 class RetrievalIndex:
@@ -117,10 +139,7 @@ class RetrievalIndex:
         if self.width > 256:
             self.ref = ref                             # (topn_l2's wide path; nothing to prepare)
             return
-        if self.width not in _WIDTHS:
-            pad = next(c for c in _WIDTHS if self.width <= c)
-            ref = torch.nn.functional.pad(ref, (0, pad - self.width))
-        self.ref = ref
+        self.ref = ref = _pad_width(ref)
         lib = L.load()
         r, d = ref.shape
         nbytes = lib.scl_topn_index_bytes(r, d, self._flags)
@@ -132,46 +151,26 @@ class RetrievalIndex:
 
     def query(self, query, n, certify=True, stats=None):
         """query [Q, width] float32 on the index's device -> (dist [Q,n] float64, idx [Q,n] int64)."""
-        L.require_device(query)
-        query = query.float().contiguous()
-        if query.dim() != 2 or query.shape[1] != self.width:
-            raise ValueError("query %s must be [Q,%d]" % (tuple(query.shape), self.width))
-        ref = self.ref
-        r, d = ref.shape
-        q = query.shape[0]
-        if n > r or n < 1:
-            raise ValueError("n must be in [1, R], got n=%d R=%d" % (n, r))
+        ref, query = _checked(self.ref, query, n, self.width)
         if self._index is None or n > MAX_N:
             if stats is not None:
                 stats['route'] = 'delegate'
             return topn_l2(ref[:, :self.width], query, n, self.idx_offset, self.score, certify, stats)
-        if d != self.width:
-            query = torch.nn.functional.pad(query, (0, d - self.width))
         lib = L.load()
-        nbytes = lib.scl_topn_index_query_workspace_bytes(r, q, d, n, self._flags)
-        if nbytes == 0:
-            raise ValueError("unsupported retrieval shape R=%d Q=%d d=%d n=%d" % (r, q, d, n))
-        if self._ws is None or self._ws.numel() < nbytes:
-            self._ws = L.workspace(nbytes, ref.device)
-        ws = self._ws
-        if stats is not None:
-            stats['route'] = 'stream' if q <= L.TOPN_STREAM_MAX_Q else 'scan'
-        idx = torch.empty((q, n), dtype=torch.int64, device=ref.device)
-        dist = torch.empty((q, n), dtype=torch.float64, device=ref.device)
-        flag = torch.empty(q, dtype=torch.uint8, device=ref.device) if certify else None
-        bound = torch.empty(q, dtype=torch.float64, device=ref.device) if certify else None
-        L.check(lib.scl_topn_index_query(L.ptr(ref), r, d, L.ptr(self._index), self._index.numel(),
-                                         L.ptr(query), q, n, self.idx_offset, L.ptr(idx), L.ptr(dist),
-                                         L.ptr(flag), L.ptr(bound), L.ptr(ws), ws.numel(),
-                                         self._flags, L.stream_of(ref)))
-        if not certify:
-            return dist, idx
-        bad = torch.nonzero(flag).reshape(-1)                      # (synchronises; usually empty)
-        if stats is not None:
-            stats['uncertified'] = int(bad.numel())
-        if bad.numel():
-            _resolve_exactly(ref, query, n, self.idx_offset, bad, bound, dist, idx)
-        return dist, idx
+        r, d = ref.shape
+
+        def call(query, idx, dist, flag, bound):
+            q = query.shape[0]
+            nbytes = _sized(lib.scl_topn_index_query_workspace_bytes(r, q, d, n, self._flags), r, q, d, n)
+            if self._ws is None or self._ws.numel() < nbytes:
+                self._ws = L.workspace(nbytes, ref.device)
+            if stats is not None:
+                stats['route'] = 'stream' if q <= L.TOPN_STREAM_MAX_Q else 'scan'
+            L.check(lib.scl_topn_index_query(L.ptr(ref), r, d, L.ptr(self._index), self._index.numel(),
+                                             L.ptr(query), q, n, self.idx_offset, L.ptr(idx), L.ptr(dist),
+                                             L.ptr(flag), L.ptr(bound), L.ptr(self._ws), self._ws.numel(),
+                                             self._flags, L.stream_of(ref)))
+        return _run(ref, query, n, self.idx_offset, certify, stats, call)
 
 
 _FILTER_CAP = 2048      # candidates within the bound kept per uncertified query

@@ -4,6 +4,7 @@ evaluation/retrieval.RetrievalIndex) and of the localiser built on it (evaluatio
 The defining property: ``RetrievalIndex(ref, off, score).query(q, n)`` equals
 ``retrieval.topn_l2(ref, q, n, off, score)`` in both tensors — and, so that the exact fallback
 cannot hide a broken scan, no query of the tie-free sets below may need it."""
+import functools
 import os
 
 import numpy as np
@@ -284,3 +285,117 @@ def test_command_writes_top_n_mains_pickle(dev, tmp_path, monkeypatch, capsys):
     assert len(want) == 1
     assert os.path.relpath(got, str(tmp_path / 'loc')) == os.path.relpath(want[0], str(tmp_path / 'top'))
     _assert_payload_equal(io.load_pickle(got), io.load_pickle(want[0]))
+
+
+# ---- the workspace and index-block layouts, between guard bands ----------------------------------------
+# Every C entry point below gets EXACTLY the bytes its size query returned, inside a larger buffer whose
+# 4096 bytes on either side must come back untouched; the lists must be the oracle's with nothing handed
+# to the exact fallback (the entry points are called directly: there is none), and a run on a buffer
+# full of 0xA5 must equal a run on a zeroed one — nothing is read before it is written.
+GUARD, FILL = 4096, 0xA5
+F32, BF = 0, 1
+
+
+@functools.lru_cache(maxsize=None)
+def _guard_sets(r, q, n=5):
+    """(ref, qry, oracle dists, oracle idx) at d = 32, computed once and shared read-only."""
+    ref, qry = U.retrieval_sets(r, q, 32)
+    out = (ref, qry) + TN.topn_kdtree(ref, qry, n)
+    for a in out:
+        a.setflags(write=False)
+    return out
+
+
+class _Guarded:
+    """``nbytes`` device bytes (``.inner``) between two guard bands, all filled with ``fill``."""
+
+    def __init__(self, dev, nbytes, fill):
+        self.fill = fill
+        self.buf = torch.full((nbytes + 2 * GUARD,), fill, dtype=torch.uint8, device=dev)
+        self.inner = self.buf[GUARD:GUARD + nbytes]
+        assert self.inner.data_ptr() % 256 == 0 and self.inner.numel() == nbytes
+
+    def assert_bands_intact(self):
+        torch.cuda.synchronize()
+        assert bool((self.buf[:GUARD] == self.fill).all()), "bytes before the block were written"
+        assert bool((self.buf[-GUARD:] == self.fill).all()), "bytes behind the block were written"
+
+
+def _outputs(dev, q, n, certify=True):
+    idx = torch.full((q, n), -7, dtype=torch.int64, device=dev)
+    dist = torch.full((q, n), -1.0, dtype=torch.float64, device=dev)
+    flag = torch.ones(q, dtype=torch.uint8, device=dev) if certify else None
+    bound = torch.full((q,), -1.0, dtype=torch.float64, device=dev) if certify else None
+    return idx, dist, flag, bound
+
+
+def _assert_oracle_lists(out, want_d, want_i):
+    idx, dist, flag, _ = out
+    if flag is not None:
+        assert int(flag.sum()) == 0, flag
+    np.testing.assert_array_equal(idx.cpu().numpy(), want_i)
+    np.testing.assert_allclose(dist.cpu().numpy(), want_d, rtol=1e-12, atol=0)
+
+
+def _assert_same(a, b):
+    for x, y in zip(a, b):
+        assert (x is None and y is None) or torch.equal(x, y)
+
+
+def _cert_between_bands(dev, r, q, flags, certify, fill, n=5):
+    from soft_contrastive_learning_amd import _lib as L
+    lib = L.load()
+    ref, qry, want_d, want_i = _guard_sets(r, q)
+    rt, qt = torch.tensor(ref, device=dev), torch.tensor(qry, device=dev)
+    ws = _Guarded(dev, lib.scl_topn_l2_ex_workspace_bytes(r, q, 32, n, flags), fill)
+    out = _outputs(dev, q, n, certify)
+    L.check(lib.scl_topn_l2_cert(L.ptr(rt), r, L.ptr(qt), q, 32, n, 0, L.ptr(out[0]), L.ptr(out[1]),
+                                 L.ptr(out[2]), L.ptr(out[3]), L.ptr(ws.inner), ws.inner.numel(), flags,
+                                 L.stream_of(rt)))
+    ws.assert_bands_intact()
+    _assert_oracle_lists(out, want_d, want_i)
+    return out
+
+
+# 1000: the sorted-list scan, refnorm[R] not a multiple of 64 floats.  32771: just above the 32768 from
+# which a certified call uses the threshold scheme's layout (pre | cs | ci | tau | cnt).
+@pytest.mark.parametrize("flags", [F32, BF])
+@pytest.mark.parametrize("r,q", [(1000, 33), (32771, 40)])
+def test_one_shot_workspace_between_guard_bands(dev, r, q, flags):
+    _assert_same(_cert_between_bands(dev, r, q, flags, True, FILL),
+                 _cert_between_bands(dev, r, q, flags, True, 0))
+
+
+def test_one_shot_workspace_between_guard_bands_without_certificate(dev):
+    _assert_same(_cert_between_bands(dev, 1000, 33, BF, False, FILL),
+                 _cert_between_bands(dev, 1000, 33, BF, False, 0))
+
+
+def _index_between_bands(dev, flags, fill, r=32771, n=5):
+    """scl_topn_index_build into a guarded block, then a stream (Q = 8) and a scan (Q = 40) query of it,
+    each with a guarded workspace."""
+    from soft_contrastive_learning_amd import _lib as L
+    lib = L.load()
+    ref, qry, want_d, want_i = _guard_sets(r, 40)
+    rt, qt = torch.tensor(ref, device=dev), torch.tensor(qry, device=dev)
+    index = _Guarded(dev, lib.scl_topn_index_bytes(r, 32, flags), fill)
+    L.check(lib.scl_topn_index_build(L.ptr(rt), r, 32, L.ptr(index.inner), index.inner.numel(), flags,
+                                     L.stream_of(rt)))
+    index.assert_bands_intact()
+    outs = []
+    for q in (8, 40):
+        ws = _Guarded(dev, lib.scl_topn_index_query_workspace_bytes(r, q, 32, n, flags), fill)
+        out = _outputs(dev, q, n)
+        L.check(lib.scl_topn_index_query(L.ptr(rt), r, 32, L.ptr(index.inner), index.inner.numel(), L.ptr(qt), q,
+                                         n, 0, L.ptr(out[0]), L.ptr(out[1]), L.ptr(out[2]), L.ptr(out[3]),
+                                         L.ptr(ws.inner), ws.inner.numel(), flags, L.stream_of(rt)))
+        ws.assert_bands_intact()
+        index.assert_bands_intact()
+        _assert_oracle_lists(out, want_d[:q], want_i[:q])
+        outs += out
+    return outs
+
+
+@pytest.mark.parametrize("flags", [F32, BF])
+def test_index_block_and_query_workspaces_between_guard_bands(dev, flags):
+    _assert_same(_index_between_bands(dev, flags, FILL), _index_between_bands(dev, flags, 0))

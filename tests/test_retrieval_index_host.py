@@ -66,6 +66,65 @@ def test_size_queries(lib):
                 - lib.scl_topn_index_bytes(r, d, F32))
 
 
+# What the size queries returned BEFORE the layouts were folded into one description each (evaluated on
+# that commit's build): the fold may not move a byte.  The NetVLAD rows are for 256 CUs — the count
+# the library assumes without a device, and the MI355X's.
+_SIZE_QS = (1, 32, 33, 130)
+# (R, d, flags): (index_bytes, then per Q of _SIZE_QS: (l2_ex_workspace_bytes, index_query_workspace_bytes))
+_TOPN_SIZES = {
+    (25, 32, 0): (512, (1024, 768), (8704, 11520), (9216, 8704), (33792, 33280)),
+    (25, 32, 1): (4096, (4608, 768), (12288, 11520), (12800, 8704), (37376, 33280)),
+    (25, 256, 0): (512, (1024, 768), (8704, 11520), (9216, 8704), (33792, 33280)),
+    (25, 256, 1): (26112, (26624, 768), (34304, 11520), (34816, 8704), (59392, 33280)),
+    (1000, 32, 0): (4352, (4864, 4608), (12544, 136192), (13056, 8704), (37632, 33280)),
+    (1000, 32, 1): (132352, (132864, 4608), (140544, 136192), (141056, 8704), (165632, 33280)),
+    (1000, 256, 0): (4352, (4864, 4608), (12544, 136192), (13056, 8704), (37632, 33280)),
+    (1000, 256, 1): (1028352, (1028864, 4608), (1036544, 136192), (1037056, 8704), (1061632, 33280)),
+    (32767, 32, 0): (131328, (139520, 139264), (393472, 4456448), (401664, 270336), (1196288, 1064960)),
+    (32767, 32, 1): (4325632, (4333824, 139264), (4587776, 4456448), (4595968, 270336), (5390592, 1064960)),
+    (32767, 256, 0): (131328, (139520, 139264), (393472, 4456448), (401664, 270336), (1196288, 1064960)),
+    (32767, 256, 1): (33684736, (33692928, 139264), (33946880, 4456448), (33955072, 270336), (34749696, 1064960)),
+    (32768, 32, 0): (131328, (166656, 139264), (1249792, 4456448), (1284864, 1153536), (4674816, 4543488)),
+    (32768, 32, 1): (4325632, (4360960, 139264), (5444096, 4456448), (5479168, 1153536), (8869120, 4543488)),
+    (32768, 256, 0): (131328, (166656, 139264), (1249792, 4456448), (1284864, 1153536), (4674816, 4543488)),
+    (32768, 256, 1): (33685760, (33721088, 139264), (34804224, 4456448), (34839296, 1153536), (38229248, 4543488)),
+    (100003, 32, 0): (400384, (435712, 408320), (1518848, 13062656), (1553920, 1153536), (4943872, 4543488)),
+    (100003, 32, 1): (13200896, (13236224, 408320), (14319360, 13062656), (14354432, 1153536), (17744384, 4543488)),
+    (100003, 256, 0): (400384, (435712, 408320), (1518848, 13062656), (1553920, 1153536), (4943872, 4543488)),
+    (100003, 256, 1): (102803456, (102838784, 408320), (103921920, 13062656), (103956992, 1153536),
+                       (107346944, 4543488)),
+}
+_NETVLAD_SIZES = {    # (B, N): (fwd_workspace_bytes, bwd_workspace_bytes)
+    (1, 1): (1061120, 2370304),
+    (2, 37): (1746176, 3447296),
+    (24, 1200): (42818560, 53104128),
+    (144, 300): (107555584, 164902656),
+}
+
+
+def test_sizes_are_those_of_the_hand_carved_layouts(lib):
+    for (r, d, flags), (index_bytes, *per_q) in _TOPN_SIZES.items():
+        assert lib.scl_topn_index_bytes(r, d, flags) == index_bytes, (r, d, flags)
+        for q, (l2_ws, query_ws) in zip(_SIZE_QS, per_q):
+            n = min(25, r)
+            assert lib.scl_topn_l2_ex_workspace_bytes(r, q, d, n, flags) == l2_ws, (r, q, d, flags)
+            assert lib.scl_topn_index_query_workspace_bytes(r, q, d, n, flags) == query_ws, (r, q, d, flags)
+    for (b, n), (fwd, bwd) in _NETVLAD_SIZES.items():
+        assert lib.scl_netvlad_fwd_workspace_bytes(b, n) == fwd, (b, n)
+        assert lib.scl_netvlad_bwd_workspace_bytes(b, n) == bwd, (b, n)
+
+
+def test_one_shot_workspace_is_index_block_plus_scan_lists(lib):
+    """scl_topn_l2_cert's workspace = index block | candidate lists, and the scan route of
+    scl_topn_index_query needs exactly those lists."""
+    for r, d, flags in _TOPN_SIZES:
+        for q in (33, 130):
+            n = min(25, r)
+            assert (lib.scl_topn_index_query_workspace_bytes(r, q, d, n, flags)
+                    == lib.scl_topn_l2_ex_workspace_bytes(r, q, d, n, flags)
+                    - lib.scl_topn_index_bytes(r, d, flags)), (r, q, d, flags)
+
+
 def _p(v):
     return ctypes.c_void_p(v)
 
