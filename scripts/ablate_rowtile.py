@@ -6,6 +6,9 @@ Runs the production kernel and its seven diagnostic variants interleaved in ONE 
 duration of each.  Variant bits: 1 = no epilogue stores, 2 = no x loads, 4 = no operand
 staging / barriers.  The variants compute garbage; only their timing is meaningful.
 
+The map is float32: that is where rowtile16_kernel<ASSIGN> is the production kernel, so variant
+0 has its row (a bf16 map takes the eight-wave fused kernels under variant 0).
+
     python scripts/ablate_rowtile.py [--batch 24] [--rounds 15]
 """
 import argparse
@@ -37,7 +40,7 @@ def main():
     lib = _lib.load()
     dev = torch.device('cuda:0')
     b, n = args.batch, 1200
-    x = torch.tensor(U.feature_map(b, n, seed=5), device=dev).bfloat16().reshape(b, 1, n, 512)
+    x = torch.tensor(U.feature_map(b, n, seed=5), device=dev).reshape(b, 1, n, 512)
     w, c = U.vlad_params()
     wt, ct = torch.tensor(w, device=dev), torch.tensor(c, device=dev)
     times = {v: [] for v in NAMES}

@@ -5,15 +5,17 @@
 // by netvlad_tf.layers.netVLAD(x, 64) (external, restated in oracle/netvlad_np.py).
 // The TF graph materialises the 5-D tensor [B,H',W',D,K] (157 MB per 640x480 image)
 // in forward and again in autodiff; here nothing larger than [B,N,64] is ever written.
-//
-// Every contraction runs on the f32-input matrix cores (v_mfma_f32_16x16x4_f32 for the
-// location-tile kernels, v_mfma_f32_32x32x2_f32 for the aggregation): exact f32 (bitwise a
-// k-ordered fmaf chain), so the governing roofline is the 157.3 TF f32 MFMA peak, not HBM
-// (SURVEY.md H1).  Linearity is used to keep x raw:
+// Linearity is used to keep x raw in both pipelines:
 //   s[n,k] = rn[n] * sum_d x[n,d] W[d,k],      rn[n] = rsqrt(max(sum_d x^2, 1e-12))
 //   V[d,k] = sum_n (a[n,k] rn[n]) x[n,d] + C[d,k] * sum_n a[n,k]
 //
-// Forward kernels
+// TWO pipelines, chosen by the feature map's type at the front door (the end of this file; ONE
+// VladPlan per call, "plan and workspaces" below).  Kernels in launch order:
+//
+// float32 map: the float32-MFMA pipeline (vlad_f32_forward / vlad_f32_backward).  Every contraction
+// on the f32-input matrix cores (v_mfma_f32_16x16x4_f32 for the location-tile kernels,
+// v_mfma_f32_32x32x2_f32 for the aggregation): exact f32 (bitwise a k-ordered fmaf chain), so the
+// governing roofline is the 157.3 TF f32 MFMA peak, not HBM.
 //   transpose_w_kernel         W[512,64] -> Wt[64,512] (source of the LDS operand image)
 //   rowtile16_kernel<ASSIGN>   per 16-location tile: x.W against a double-buffered LDS image
 //                              of Wt, row norms from the same x loads, softmax over K by
@@ -21,18 +23,39 @@
 //   aggregate_kernel           per (image, 64-channel tile, location split): x^T.(a rn),
 //                              4 waves along n, LDS tree reduce -> partial slabs
 //   finish_sum/norm_kernel     slabs + C*asum, intra-norm over D, global norm -> out
-// Backward kernels
-//   bwd_dots/bwd_du_kernel     grad through both norms (closed form from four column dots)
-//                              -> dU (both layouts, + bf16 planes), c.dU
+//   -- backward: vlad_bwd_prologue_kernel (grad through both norms -> dU, dU^T, c.dU),
 //   rowtile16_kernel<DASSIGN>  x.dU[b] -> d a -> softmax backward -> ds, <dxhat,xhat>
 //   aggregate_kernel           x^T.(ds rn) -> per-image dW slabs
 //   dx16_kernel                [a | ds].[dU | W]^T and the l2-norm Jacobian -> grad_x
 //   wgrad_finish_kernel        sums over the batch -> grad_w, grad_c
+//   Workspace: FwdWs wt, part, colsum, colsq, vlad, assign, rnorm; BwdWs du, dut, cdu, ds, rowdot, wpart.
+//
+// bf16 map (the training step, inference; bench.py's NETVLAD_FWD / NETVLAD_BWD): the eight-wave
+// fused pipeline (vlad_bf16_forward / vlad_bf16_backward), ONE pass over x per direction on
+// v_mfma_f32_16x16x32_bf16, every float32 operand as VF_NPL = 2 bf16 planes.
+//   vlad_planes_kernel         only when the caller brought no plane images of W
+//   vlad_fwd8_kernel<SAVE>     per (image, location slice): logits, softmax, aggregation -> a, rn,
+//                              the slice's slab and its column sums of a
+//   vlad_finish_kernel         slabs + C*asum, both norms -> out, the saved pre-norm VLAD
+//   -- or (VladPlan::fin, inference from 144 images) vlad_fwd8_kernel<false, false, true> alone
+//   -- backward: vlad_planes_kernel (as above), vlad_bwd_prologue_kernel (-> dU, its two register images, c.dU),
+//   vlad_bwd8_kernel           x.dU[b], softmax backward, x^T.(ds rn) -> ds, <dxhat,xhat>, dW slabs
+//   vlad_dx_kernel             grad_x; in its tail the sums over slabs and images -> grad_w, grad_c
+//   Workspace: FwdWs part, colsum, trash, vlad, wplanes, gran, stamps; BwdWs du, cdu, ds, rowdot,
+//   wpart, trash, duimg, dximg, wdximg, stamps.  No logits are written or read (save_logit may be NULL).
+//
+// The four-wave ancestors of the fused kernels and every other kernel only a diagnostic variant
+// reaches live in netvlad_diag.hip, with the comments that describe them.
 #include <mutex>
 #include <type_traits>
 
 #include "scl_common.h"
 #include "vlad_planes.h"
+
+__global__ __launch_bounds__(256) void vlad_planes_kernel(const float* __restrict__ w,
+                                                          unsigned short* __restrict__ planes) {
+  vlad_planes_wave(w, planes, planes + VP_FWD_ELEMS, 4 * blockIdx.x + (threadIdx.x >> 6), threadIdx.x & 63);
+}
 
 namespace {
 
@@ -496,65 +519,18 @@ __global__ __launch_bounds__(256) void aggregate_kernel(const void* __restrict__
   }
 }
 
-// =======================================================================================
-// Fused kernels for bf16 feature maps (round 3): ONE pass over x per direction.
-//
-// vlad_fwd_kernel: soft-assignment AND aggregation of one (image, location slice) per
-// workgroup.  What bounded the two-kernel form (rowtile_ring + aggregate16b) was bytes per CU,
-// not matrix or LDS time: every 128 locations re-streamed the 196 KB operand image of W
-// through the CU's L2 -> LDS path (12-13 B per cycle and CU), and x and the assignments made a
-// second trip for the aggregation.  Here
-//   * W^T lives in REGISTERS for the whole kernel: wave w owns clusters 16 w .. 16 w + 15 as
-//     three bf16 planes (16 k-steps x 3 planes x 4 registers = 192 per lane);
-//   * the partial VLAD of the slice lives in REGISTERS too: V[512 channels][the wave's 16
-//     clusters] = 32 accumulator tiles = 128 per lane (one wave per SIMD, 512-register budget);
-//   * only x moves: 32-location steps through a 3-stage LDS ring filled by LDS-DMA (32 KB per
-//     stage, two stages in flight), each x tile consumed twice while it is in LDS — row-wise
-//     (ds_read_b128) as the B operand of the logits, column-wise (ds_read_b64_tr_b16) as the A
-//     operand of the aggregation.  Unit u(loc, c) = 64 loc + (c ^ (loc & 15)) (c = 16-byte
-//     chunk of the row) makes both kinds of read conflict-free (scripts/lds_conflicts.py); the
-//     swizzle sits on the DMA's source address.
-// The logits run with the operands SWAPPED (S^T = W^T x^T), so a lane holds four consecutive
-// clusters of ONE location: the softmax needs two cross-lane steps instead of four per value, and
-// a / logits leave as 16-byte stores.  Row norms come from the matrix cores as well: x_frag is
-// both operands of one more MFMA per k-step, whose diagonal is sum_d x^2 (bf16 products are
-// exact in float32).  The softmax over the 64 clusters spans the four waves: each wave
-// publishes (max, sum exp) of its 16 clusters per location, ONE barrier, then every wave
-// finishes a = e^(s - m_w) e^(m_w - M) / total.  The coefficients a * rn then go through a
-// per-wave [32 loc][16 cl] x 3-plane LDS image (8-byte writes, transposed reads) to become
-// the B operand of the aggregation — no round trip through HBM, no second read of x.
-// Contraction index k = 8 g + e of the aggregation is location pi(k) of the step (see vf_pi):
-// any permutation works as long as both operands use it, and this one keeps the transposed
-// reads of the x tile conflict-free.
-// Output: a, logits, rn (training), the slice's slab in accumulator order and its column sums
-// of a.  grid (S slices, B images), block 256, one workgroup per CU.
 constexpr int VF_STEP = 32;                       // locations per step
 constexpr int VF_STAGE = VF_STEP * D * 2;         // bytes per x stage (32,768)
 constexpr int VF_NST = 3;
-constexpr int VF_AHEAD = 6;                      // A fragments in flight in the aggregation (<= 7)
 constexpr int VF_CFLD = 48;                       // bytes per coefficient row (16 clusters + pad)
 constexpr int VF_NPL = 2;                         // bf16 planes of the float32 operands (W^T, dU^T,
                                                   // a rn, ds rn): o = o1 + o2 + O(2^-17 |o|); 3 = exact
 constexpr int VF_CFPL = VF_STEP * VF_CFLD;        // bytes per plane (1,536)
 constexpr int VF_CF = VF_NPL * VF_CFPL;           // bytes per wave
-constexpr int VF_EXCH = 4 * VF_STEP * 16;         // [wave][location][up to 4 floats]
-constexpr size_t kVladFusedLds = (size_t)VF_NST * VF_STAGE + 4 * VF_CF + VF_EXCH;   // 118,784 B
-
 // location (within the step) of contraction index k = 8 g + e
 __host__ __device__ constexpr int vf_pi(int g, int e) {
   return 16 * (g >> 1) + 2 * (4 * (g & 1) + (e & 3)) + (e >> 2);
 }
-
-// W [512][64] float32 -> register images of the fused kernels: 16-byte unit
-// ((w * 16 + s) * VF_NPL + plane) * 64 + lane  holds  W_plane[ch 32 s + 8 g + e][cluster 16 w + i],
-// e = 0..7, for lane = 16 g + i: wave w loads its 48 fragments with coalesced 16-byte loads.
-// VF_WREP identical copies, workgroups take copy (slice index) % VF_WREP.  (Tried with 4: every
-// workgroup reads this image in the same order at the same time, but the prologue — 8.3 k cycles
-// for 192 KB + 64 KB of x — did not move: it runs at the CU's L2 -> register rate, 30 B per cycle,
-// not into a hot L2 channel.  Left at 1.)
-// grid (64, VF_WREP), block 64 (block = (w, s)).
-constexpr int VF_WREP = 1;
-constexpr int VF_WIMG = VF_NPL * D * K;           // bf16 elements per copy
 
 // v + (v of the lane 16 / 32 away): one register swap between 16-lane rows / 32-lane halves
 // (v_permlane16_swap_b32 / v_permlane32_swap_b32) and one add — no trip through the LDS crossbar
@@ -581,22 +557,10 @@ __device__ __forceinline__ u32x4 vf_ldsr128(unsigned byte) { return *(const lds_
 __device__ __forceinline__ void vf_ldsw64(unsigned byte, unsigned lo, unsigned hi) {
   *(lds_u32x2*)(size_t)byte = u32x2{lo, hi};
 }
-// counted wait on the wave's vector-memory queue (immediate operand: a small switch)
-__device__ __forceinline__ void vf_wait_vm(int n) {
-  switch (n) {
-    case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-    case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-    case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-    case 11: asm volatile("s_waitcnt vmcnt(11)" ::: "memory"); break;
-    case 13: asm volatile("s_waitcnt vmcnt(13)" ::: "memory"); break;
-    default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-  }
-}
 
 struct VladFwdArgs {
   const unsigned short* x;      // [B][N][512] bf16
-  const unsigned short* wimg;   // vlad_split_w_kernel's image
+  const unsigned short* wimg;   // vlad_planes_kernel's image
   int N, pre_l2, steps_per_slice;
   float* assign;                // [B][N][64] or NULL (inference)
   float* logit;                 // [B][N][64] or NULL
@@ -617,18 +581,9 @@ struct VladFwdArgs {
 };
 
 
-// vlad_bwd_kernel: the backward twin of vlad_fwd_kernel — x.dU[b], the softmax backward and the
-// weight-gradient aggregation x^T.(ds rn) of one (image, location slice) in one pass over x.
-// The image's dU^T sits in registers (bwd_du_kernel writes it as the same register image the
-// forward uses for W^T), the slice's partial dW in the accumulators.  Per location the softmax
-// backward needs sums over all 64 clusters, i.e. over the four waves; every wave publishes four
-// partial sums over its 16 clusters,
-//   P1 = sum a da,  P2 = sum a t,  P3 = sum a da lg,  P4 = sum a lg     (t = xhat.dU, da = t + c.dU)
-// and after ONE barrier   dot = sum P1,   <dxhat, xhat> = sum P2 + sum P3 - dot sum P4
-// (= sum_k a t + ds lg with ds = a (da - dot)).  Outputs: ds, rowdot, the slice's dW slab.
 struct VladBwdArgs {
   const unsigned short* x;      // [B][N][512] bf16
-  const unsigned short* duimg;  // [B] register images of dU^T (bwd_du_kernel)
+  const unsigned short* duimg;  // [B] register images of dU^T (vlad_bwd_prologue_kernel)
   const float* a;               // [B][N][64] saved assignments
   const float* lg;              // [B][N][64] saved logits
   const float* rn;              // [B][N]
@@ -640,17 +595,11 @@ struct VladBwdArgs {
   float* trash;
 };
 
-
 // =======================================================================================
-// Round 4: the two fused kernels with EIGHT waves per workgroup (two per SIMD).
-//
-// What the stamps of the four-wave kernels showed (profiles/r03/vlad_stamps_fwd.txt): a 32-location
-// step takes 6.4 k cycles, of which 160 MFMAs x 16 cycles = 2.6 k are matrix work; the rest is the
-// softmax / coefficient arithmetic and its cross-lane and LDS traffic (2.1 k), LDS latency in front
-// of the aggregation's products, and two barriers — all strictly one after the other, because a
-// wave that owns a SIMD alone issues in order: a vector instruction costs it 4 cycles (2 with a
-// second wave on the SIMD) and nothing runs while it waits.  Here wave (w, h) = clusters 16 w .. +15
-// x CHANNEL HALF h:
+// Round 4: the two fused kernels with EIGHT waves per workgroup (two per SIMD).  (What the stamps of
+// the four-wave kernels showed, and the design the two share — W^T in registers, the LDS ring and its
+// swizzle, the swapped-operand softmax: netvlad_diag.hip, in front of vlad_fwd_kernel.)  Here wave
+// (w, h) = clusters 16 w .. +15 x CHANNEL HALF h:
 //   * registers per wave halve (W^T fragments 64, VLAD accumulators 64), so two waves fit a SIMD:
 //     one wave's LDS round trips, waits and vector work hide behind the other's, and vector
 //     instructions issue at twice the rate;
@@ -665,7 +614,8 @@ struct VladBwdArgs {
 //     image (rows 16 h .. of it written by wave (w, h)).
 // Four barriers per step (stage landed | partials exchanged | (max, sum exp) exchanged |
 // coefficients written) instead of two; x staging, LDS images, slab layout, saved outputs and the
-// W^T register image are the four-wave kernel's (vlad_fwd_kernel), so every consumer is unchanged.
+// W^T register image are the four-wave kernel's (vlad_fwd_kernel, netvlad_diag.hip), so every consumer
+// is unchanged.
 // scl_debug_set_variant(922) runs the four-wave kernels (same-box A/B).
 constexpr int V8_XL = 8 * 64 * 16;               // partial logits for the partner: [wave][lane] x 16 B
 constexpr int V8_PN = 2 * 16 * 8 * 4;            // norm partials [tile][location][wave]
@@ -1015,10 +965,16 @@ __global__ __launch_bounds__(512) void vlad_fwd8_kernel(VladFwdArgs p) {
 #undef VF_STAMP
 }
 
-// vlad_bwd8_kernel: the backward twin with eight waves (see vlad_bwd_kernel for the algebra):
-// wave (w, h) contracts x with the image's dU^T over its channel half, hands the other tile's
-// partial to its partner, runs the softmax backward of its 16 locations (partial sums over its 16
-// clusters exchanged across the four cluster groups) and aggregates its 16 channel tiles of dW.
+// vlad_bwd8_kernel: the backward twin with eight waves — x.dU[b], the softmax backward and the
+// weight-gradient aggregation x^T.(ds rn) of one (image, location slice) in one pass over x.
+// Wave (w, h) contracts x with the image's dU^T over its channel half (dU^T sits in registers:
+// vlad_bwd_prologue_kernel writes it as the same register image the forward uses for W^T), hands the
+// other tile's partial to its partner, runs the softmax backward of its 16 locations and aggregates
+// its 16 channel tiles of dW.  Per location the softmax backward needs sums over all 64 clusters,
+// i.e. over the four cluster groups; every wave publishes four partial sums over its 16 clusters,
+//   P1 = sum a da,  P2 = sum a t,  P3 = sum a da lg,  P4 = sum a lg     (t = xhat.dU, da = t + c.dU)
+// and after ONE barrier   dot = sum P1,   <dxhat, xhat> = sum P2 + sum P3 - dot sum P4
+// (= sum_k a t + ds lg with ds = a (da - dot)).  Outputs: ds, rowdot, the slice's dW slab.
 __global__ __launch_bounds__(512) void vlad_bwd8_kernel(VladBwdArgs p) {
   extern __shared__ __attribute__((aligned(1024))) unsigned char vf_lds[];
   const int lane = threadIdx.x & 63;
@@ -1211,7 +1167,6 @@ __global__ __launch_bounds__(512) void vlad_bwd8_kernel(VladBwdArgs p) {
 #pragma unroll
   for (int c = 0; c < 16; ++c) slab[c * 64] = accv[c];
 }
-constexpr int VW_GROUPS = 8;
 
 // ---------------------------------------------------------------------------------------
 // Sibling exchange inside a launch (round 4).  The forward finish and the backward prologue each
@@ -1227,7 +1182,7 @@ constexpr int VW_GROUPS = 8;
 // The spin is BOUNDED: a workgroup whose siblings are not resident in time computes their scalars
 // itself with the same routine (same instruction sequence, same bits) — correctness never depends on
 // co-residency or dispatch order, only speed does.  Granules are zeroed by the kernel in front
-// (forward: vlad_fwd_kernel, same call) or kept zero between calls (backward: row 513 of save_vlad,
+// (forward: vlad_fwd8_kernel, same call) or kept zero between calls (backward: row 513 of save_vlad,
 // zeroed by the forward pass and re-zeroed by the last workgroup of the prologue to leave).
 typedef unsigned long long gran_t;
 typedef __attribute__((address_space(1))) gran_t* gran_gptr;
@@ -1250,9 +1205,6 @@ __device__ __forceinline__ bool gran_sweep(gran_t* g, int n, int limit, float& v
   }
 }
 constexpr int kSpinLimit = 20000;          // x (poll + s_sleep 8) ~ several ms: never reached in practice
-// scl_debug_set_variant(921): no patience at all — every workgroup that does not find its siblings'
-// granules at the first poll takes the self-computing path (tests: same bits either way)
-inline int spin_limit() { return scl_variant() == 921 ? 0 : kSpinLimit; }
 
 // vlad_finish_kernel: everything behind the fused forward kernel in ONE launch — U = sum of the
 // image's slice slabs + C * asum, the intra-normalisation per cluster, the global normalisation,
@@ -1393,12 +1345,12 @@ __global__ __launch_bounds__(256) void vlad_finish_kernel(VladFinishArgs p) {
   if (c == 0 && t < K) reinterpret_cast<unsigned*>(vrow)[(D + 1) * K + t] = 0u;   // the backward's sync words
 }
 
-// vlad_bwd_prologue_kernel: the gradient through both normalisations (bwd_dots_kernel's comment
-// has the closed form) in ONE launch, 8 workgroups per image, workgroup c = clusters 8 c .. + 7 of
+// vlad_bwd_prologue_kernel: the gradient through both normalisations (closed form: the comment in
+// front of dx16_kernel) in ONE launch, 8 workgroups per image, workgroup c = clusters 8 c .. + 7 of
 // all 512 channels: A_k, col_k, Bc_k, Dc_k are local; the two sums over all clusters, tot = sum_k
 // q_k^2 col_k and S1 = sum_k q_k A_k, travel as granules (above).  Thread (ip, r): cluster 8 c + ip,
-// 8-channel chunks r and r + 32; its 16 values of U and grad_out stay in registers for dU.  Outputs as
-// bwd_du_kernel: dU float32 [d][k] (+ transposed for the float32-MFMA kernels), c.dU, and for bf16
+// 8-channel chunks r and r + 32; its 16 values of U and grad_out stay in registers for dU.  Outputs:
+// dU float32 [d][k] (+ transposed for the float32-MFMA kernels), c.dU, and for bf16
 // feature maps the two register images of the fused kernels (duimg straight from the registers —
 // 8 consecutive channels of a cluster are one thread's — dximg through a [512][8] LDS tile).
 struct VladProArgs {
@@ -1861,7 +1813,7 @@ struct VladDxArgs {
   const float* ds;              // [B][N][64]
   const float* rn;              // [B][N]
   const float* rowdot;          // [B][N]
-  const unsigned short* dximg;  // [B] register images of dU (bwd_du_kernel)
+  const unsigned short* dximg;  // [B] register images of dU (vlad_bwd_prologue_kernel)
   const unsigned short* wdximg; // the same image of W
   int N, pre_l2, steps_per_slice;
   unsigned short* gx;           // [B][N][512] bf16
@@ -1869,7 +1821,7 @@ struct VladDxArgs {
   unsigned long long* stamps;
   unsigned short* trash;        // 64 x 16 bytes for the stores of rows past the end
   // tail (wslab != NULL): this workgroup's share of the two parameter gradients
-  const float* wslab;           // [nslab][8192 units][4]: vlad_bwd_kernel's dW slabs (complete: it
+  const float* wslab;           // [nslab][8192 units][4]: vlad_bwd8_kernel's dW slabs (complete: it
   int nslab;                    //   ran in front of this kernel)
   const float* du;              // [B][512][64]
   const float* save_vlad;       // [B][VROWS][64]: row 512 = asum
@@ -2270,19 +2222,21 @@ void launch_rowtile(const RowTileArgs& a, hipStream_t st) {
              grid, dim3(256), kRowTile16Lds, st, a);
 }
 
-// bf16 feature maps take the fused kernels; scl_debug_set_variant(1 .. 8) sends them through the
-// float32-MFMA kernels instead (A/B timing and parity runs)
-inline bool use_fused() { return scl_variant() < 1 || scl_variant() > 8; }
-
-// Slices of the fused kernels: steps of 32 locations per workgroup so that B * S workgroups
-// cover the chip once (one workgroup per CU, 512 registers per lane).
+// ---------------------------------------------------------------------- plan and workspaces
+// Everything a call decides from (B, N, mode), decided once: the front door makes the plan, the
+// carves and the pipeline functions read it.  Slices of the eight-wave kernels: steps of 32
+// locations per workgroup so that B * S workgroups cover the chip once (one workgroup per CU, 512
+// registers per lane).  The diagnostic hooks of the product sources (scl_debug_set_variant 917, 918,
+// 921, 923, 924; SCL_VLAD_FIN_IMAGES) are all in vlad_plan: scl_variant() is the constant 0 in the
+// product build, where they fold away.
+enum VladMode { VLAD_TRAIN, VLAD_INFER };   // VLAD_INFER: the caller keeps nothing of the forward pass
 struct VladPlan {
-  int steps_per_slice, S;
+  int steps_per_slice, S;   // eight-wave kernels: grid (B, S), one slab per (slice, image)
+  int slabs;                // slabs per image in both workspaces: max(S of the sliced form, NSPLIT)
+  bool fin;                 // inference as ONE launch: a workgroup per image, the finish in its tail (S == 1)
+  int spin_limit;           // polls of the granule exchange before a workgroup computes its siblings' share
+  int fwd_dbg, dx_dbg;      // clock stamps (VladFwdArgs::dbg, VladDxArgs::dbg; scripts/vlad_stamps.py)
 };
-inline int vlad_cus() {
-  const int n = scl_device_cus();      // per device (scl_common.h)
-  return n;
-}
 // images from which inference takes one workgroup per image with the fused finish (SCL_VLAD_FIN_IMAGES;
 // measured, profiles/r06/netvlad_inference_sweep.txt)
 inline int vlad_fin_images() {
@@ -2293,30 +2247,53 @@ inline int vlad_fin_images() {
   }();
   return n;
 }
-inline VladPlan vlad_plan(int B, int N) {
+inline VladPlan vlad_plan(int B, int N, VladMode mode) {
   const int nsteps = (N + VF_STEP - 1) / VF_STEP;
+  const int cus = scl_device_cus();      // per device (scl_common.h)
+  const int v = scl_variant();
   VladPlan p;
   // (Round 5 tried "as many slices as keep B * S within ONE round of the chip" — 96 images: 2 slices
   // of 19 steps instead of 3 of 15 / 15 / 8, two partial VLADs per image instead of three.  Measured
   // equal to 2 % slower: the 32 workgroups of the short third slices start when the first short ones
   // end and finish with the long ones, so the cut by total steps / CUs was already balanced.)
-  p.steps_per_slice = (int)(((int64_t)nsteps * B + vlad_cus() - 1) / vlad_cus());
+  p.steps_per_slice = (int)(((int64_t)nsteps * B + cus - 1) / cus);
   if (p.steps_per_slice < 1) p.steps_per_slice = 1;
   p.S = (nsteps + p.steps_per_slice - 1) / p.steps_per_slice;
+  p.slabs = p.S > NSPLIT ? p.S : NSPLIT;
+  // Inference at many images: ONE workgroup per image with the finish in its tail — no partial VLADs
+  // written and re-read, one launch (evaluation/inference.py at large images_per_pass).  From
+  // vlad_fin_images() images on; below that the slices keep the chip full.
+  p.fin = mode == VLAD_INFER && (B >= vlad_fin_images() || v == 924) &&   // 924: at any batch size (tests)
+          v != 923;                                                       // 923: the two launches, for A/B
+  if (p.fin) {
+    p.steps_per_slice = nsteps;
+    p.S = 1;
+  }
+  // 921: no patience at all — every workgroup that does not find its siblings' granules at the first
+  // poll takes the self-computing path (tests: same bits either way)
+  p.spin_limit = v == 921 ? 0 : kSpinLimit;
+  p.fwd_dbg = v == 918 ? 16 : 0;
+  p.dx_dbg = v == 917 ? 1 : 0;
   return p;
 }
 
+// One layout for both pipelines and every diagnostic variant; each field names its users.
 struct FwdWs {
-  float *wt, *part, *colsum, *colsq, *vlad, *assign, *rnorm, *trash;
-  unsigned long long* stamps;   // diagnostics: [B * S][32], the LAST bytes of the workspace
-  unsigned short* wplanes;      // register images of W when the caller brought none (vlad_planes.h)
-  unsigned long long* gran;     // [B][8] granules of the finish kernel's exchange
+  float* wt;                    // float32-MFMA: W^T [64][512] (transpose_w_kernel)
+  float *part, *colsum;         // both: [slabs] partial VLADs per image and their column sums of a
+  float* colsq;                 // float32-MFMA: finish_sum_kernel -> finish_norm_kernel
+  float* vlad;                  // both: the pre-norm VLAD when the caller saves none
+  float *assign, *rnorm;        // float32-MFMA: a and rn when the caller saves none
+  float* trash;                 // eight-wave: VladFwdArgs::trash
+  unsigned long long* stamps;   // diagnostics: [B * slabs][32], the LAST bytes of the workspace
+  unsigned short* wplanes;      // eight-wave: register images of W when the caller brought none (vlad_planes.h)
+  unsigned long long* gran;     // eight-wave: [B][8] granules of the finish kernel's exchange
   size_t total;
 };
-inline FwdWs carve_fwd(void* ws, int B, int N) {
+inline FwdWs carve_fwd(void* ws, int B, int N, const VladPlan& pl) {
   Carver c(ws);
   FwdWs w;
-  const int S = vlad_plan(B, N).S > NSPLIT ? vlad_plan(B, N).S : NSPLIT;
+  const int S = pl.slabs;
   w.wt = c.take((size_t)D * K);
   w.part = c.take((size_t)B * S * D * K);
   w.colsum = c.take((size_t)B * S * K);
@@ -2332,36 +2309,294 @@ inline FwdWs carve_fwd(void* ws, int B, int N) {
   return w;
 }
 
+constexpr int kWgradGroups = 8;  // slab groups of BwdWs::wpartial
 struct BwdWs {
-  float *du, *dut, *cdu, *ds, *rowdot, *wpart, *dots, *wpartial, *trash;
-  unsigned short* duimg;     // [B] register images of dU^T for vlad_bwd_kernel
-  unsigned short* dximg;     // [B] register images of dU for vlad_dx_kernel (2 planes)
-  unsigned short* wdximg;    // the same image of W
-  unsigned long long* stamps;   // diagnostics: [B * S][32], the LAST bytes of the workspace
+  float *du, *cdu, *ds, *rowdot;   // both: dU [B][512][64], c.dU, ds [B][N][64], <dxhat, xhat>
+  float* dut;                   // float32-MFMA: dU^T, the row-tile kernel's operand
+  float* wpart;                 // both: [slabs] dW slabs per image
+  float* dots;                  // netvlad_diag.hip only (920): bwd_dots_kernel -> bwd_du_kernel
+  float* wpartial;              // netvlad_diag.hip only (920): vlad_wgrad_partial_kernel's group sums
+  float* trash;                 // eight-wave: VladBwdArgs::trash, VladDxArgs::trash
+  unsigned short* duimg;        // eight-wave: [B] register images of dU^T for vlad_bwd8_kernel
+  unsigned short* dximg;        // eight-wave: [B] register images of dU for vlad_dx_kernel (2 planes)
+  unsigned short* wdximg;       // eight-wave: both images of W when the caller brought none
+  unsigned long long* stamps;   // diagnostics: [B * slabs][32], the LAST bytes of the workspace
   size_t total;
 };
-inline BwdWs carve_bwd(void* ws, int B, int N) {
+inline BwdWs carve_bwd(void* ws, int B, int N, const VladPlan& pl) {
   Carver c(ws);
   BwdWs w;
+  const int S = pl.slabs;
   w.du = c.take((size_t)B * D * K);
   w.dut = c.take((size_t)B * D * K);
   w.cdu = c.take((size_t)B * K);
   w.ds = c.take((size_t)B * N * K);
   w.rowdot = c.take((size_t)B * N);
-  const int S = vlad_plan(B, N).S > NSPLIT ? vlad_plan(B, N).S : NSPLIT;
   w.wpart = c.take((size_t)B * S * D * K);
-  w.wpartial = c.take((size_t)VW_GROUPS * D * K);
+  w.wpartial = c.take((size_t)kWgradGroups * D * K);
   w.trash = c.take(256);
   w.dots = c.take((size_t)B * 8 * 4 * K);
   w.duimg = (unsigned short*)c.take((size_t)B * VF_NPL * D * K / 2);
   w.dximg = (unsigned short*)c.take((size_t)B * 2 * D * K / 2);
-  w.wdximg = (unsigned short*)c.take(VP_BYTES / 4);       // both images of W when the caller brought none
+  w.wdximg = (unsigned short*)c.take(VP_BYTES / 4);
   w.stamps = (unsigned long long*)c.take((size_t)B * S * 32 * 2);
   w.total = c.off;
   return w;
 }
 
 inline bool shape_ok(int B, int N) { return B >= 1 && N >= 1 && B <= 65535 && N <= (1 << 22); }
+
+// vlad_bwd_prologue_kernel in front of either backward pass: fused = the eight-wave kernels follow
+// (they take the bf16 register image of dU^T), else the row-tile kernel (dU^T in float32).
+inline void launch_bwd_prologue(const float* grad_out, const float* centers, float* save_vlad, int B, bool fused,
+                                const BwdWs& w, const VladPlan& pl, hipStream_t st) {
+  VladProArgs pa{};
+  pa.save_vlad = save_vlad;
+  pa.grad_out = grad_out;
+  pa.centers = centers;
+  pa.du = w.du;
+  pa.dut = fused ? (float*)nullptr : w.dut;
+  pa.duimg = fused ? w.duimg : (unsigned short*)nullptr;
+  pa.dximg = w.dximg;
+  pa.cdu = w.cdu;
+  pa.spin_limit = pl.spin_limit;
+  SCL_LAUNCH("vlad_bwd_prologue_kernel", vlad_bwd_prologue_kernel, dim3(8, B), dim3(256), 0, st, pa);
+}
+
+
+// The forward launches.  assign_launcher: the diagnostic build passes an ablated row-tile kernel
+// (netvlad_diag.hip, variants 1 .. 7).
+template <typename T>
+int vlad_f32_forward(const void* x, const float* assign_w, const float* centers, int B, int N, int pre_l2,
+                     float* out, float* save_assign, float* save_logit, float* save_rnorm, float* save_vlad,
+                     const FwdWs& w, hipStream_t st,
+                     void (*assign_launcher)(const RowTileArgs&, hipStream_t) = launch_rowtile<T, ASSIGN>) {
+  constexpr bool f32 = std::is_same<T, float>::value;
+  float* assign = save_assign ? save_assign : w.assign;
+  float* rnorm = save_rnorm ? save_rnorm : w.rnorm;
+  float* vlad = save_vlad ? save_vlad : w.vlad;
+  SCL_LAUNCH("transpose_w_kernel", transpose_w_kernel, dim3(D * K / 256), dim3(256), 0, st, assign_w,
+             w.wt);
+  RowTileArgs a{};
+  a.x = x;
+  a.bt = w.wt;
+  a.bt_stride = 0;
+  a.B = B;
+  a.N = N;
+  a.pre_l2 = pre_l2 ? 1 : 0;
+  a.assign = assign;
+  a.logit = save_logit;
+  a.rnorm = rnorm;
+  assign_launcher(a, st);
+  SCL_LAUNCH(f32 ? "aggregate_kernel<float>" : "aggregate_kernel<bf16>", aggregate_kernel<T>,
+             dim3(D / 64, NSPLIT, B), dim3(256), 0, st, x, (const float*)assign, (const float*)rnorm, N, w.part,
+             w.colsum);
+  SCL_LAUNCH("finish_sum_kernel", finish_sum_kernel, dim3(8, B), dim3(256), 0, st,
+             (const float*)w.part, (const float*)w.colsum, centers, vlad, w.colsq);
+  SCL_LAUNCH("finish_norm_kernel", finish_norm_kernel, dim3(8, B), dim3(256), 0, st, vlad,
+             (const float*)w.colsq, 8, out);
+  return scl_launch_status();
+}
+
+// The four launches behind the prologue (on their own: round 3's launch structure in netvlad_diag.hip
+// puts its two-kernel prologue in front of them).
+template <typename T>
+int vlad_f32_grads(const void* x, const float* assign_w, const float* save_assign, const float* save_logit,
+                   const float* save_rnorm, float* save_vlad, int B, int N, int pre_l2, void* grad_x,
+                   float* grad_w, float* grad_c, const BwdWs& w, hipStream_t st) {
+  constexpr bool f32 = std::is_same<T, float>::value;
+  RowTileArgs a{};
+  a.x = x;
+  a.bt = w.dut;
+  a.bt_stride = (int64_t)D * K;
+  a.B = B;
+  a.N = N;
+  a.pre_l2 = pre_l2 ? 1 : 0;
+  a.a_in = save_assign;
+  a.logit_in = save_logit;
+  a.rn_in = save_rnorm;
+  a.cdu = w.cdu;
+  a.ds = w.ds;
+  a.rowdot = w.rowdot;
+  launch_rowtile<T, DASSIGN>(a, st);
+  SCL_LAUNCH(f32 ? "aggregate_kernel<float>" : "aggregate_kernel<bf16>", aggregate_kernel<T>,
+             dim3(D / 64, NSPLIT, B), dim3(256), 0, st, x, (const float*)w.ds, save_rnorm, N, w.wpart,
+             (float*)nullptr);
+  SCL_LAUNCH(f32 ? "dx16_kernel<float>" : "dx16_kernel<bf16>", dx16_kernel<T>, dim3(((N + 15) / 16 + 3) / 4, B),
+             dim3(256), kDx16Lds, st, x, save_assign, (const float*)w.ds, save_rnorm, (const float*)w.rowdot,
+             (const float*)w.du, assign_w, N, pre_l2 ? 1 : 0, grad_x);
+  SCL_LAUNCH("wgrad_finish_kernel", wgrad_finish_kernel, dim3(D * K / 64), dim3(256), 0, st,
+             (const float*)w.wpart, (const float*)w.du, save_vlad, B, grad_w, grad_c);
+  return scl_launch_status();
+}
+
+template <typename T>
+int vlad_f32_backward(const void* x, const float* assign_w, const float* centers, const float* grad_out,
+                      const float* save_assign, const float* save_logit, const float* save_rnorm,
+                      float* save_vlad, int B, int N, int pre_l2, void* grad_x, float* grad_w, float* grad_c,
+                      const BwdWs& w, const VladPlan& pl, hipStream_t st) {
+  launch_bwd_prologue(grad_out, centers, save_vlad, B, false, w, pl, st);
+  return vlad_f32_grads<T>(x, assign_w, save_assign, save_logit, save_rnorm, save_vlad, B, N, pre_l2, grad_x,
+                           grad_w, grad_c, w, st);
+}
+
+
+// ---------------------------------------------------------------------- host side
+// The launches of the two passes, cut where the four-wave and round-3 launch structures of
+// netvlad_diag.hip need a seam: those call the same helpers and swap the kernel, its LDS size and
+// its block size.
+
+// the register images of W (vlad_planes.h): the caller's, or written here into `own` (VP_BYTES of workspace)
+inline const unsigned short* vlad_w_planes(const void* w_planes, const float* assign_w, unsigned short* own,
+                                           hipStream_t st) {
+  if (w_planes) return (const unsigned short*)w_planes;
+  SCL_LAUNCH("vlad_planes_kernel", vlad_planes_kernel, dim3(VP_WAVES / 4), dim3(256), 0, st, assign_w, own);
+  return own;
+}
+
+// save: the caller keeps a and rn (the eight-wave kernels neither write nor read logits — save_logit may
+// be NULL; the four-wave kernels of the diagnostic build still do)
+inline VladFwdArgs vlad_fwd_args(const void* x, const unsigned short* planes, int N, int pre_l2, bool save,
+                                 float* save_assign, float* save_logit, float* save_rnorm, const FwdWs& w,
+                                 const VladPlan& pl) {
+  VladFwdArgs fa{};
+  fa.x = (const unsigned short*)x;
+  fa.wimg = planes;
+  fa.N = N;
+  fa.pre_l2 = pre_l2 ? 1 : 0;
+  fa.steps_per_slice = pl.steps_per_slice;
+  fa.slab = w.part;
+  fa.colsum = w.colsum;
+  fa.trash = w.trash;
+  fa.gran = w.gran;
+  fa.dbg = pl.fwd_dbg;
+  fa.stamps = w.stamps;
+  if (save) {
+    fa.assign = save_assign;
+    fa.logit = save_logit;
+    fa.rnorm = save_rnorm;
+  }
+  return fa;
+}
+
+inline void launch_vlad_finish(const float* centers, int B, float* out, float* save_vlad, const FwdWs& w,
+                               const VladPlan& pl, hipStream_t st) {
+  VladFinishArgs na{};
+  na.slab = w.part;
+  na.colsum = w.colsum;
+  na.centers = centers;
+  na.S = pl.S;
+  na.B = B;
+  na.vlad = save_vlad ? save_vlad : w.vlad;
+  na.out = out;
+  na.gran = w.gran;
+  na.spin_limit = pl.spin_limit;
+  SCL_LAUNCH("vlad_finish_kernel", vlad_finish_kernel, dim3(8, B), dim3(256), 0, st, na);
+}
+
+// one pass over x: soft-assignment and aggregation fused; then ONE finish kernel — or, pl.fin, the
+// finish in the tail of the forward kernel
+inline int vlad_bf16_forward(const void* x, const float* assign_w, const float* centers, const void* w_planes,
+                             int B, int N, int pre_l2, float* out, float* save_assign, float* save_logit,
+                             float* save_rnorm, float* save_vlad, const FwdWs& w, const VladPlan& pl,
+                             hipStream_t st) {
+  static SclDeviceOnce once;
+  scl_call_once(once, [] {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&vlad_fwd8_kernel<true>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kVlad8Lds);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&vlad_fwd8_kernel<false>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kVlad8Lds);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&vlad_fwd8_kernel<false, false, true>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kVlad8Lds);
+  });
+  const unsigned short* planes = vlad_w_planes(w_planes, assign_w, w.wplanes, st);
+  const bool save = save_assign && save_rnorm;
+  VladFwdArgs fa = vlad_fwd_args(x, planes, N, pre_l2, save, save_assign, save_logit, save_rnorm, w, pl);
+  if (pl.fin) {
+    fa.fin_centers = centers;
+    fa.fin_out = out;
+    SCL_LAUNCH("vlad_fwd8_kernel<finish>", (vlad_fwd8_kernel<false, false, true>), dim3(B, 1), dim3(512),
+               kVlad8Lds, st, fa);
+    return scl_launch_status();
+  }
+  if (save)
+    SCL_LAUNCH("vlad_fwd8_kernel<true>", vlad_fwd8_kernel<true>, dim3(B, pl.S), dim3(512), kVlad8Lds,
+               st, fa);
+  else
+    SCL_LAUNCH("vlad_fwd8_kernel<false>", vlad_fwd8_kernel<false>, dim3(B, pl.S), dim3(512), kVlad8Lds,
+               st, fa);
+  launch_vlad_finish(centers, B, out, save_vlad, w, pl, st);
+  return scl_launch_status();
+}
+
+inline VladBwdArgs vlad_bwd_args(const void* x, const float* save_assign, const float* save_logit,
+                                 const float* save_rnorm, int N, const BwdWs& w, const VladPlan& pl) {
+  VladBwdArgs ba{};
+  ba.x = (const unsigned short*)x;
+  ba.duimg = w.duimg;
+  ba.a = save_assign;
+  ba.lg = save_logit;
+  ba.rn = save_rnorm;
+  ba.cdu = w.cdu;
+  ba.N = N;
+  ba.steps_per_slice = pl.steps_per_slice;
+  ba.ds = w.ds;
+  ba.rowdot = w.rowdot;
+  ba.slab = w.wpart;
+  ba.trash = w.trash;
+  return ba;
+}
+
+// wdx: the grad_x image of W.  The parameter gradients ride in the tail of the launch (wslab != NULL).
+inline VladDxArgs vlad_dx_args(const void* x, const unsigned short* wdx, const float* save_assign,
+                               const float* save_rnorm, float* save_vlad, int B, int N, int pre_l2, void* grad_x,
+                               float* grad_w, float* grad_c, const BwdWs& w, const VladPlan& pl) {
+  VladDxArgs da{};
+  da.x = (const unsigned short*)x;
+  da.a = save_assign;
+  da.ds = w.ds;
+  da.rn = save_rnorm;
+  da.rowdot = w.rowdot;
+  da.dximg = w.dximg;
+  da.wdximg = wdx;
+  da.N = N;
+  da.pre_l2 = pre_l2 ? 1 : 0;
+  da.steps_per_slice = pl.steps_per_slice;
+  da.gx = (unsigned short*)grad_x;
+  da.trash = (unsigned short*)w.trash;
+  da.dbg = pl.dx_dbg;
+  da.stamps = w.stamps;
+  da.wslab = w.wpart;
+  da.nslab = pl.S * B;
+  da.du = w.du;
+  da.save_vlad = save_vlad;
+  da.B = B;
+  da.grad_w = grad_w;
+  da.grad_c = grad_c;
+  return da;
+}
+
+inline int vlad_bf16_backward(const void* x, const float* assign_w, const float* centers, const void* w_planes,
+                              const float* grad_out, const float* save_assign, const float* save_logit,
+                              const float* save_rnorm, float* save_vlad, int B, int N, int pre_l2, void* grad_x,
+                              float* grad_w, float* grad_c, const BwdWs& w, const VladPlan& pl, hipStream_t st) {
+  static SclDeviceOnce once;
+  scl_call_once(once, [] {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&vlad_dx_kernel),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kVladDxLds);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&vlad_bwd8_kernel),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kVlad8Lds);
+  });
+  const unsigned short* wdx = vlad_w_planes(w_planes, assign_w, w.wdximg, st) + VP_FWD_ELEMS;
+  launch_bwd_prologue(grad_out, centers, save_vlad, B, true, w, pl, st);
+  const VladBwdArgs ba = vlad_bwd_args(x, save_assign, save_logit, save_rnorm, N, w, pl);
+  SCL_LAUNCH("vlad_bwd8_kernel", vlad_bwd8_kernel, dim3(B, pl.S), dim3(512), kVlad8Lds, st, ba);
+  const VladDxArgs da =
+      vlad_dx_args(x, wdx, save_assign, save_rnorm, save_vlad, B, N, pre_l2, grad_x, grad_w, grad_c, w, pl);
+  SCL_LAUNCH("vlad_dx_kernel", vlad_dx_kernel, dim3(B, pl.S), dim3(256), kVladDxLds, st, da);
+  return scl_launch_status();
+}
+
 
 }  // namespace
 
@@ -2370,23 +2605,17 @@ inline bool shape_ok(int B, int N) { return B >= 1 && N >= 1 && B <= 65535 && N 
 static bool netvlad_fwd_diag(const void* x, int x_dtype, const float* assign_w, const float* centers,
                              const void* w_planes, int B, int N, int pre_l2, float* out, float* save_assign,
                              float* save_logit, float* save_rnorm, float* save_vlad, const FwdWs& w,
-                             hipStream_t st, int* rc);
+                             const VladPlan& pl, hipStream_t st, int* rc);
 static bool netvlad_bwd_diag(const void* x, int x_dtype, const float* assign_w, const float* centers,
                              const void* w_planes, const float* grad_out, const float* save_assign,
                              const float* save_logit, const float* save_rnorm, float* save_vlad, int B, int N,
                              int pre_l2, void* grad_x, float* grad_w, float* grad_c, const BwdWs& w,
-                             hipStream_t st, int* rc);
+                             const VladPlan& pl, hipStream_t st, int* rc);
 #endif
 
 extern "C" size_t scl_netvlad_fwd_workspace_bytes(int B, int N) {
   if (!shape_ok(B, N)) return 0;
-  return carve_fwd(nullptr, B, N).total;
-}
-
-
-__global__ __launch_bounds__(256) void vlad_planes_kernel(const float* __restrict__ w,
-                                                          unsigned short* __restrict__ planes) {
-  vlad_planes_wave(w, planes, planes + VP_FWD_ELEMS, 4 * blockIdx.x + (threadIdx.x >> 6), threadIdx.x & 63);
+  return carve_fwd(nullptr, B, N, vlad_plan(B, N, VLAD_TRAIN)).total;
 }
 
 extern "C" size_t scl_netvlad_planes_bytes(void) { return VP_BYTES; }
@@ -2410,123 +2639,23 @@ extern "C" int scl_netvlad_fwd_p(const void* x, int x_dtype, const float* assign
   if (((uintptr_t)x % 16) != 0) return SCL_E_SHAPE;
   if (w_planes && !scl_aligned256(w_planes)) return SCL_E_SHAPE;
   if (!scl_aligned256(workspace)) return SCL_E_WORKSPACE;
-  FwdWs w = carve_fwd(workspace, B, N);
+  const VladPlan pl = vlad_plan(B, N, !save_assign && !save_rnorm && !save_vlad ? VLAD_INFER : VLAD_TRAIN);
+  const FwdWs w = carve_fwd(workspace, B, N, pl);
   if (workspace_bytes < w.total) return SCL_E_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  float* assign = save_assign ? save_assign : w.assign;
-  float* rnorm = save_rnorm ? save_rnorm : w.rnorm;
 #ifdef SCL_DIAG
   {
     int rc;
     if (netvlad_fwd_diag(x, x_dtype, assign_w, centers, w_planes, B, N, pre_l2, out, save_assign, save_logit,
-                         save_rnorm, save_vlad, w, st, &rc))
+                         save_rnorm, save_vlad, w, pl, st, &rc))
       return rc;
   }
 #endif
-
-  if (x_dtype == SCL_DT_BF16 && use_fused()) {
-    // one pass over x: soft-assignment and aggregation fused; then ONE finish kernel
-    static SclDeviceOnce once;
-    scl_call_once(once, [] {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&vlad_fwd8_kernel<true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kVlad8Lds);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&vlad_fwd8_kernel<false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kVlad8Lds);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&vlad_fwd8_kernel<false, false, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kVlad8Lds);
-    });
-    VladPlan pl = vlad_plan(B, N);
-    // Inference (nothing saved) at many images: ONE workgroup per image with the finish in its tail —
-    // no partial VLADs written and re-read, one launch (evaluation/inference.py at large
-    // images_per_pass).  From kVladFinImages images on; below that the slices keep the chip full.
-    const bool fin = !save_assign && !save_rnorm && !save_vlad &&
-                     (B >= vlad_fin_images() || scl_variant() == 924) &&    // 924: at any batch size (tests)
-                     scl_variant() != 923;                                   // 923: the two launches, for A/B
-    if (fin) {
-      pl.steps_per_slice = (N + VF_STEP - 1) / VF_STEP;
-      pl.S = 1;
-    }
-    const unsigned short* planes = (const unsigned short*)w_planes;
-    if (!planes) {
-      SCL_LAUNCH("vlad_planes_kernel", vlad_planes_kernel, dim3(VP_WAVES / 4), dim3(256), 0, st, assign_w,
-                 w.wplanes);
-      planes = w.wplanes;
-    }
-    VladFwdArgs fa{};
-    fa.x = (const unsigned short*)x;
-    fa.wimg = planes;
-    fa.N = N;
-    fa.pre_l2 = pre_l2 ? 1 : 0;
-    fa.steps_per_slice = pl.steps_per_slice;
-    fa.slab = w.part;
-    fa.colsum = w.colsum;
-    fa.trash = w.trash;
-    fa.gran = w.gran;
-    fa.dbg = scl_variant() == 918 ? 16 : 0;   // scripts/vlad_stamps.py
-    fa.stamps = w.stamps;
-    // (round 6: the eight-wave kernels neither write nor read logits — save_logit may be NULL; the
-    // four-wave kernels of the diagnostic build still do)
-    const bool save = save_assign && save_rnorm;
-    if (save) {
-      fa.assign = save_assign;
-      fa.logit = save_logit;
-      fa.rnorm = save_rnorm;
-    }
-    if (fin) {
-      fa.fin_centers = centers;
-      fa.fin_out = out;
-      SCL_LAUNCH("vlad_fwd8_kernel<finish>", (vlad_fwd8_kernel<false, false, true>), dim3(B, 1), dim3(512),
-                 kVlad8Lds, st, fa);
-      return scl_launch_status();
-    }
-    if (save)
-      SCL_LAUNCH("vlad_fwd8_kernel<true>", vlad_fwd8_kernel<true>, dim3(B, pl.S), dim3(512), kVlad8Lds,
-                 st, fa);
-    else
-      SCL_LAUNCH("vlad_fwd8_kernel<false>", vlad_fwd8_kernel<false>, dim3(B, pl.S), dim3(512), kVlad8Lds,
-                 st, fa);
-    float* vlad = save_vlad ? save_vlad : w.vlad;
-    VladFinishArgs na{};
-    na.slab = w.part;
-    na.colsum = w.colsum;
-    na.centers = centers;
-    na.S = pl.S;
-    na.B = B;
-    na.vlad = vlad;
-    na.out = out;
-    na.gran = w.gran;
-    na.spin_limit = spin_limit();
-    SCL_LAUNCH("vlad_finish_kernel", vlad_finish_kernel, dim3(8, B), dim3(256), 0, st, na);
-    return scl_launch_status();
-  }
-  // float32 feature maps (and bf16 ones under scl_debug_set_variant(1 .. 8)): float32-MFMA kernels
-  SCL_LAUNCH("transpose_w_kernel", transpose_w_kernel, dim3(D * K / 256), dim3(256), 0, st, assign_w,
-             w.wt);
-  RowTileArgs a{};
-  a.x = x;
-  a.bt = w.wt;
-  a.bt_stride = 0;
-  a.B = B;
-  a.N = N;
-  a.pre_l2 = pre_l2 ? 1 : 0;
-  a.assign = assign;
-  a.logit = save_logit;
-  a.rnorm = rnorm;
-  if (x_dtype == SCL_DT_F32) {
-    launch_rowtile<float, ASSIGN>(a, st);
-    SCL_LAUNCH("aggregate_kernel<float>", aggregate_kernel<float>, dim3(D / 64, NSPLIT, B), dim3(256), 0,
-               st, x, (const float*)assign, (const float*)rnorm, N, w.part, w.colsum);
-  } else {
-    launch_rowtile<unsigned short, ASSIGN>(a, st);
-    SCL_LAUNCH("aggregate_kernel<bf16>", aggregate_kernel<unsigned short>, dim3(D / 64, NSPLIT, B),
-               dim3(256), 0, st, x, (const float*)assign, (const float*)rnorm, N, w.part, w.colsum);
-  }
-  float* vlad = save_vlad ? save_vlad : w.vlad;
-  SCL_LAUNCH("finish_sum_kernel", finish_sum_kernel, dim3(8, B), dim3(256), 0, st,
-             (const float*)w.part, (const float*)w.colsum, centers, vlad, w.colsq);
-  SCL_LAUNCH("finish_norm_kernel", finish_norm_kernel, dim3(8, B), dim3(256), 0, st, vlad,
-             (const float*)w.colsq, 8, out);
-  return scl_launch_status();
+  return x_dtype == SCL_DT_BF16
+             ? vlad_bf16_forward(x, assign_w, centers, w_planes, B, N, pre_l2, out, save_assign, save_logit,
+                                 save_rnorm, save_vlad, w, pl, st)
+             : vlad_f32_forward<float>(x, assign_w, centers, B, N, pre_l2, out, save_assign, save_logit,
+                                       save_rnorm, save_vlad, w, st);
 }
 
 extern "C" int scl_netvlad_fwd(const void* x, int x_dtype, const float* assign_w,
@@ -2540,7 +2669,7 @@ extern "C" int scl_netvlad_fwd(const void* x, int x_dtype, const float* assign_w
 
 extern "C" size_t scl_netvlad_bwd_workspace_bytes(int B, int N) {
   if (!shape_ok(B, N)) return 0;
-  return carve_bwd(nullptr, B, N).total;
+  return carve_bwd(nullptr, B, N, vlad_plan(B, N, VLAD_TRAIN)).total;
 }
 
 extern "C" int scl_netvlad_bwd_p(const void* x, int x_dtype, const float* assign_w,
@@ -2554,121 +2683,28 @@ extern "C" int scl_netvlad_bwd_p(const void* x, int x_dtype, const float* assign
     return SCL_E_NULL;
   if (!shape_ok(B, N)) return SCL_E_SHAPE;
   if (x_dtype != SCL_DT_F32 && x_dtype != SCL_DT_BF16) return SCL_E_KIND;
-  // the saved logits: float32 feature maps and the four-wave kernels of the diagnostic build only
-  if (!save_logit && !(x_dtype == SCL_DT_BF16 && use_fused())) return SCL_E_NULL;
+  // the saved logits: the float32-MFMA pipeline reads them, the eight-wave one does not
+  if (!save_logit && x_dtype != SCL_DT_BF16) return SCL_E_NULL;
   if (((uintptr_t)x % 16) != 0 || ((uintptr_t)save_vlad % 8) != 0) return SCL_E_SHAPE;
   if (w_planes && !scl_aligned256(w_planes)) return SCL_E_SHAPE;
   if (!scl_aligned256(workspace)) return SCL_E_WORKSPACE;
-  BwdWs w = carve_bwd(workspace, B, N);
+  const VladPlan pl = vlad_plan(B, N, VLAD_TRAIN);
+  const BwdWs w = carve_bwd(workspace, B, N, pl);
   if (workspace_bytes < w.total) return SCL_E_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
 #ifdef SCL_DIAG
   {
     int rc;
     if (netvlad_bwd_diag(x, x_dtype, assign_w, centers, w_planes, grad_out, save_assign, save_logit, save_rnorm,
-                         save_vlad, B, N, pre_l2, grad_x, grad_w, grad_c, w, st, &rc))
+                         save_vlad, B, N, pre_l2, grad_x, grad_w, grad_c, w, pl, st, &rc))
       return rc;
   }
 #endif
-
-  const bool fused = x_dtype == SCL_DT_BF16 && use_fused();
-  const unsigned short* wdx = w_planes ? (const unsigned short*)w_planes + VP_FWD_ELEMS : nullptr;
-  if (fused && !wdx) {
-    SCL_LAUNCH("vlad_planes_kernel", vlad_planes_kernel, dim3(VP_WAVES / 4), dim3(256), 0, st, assign_w,
-               w.wdximg);
-    wdx = w.wdximg + VP_FWD_ELEMS;
-  }
-  VladProArgs pa{};
-  pa.save_vlad = save_vlad;
-  pa.grad_out = grad_out;
-  pa.centers = centers;
-  pa.du = w.du;
-  pa.dut = fused ? (float*)nullptr : w.dut;
-  pa.duimg = fused ? w.duimg : (unsigned short*)nullptr;
-  pa.dximg = w.dximg;
-  pa.cdu = w.cdu;
-  pa.spin_limit = spin_limit();
-  SCL_LAUNCH("vlad_bwd_prologue_kernel", vlad_bwd_prologue_kernel, dim3(8, B), dim3(256), 0, st, pa);
-  if (fused) {
-    static SclDeviceOnce once;
-    scl_call_once(once, [] {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&vlad_dx_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kVladDxLds);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&vlad_bwd8_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kVlad8Lds);
-    });
-    const VladPlan pl = vlad_plan(B, N);
-    VladBwdArgs ba{};
-    ba.x = (const unsigned short*)x;
-    ba.duimg = w.duimg;
-    ba.a = save_assign;
-    ba.lg = save_logit;
-    ba.rn = save_rnorm;
-    ba.cdu = w.cdu;
-    ba.N = N;
-    ba.steps_per_slice = pl.steps_per_slice;
-    ba.ds = w.ds;
-    ba.rowdot = w.rowdot;
-    ba.slab = w.wpart;
-    ba.trash = w.trash;
-    SCL_LAUNCH("vlad_bwd8_kernel", vlad_bwd8_kernel, dim3(B, pl.S), dim3(512), kVlad8Lds, st, ba);
-    VladDxArgs da{};
-    da.x = (const unsigned short*)x;
-    da.a = save_assign;
-    da.ds = w.ds;
-    da.rn = save_rnorm;
-    da.rowdot = w.rowdot;
-    da.dximg = w.dximg;
-    da.wdximg = wdx;
-    da.N = N;
-    da.pre_l2 = pre_l2 ? 1 : 0;
-    da.steps_per_slice = pl.steps_per_slice;
-    da.gx = (unsigned short*)grad_x;
-    da.trash = (unsigned short*)w.trash;
-    da.dbg = scl_variant() == 917 ? 1 : 0;
-    da.stamps = w.stamps;
-    da.wslab = w.wpart;                  // the parameter gradients ride in the tail of this launch
-    da.nslab = pl.S * B;
-    da.du = w.du;
-    da.save_vlad = save_vlad;
-    da.B = B;
-    da.grad_w = grad_w;
-    da.grad_c = grad_c;
-    SCL_LAUNCH("vlad_dx_kernel", vlad_dx_kernel, dim3(B, pl.S), dim3(256), kVladDxLds, st, da);
-    return scl_launch_status();
-  }
-  RowTileArgs a{};
-  a.x = x;
-  a.bt = w.dut;
-  a.bt_stride = (int64_t)D * K;
-  a.B = B;
-  a.N = N;
-  a.pre_l2 = pre_l2 ? 1 : 0;
-  a.a_in = save_assign;
-  a.logit_in = save_logit;
-  a.rn_in = save_rnorm;
-  a.cdu = w.cdu;
-  a.ds = w.ds;
-  a.rowdot = w.rowdot;
-  const dim3 dxgrid(((N + 15) / 16 + 3) / 4, B);
-  if (x_dtype == SCL_DT_F32) {
-    launch_rowtile<float, DASSIGN>(a, st);
-    SCL_LAUNCH("aggregate_kernel<float>", aggregate_kernel<float>, dim3(D / 64, NSPLIT, B), dim3(256), 0,
-               st, x, (const float*)w.ds, save_rnorm, N, w.wpart, (float*)nullptr);
-    SCL_LAUNCH("dx16_kernel<float>", dx16_kernel<float>, dxgrid, dim3(256), kDx16Lds, st, x, save_assign,
-               (const float*)w.ds, save_rnorm, (const float*)w.rowdot, (const float*)w.du, assign_w,
-               N, pre_l2 ? 1 : 0, grad_x);
-  } else {
-    launch_rowtile<unsigned short, DASSIGN>(a, st);
-    SCL_LAUNCH("aggregate_kernel<bf16>", aggregate_kernel<unsigned short>, dim3(D / 64, NSPLIT, B),
-               dim3(256), 0, st, x, (const float*)w.ds, save_rnorm, N, w.wpart, (float*)nullptr);
-    SCL_LAUNCH("dx16_kernel<bf16>", dx16_kernel<unsigned short>, dxgrid, dim3(256), kDx16Lds, st, x,
-               save_assign, (const float*)w.ds, save_rnorm, (const float*)w.rowdot,
-               (const float*)w.du, assign_w, N, pre_l2 ? 1 : 0, grad_x);
-  }
-  SCL_LAUNCH("wgrad_finish_kernel", wgrad_finish_kernel, dim3(D * K / 64), dim3(256), 0, st,
-                     (const float*)w.wpart, (const float*)w.du, save_vlad, B, grad_w, grad_c);
-  return scl_launch_status();
+  return x_dtype == SCL_DT_BF16
+             ? vlad_bf16_backward(x, assign_w, centers, w_planes, grad_out, save_assign, save_logit, save_rnorm,
+                                  save_vlad, B, N, pre_l2, grad_x, grad_w, grad_c, w, pl, st)
+             : vlad_f32_backward<float>(x, assign_w, centers, grad_out, save_assign, save_logit, save_rnorm,
+                                        save_vlad, B, N, pre_l2, grad_x, grad_w, grad_c, w, pl, st);
 }
 
 extern "C" int scl_netvlad_bwd(const void* x, int x_dtype, const float* assign_w,

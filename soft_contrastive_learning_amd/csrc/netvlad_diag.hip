@@ -1,17 +1,51 @@
 // NetVLAD head, DIAGNOSTIC BUILD ONLY (csrc/Makefile: libscl_hip_diag.so, -DSCL_DIAG): the kernels
 // and launch structures the product dispatch in netvlad.hip no longer takes, reachable through
 // scl_debug_set_variant for same-box A/B timing, ablations and parity runs.
-//   1 .. 7   rowtile16_kernel<ASSIGN> ablations (scripts/ablate_rowtile.py; results meaningless)
+//   1 .. 7   rowtile16_kernel<ASSIGN> ablations (scripts/ablate_rowtile.py; results meaningless):
+//            the float32-MFMA forward (vlad_f32_forward) with the ablated kernel, on either map type;
+//            backward as 8
+//   8        a bf16 map through the plain float32-MFMA kernels, forward and backward (the only
+//            place their unsigned short instantiations exist; it needs the saved logits)
 //   916, 922 round 3's four-wave fused kernels vlad_fwd_kernel / vlad_bwd_kernel (916: clock stamps)
 //   918      vlad_fwd8_kernel with clock stamps when it saves (scripts/vlad_stamps.py)
 //   920      round 3's launch structure: separate plane split, finish_sum, finish_norm, bwd_dots,
 //            bwd_du, wgrad_partial and wgrad_finish kernels around the four-wave kernels
-// netvlad.hip calls netvlad_fwd_diag / netvlad_bwd_diag after its argument checks; they return
-// false for every other variant, and the product dispatch runs.
+// (917, 918 without saving, 921, 923, 924 are knobs of the product launches: vlad_plan, netvlad.hip.)
+// netvlad.hip calls netvlad_fwd_diag / netvlad_bwd_diag after its argument checks, plan and carve; they
+// return false for every other variant, and the product dispatch runs.  The launch structures here call
+// the product's helpers (vlad_fwd_args, launch_vlad_finish, launch_bwd_prologue, ...) and swap only the
+// kernel, LDS size and block size their variant swaps.
 #include "netvlad.hip"
 
 namespace {
 
+// ---- what only the four-wave kernels and round 3's launch structure use
+constexpr int VF_AHEAD = 6;                      // A fragments in flight in the aggregation (<= 7)
+constexpr int VF_EXCH = 4 * VF_STEP * 16;         // [wave][location][up to 4 floats]
+constexpr size_t kVladFusedLds = (size_t)VF_NST * VF_STAGE + 4 * VF_CF + VF_EXCH;   // 118,784 B
+// counted wait on the wave's vector-memory queue (immediate operand: a small switch)
+__device__ __forceinline__ void vf_wait_vm(int n) {
+  switch (n) {
+    case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
+    case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
+    case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
+    case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
+    case 11: asm volatile("s_waitcnt vmcnt(11)" ::: "memory"); break;
+    case 13: asm volatile("s_waitcnt vmcnt(13)" ::: "memory"); break;
+    default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
+  }
+}
+
+// W [512][64] float32 -> register images of the fused kernels: 16-byte unit
+// ((w * 16 + s) * VF_NPL + plane) * 64 + lane  holds  W_plane[ch 32 s + 8 g + e][cluster 16 w + i],
+// e = 0..7, for lane = 16 g + i: wave w loads its 48 fragments with coalesced 16-byte loads.
+// VF_WREP identical copies, workgroups take copy (slice index) % VF_WREP.  (Tried with 4: every
+// workgroup reads this image in the same order at the same time, but the prologue — 8.3 k cycles
+// for 192 KB + 64 KB of x — did not move: it runs at the CU's L2 -> register rate, 30 B per cycle,
+// not into a hot L2 channel.  Left at 1.)
+// grid (64, VF_WREP), block 64 (block = (w, s)).
+constexpr int VF_WREP = 1;
+constexpr int VF_WIMG = VF_NPL * D * K;           // bf16 elements per copy
 __global__ __launch_bounds__(64) void vlad_split_w_kernel(const float* __restrict__ w,
                                                           unsigned short* __restrict__ img) {
   const int lane = threadIdx.x, i = lane & 15, g = lane >> 4;
@@ -32,6 +66,45 @@ __global__ __launch_bounds__(64) void vlad_split_w_kernel(const float* __restric
   }
 }
 
+// =======================================================================================
+// Fused kernels for bf16 feature maps (round 3): ONE pass over x per direction.
+//
+// vlad_fwd_kernel: soft-assignment AND aggregation of one (image, location slice) per
+// workgroup.  What bounded the two-kernel form (rowtile_ring + aggregate16b) was bytes per CU,
+// not matrix or LDS time: every 128 locations re-streamed the 196 KB operand image of W
+// through the CU's L2 -> LDS path (12-13 B per cycle and CU), and x and the assignments made a
+// second trip for the aggregation.  Here
+//   * W^T lives in REGISTERS for the whole kernel: wave w owns clusters 16 w .. 16 w + 15 as
+//     three bf16 planes (16 k-steps x 3 planes x 4 registers = 192 per lane);
+//   * the partial VLAD of the slice lives in REGISTERS too: V[512 channels][the wave's 16
+//     clusters] = 32 accumulator tiles = 128 per lane (one wave per SIMD, 512-register budget);
+//   * only x moves: 32-location steps through a 3-stage LDS ring filled by LDS-DMA (32 KB per
+//     stage, two stages in flight), each x tile consumed twice while it is in LDS — row-wise
+//     (ds_read_b128) as the B operand of the logits, column-wise (ds_read_b64_tr_b16) as the A
+//     operand of the aggregation.  Unit u(loc, c) = 64 loc + (c ^ (loc & 15)) (c = 16-byte
+//     chunk of the row) makes both kinds of read conflict-free (scripts/lds_conflicts.py); the
+//     swizzle sits on the DMA's source address.
+// The logits run with the operands SWAPPED (S^T = W^T x^T), so a lane holds four consecutive
+// clusters of ONE location: the softmax needs two cross-lane steps instead of four per value, and
+// a / logits leave as 16-byte stores.  Row norms come from the matrix cores as well: x_frag is
+// both operands of one more MFMA per k-step, whose diagonal is sum_d x^2 (bf16 products are
+// exact in float32).  The softmax over the 64 clusters spans the four waves: each wave
+// publishes (max, sum exp) of its 16 clusters per location, ONE barrier, then every wave
+// finishes a = e^(s - m_w) e^(m_w - M) / total.  The coefficients a * rn then go through a
+// per-wave [32 loc][16 cl] x 3-plane LDS image (8-byte writes, transposed reads) to become
+// the B operand of the aggregation — no round trip through HBM, no second read of x.
+// Contraction index k = 8 g + e of the aggregation is location pi(k) of the step (see vf_pi):
+// any permutation works as long as both operands use it, and this one keeps the transposed
+// reads of the x tile conflict-free.
+// Output: a, logits, rn (training), the slice's slab in accumulator order and its column sums
+// of a.  grid (S slices, B images), block 256, one workgroup per CU.
+//
+// What its stamps showed, and why round 4 went to the eight-wave kernels of netvlad.hip
+// (profiles/r03/vlad_stamps_fwd.txt): a 32-location step takes 6.4 k cycles, of which 160 MFMAs x 16
+// cycles = 2.6 k are matrix work; the rest is the softmax / coefficient arithmetic and its cross-lane
+// and LDS traffic (2.1 k), LDS latency in front of the aggregation's products, and two barriers — all
+// strictly one after the other, because a wave that owns a SIMD alone issues in order: a vector
+// instruction costs it 4 cycles (2 with a second wave on the SIMD) and nothing runs while it waits.
 template <bool SAVE>
 __global__ __launch_bounds__(256, 1) void vlad_fwd_kernel(VladFwdArgs p) {
   // 1 KB alignment: the transposed-read addresses are formed by XOR on (stage base + offset)
@@ -345,6 +418,12 @@ __global__ __launch_bounds__(256) void vlad_finish_sum_kernel(const float* __res
   if (g == 0) colsq_part[((int64_t)b * 32 + ct) * K + k] = ss;
 }
 
+// vlad_bwd_kernel: the backward twin of vlad_fwd_kernel — x.dU[b], the softmax backward and the
+// weight-gradient aggregation x^T.(ds rn) of one (image, location slice) in one pass over x.
+// The image's dU^T sits in registers (the same register image the forward uses for W^T), the slice's
+// partial dW in the accumulators.  The four partial sums P1 .. P4 each wave publishes per location
+// and what follows the ONE barrier: vlad_bwd8_kernel's comment (netvlad.hip); here lg are the SAVED
+// logits.  Outputs: ds, rowdot, the slice's dW slab.
 __global__ __launch_bounds__(256, 1) void vlad_bwd_kernel(VladBwdArgs p) {
   extern __shared__ __attribute__((aligned(1024))) unsigned char vf_lds[];
   const int lane = threadIdx.x & 63;
@@ -546,6 +625,7 @@ __global__ __launch_bounds__(256, 1) void vlad_bwd_kernel(VladBwdArgs p) {
 }
 
 
+constexpr int VW_GROUPS = kWgradGroups;   // BwdWs::wpartial holds this many group sums
 // grad_w[d,k] = sum over all (slice, image) slabs, in two levels so that every CU reads its share
 // of the 31 MB: vlad_wgrad_partial_kernel, grid (32 channel tiles, VW_GROUPS), sums one group's
 // slabs (VF_MAXS loads in flight) into partial[group][...]; vlad_wgrad_finish_kernel, grid 32,
@@ -750,22 +830,24 @@ __global__ __launch_bounds__(256) void bwd_du_kernel(const float* __restrict__ s
 }
 
 template <typename T, int VAR>
-void launch_variant_one(const RowTileArgs& a, dim3 grid, hipStream_t st) {
+void launch_variant_one(const RowTileArgs& a, hipStream_t st) {
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&rowtile16_kernel<T, ASSIGN, VAR>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRowTile16Lds);
+  const dim3 grid(((a.N + 15) / 16 + 3) / 4, a.B);
   SCL_LAUNCH("rowtile16_kernel<ASSIGN>", (rowtile16_kernel<T, ASSIGN, VAR>), grid, dim3(256), kRowTile16Lds,
              st, a);
 }
+// the ablated stand-in for launch_rowtile<T, ASSIGN> (vlad_f32_forward's launcher parameter)
 template <typename T>
-void launch_rowtile_variant(const RowTileArgs& a, dim3 grid, hipStream_t st) {
+void launch_rowtile_variant(const RowTileArgs& a, hipStream_t st) {
   switch (scl_variant() & 7) {
-    case 1: launch_variant_one<T, 1>(a, grid, st); break;
-    case 2: launch_variant_one<T, 2>(a, grid, st); break;
-    case 3: launch_variant_one<T, 3>(a, grid, st); break;
-    case 4: launch_variant_one<T, 4>(a, grid, st); break;
-    case 5: launch_variant_one<T, 5>(a, grid, st); break;
-    case 6: launch_variant_one<T, 6>(a, grid, st); break;
-    default: launch_variant_one<T, 7>(a, grid, st); break;
+    case 1: launch_variant_one<T, 1>(a, st); break;
+    case 2: launch_variant_one<T, 2>(a, st); break;
+    case 3: launch_variant_one<T, 3>(a, st); break;
+    case 4: launch_variant_one<T, 4>(a, st); break;
+    case 5: launch_variant_one<T, 5>(a, st); break;
+    case 6: launch_variant_one<T, 6>(a, st); break;
+    default: launch_variant_one<T, 7>(a, st); break;
   }
 }
 
@@ -779,45 +861,25 @@ inline bool four_waves() { return scl_variant() == 922 || scl_variant() == 920 |
 static bool netvlad_fwd_diag(const void* x, int x_dtype, const float* assign_w, const float* centers,
                              const void* w_planes, int B, int N, int pre_l2, float* out, float* save_assign,
                              float* save_logit, float* save_rnorm, float* save_vlad, const FwdWs& w,
-                             hipStream_t st, int* rc) {
+                             const VladPlan& pl_call, hipStream_t st, int* rc) {
   const int v = scl_variant();
+  const bool bf16 = x_dtype == SCL_DT_BF16;
   if (v >= 1 && v <= 7) {
-    // the float32-MFMA route of netvlad.hip with an ablated row-tile kernel
-    float* assign = save_assign ? save_assign : w.assign;
-    float* rnorm = save_rnorm ? save_rnorm : w.rnorm;
-    SCL_LAUNCH("transpose_w_kernel", transpose_w_kernel, dim3(D * K / 256), dim3(256), 0, st, assign_w,
-               w.wt);
-    RowTileArgs a{};
-    a.x = x;
-    a.bt = w.wt;
-    a.bt_stride = 0;
-    a.B = B;
-    a.N = N;
-    a.pre_l2 = pre_l2 ? 1 : 0;
-    a.assign = assign;
-    a.logit = save_logit;
-    a.rnorm = rnorm;
-    const dim3 grid(((N + 15) / 16 + 3) / 4, B);
-    if (x_dtype == SCL_DT_F32) {
-      launch_rowtile_variant<float>(a, grid, st);
-      SCL_LAUNCH("aggregate_kernel<float>", aggregate_kernel<float>, dim3(D / 64, NSPLIT, B), dim3(256), 0,
-                 st, x, (const float*)assign, (const float*)rnorm, N, w.part, w.colsum);
-    } else {
-      launch_rowtile_variant<unsigned short>(a, grid, st);
-      SCL_LAUNCH("aggregate_kernel<bf16>", aggregate_kernel<unsigned short>, dim3(D / 64, NSPLIT, B),
-                 dim3(256), 0, st, x, (const float*)assign, (const float*)rnorm, N, w.part, w.colsum);
-    }
-    float* vlad = save_vlad ? save_vlad : w.vlad;
-    SCL_LAUNCH("finish_sum_kernel", finish_sum_kernel, dim3(8, B), dim3(256), 0, st,
-               (const float*)w.part, (const float*)w.colsum, centers, vlad, w.colsq);
-    SCL_LAUNCH("finish_norm_kernel", finish_norm_kernel, dim3(8, B), dim3(256), 0, st, vlad,
-               (const float*)w.colsq, 8, out);
-    *rc = scl_launch_status();
+    // the float32-MFMA forward with an ablated row-tile kernel, whatever the map's type
+    *rc = bf16 ? vlad_f32_forward<unsigned short>(x, assign_w, centers, B, N, pre_l2, out, save_assign, save_logit,
+                                                  save_rnorm, save_vlad, w, st, launch_rowtile_variant<unsigned short>)
+               : vlad_f32_forward<float>(x, assign_w, centers, B, N, pre_l2, out, save_assign, save_logit,
+                                         save_rnorm, save_vlad, w, st, launch_rowtile_variant<float>);
+    return true;
+  }
+  if (v == 8 && bf16) {   // a bf16 map through the plain float32-MFMA kernels (A/B timing and parity runs)
+    *rc = vlad_f32_forward<unsigned short>(x, assign_w, centers, B, N, pre_l2, out, save_assign, save_logit,
+                                           save_rnorm, save_vlad, w, st);
     return true;
   }
   // (the four-wave kernels write and read logits; variant 918 without saving runs the product kernels)
   const bool save = save_assign && save_rnorm && (save_logit || !four_waves());
-  if (x_dtype != SCL_DT_BF16 || !(four_waves() || (v == 918 && save))) return false;
+  if (!bf16 || !(four_waves() || (v == 918 && save))) return false;
   static SclDeviceOnce once;
   scl_call_once(once, [] {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&vlad_fwd_kernel<true>),
@@ -827,34 +889,16 @@ static bool netvlad_fwd_diag(const void* x, int x_dtype, const float* assign_w, 
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&vlad_fwd8_kernel<true, true>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)kVlad8Lds);
   });
-  const VladPlan pl = vlad_plan(B, N);
-  const unsigned short* planes = (const unsigned short*)w_planes;
-  if (old_launches()) {
+  // always the sliced form: the four-wave kernels have no finish in their tail (pl_call.fin)
+  const VladPlan pl = pl_call.fin ? vlad_plan(B, N, VLAD_TRAIN) : pl_call;
+  const unsigned short* planes = w.wplanes;
+  if (old_launches())
     SCL_LAUNCH("vlad_split_w_kernel", vlad_split_w_kernel, dim3(64, VF_WREP), dim3(64), 0, st, assign_w,
                w.wplanes);
-    planes = w.wplanes;
-  } else if (!planes) {
-    SCL_LAUNCH("vlad_planes_kernel", vlad_planes_kernel, dim3(VP_WAVES / 4), dim3(256), 0, st, assign_w,
-               w.wplanes);
-    planes = w.wplanes;
-  }
-  VladFwdArgs fa{};
-  fa.x = (const unsigned short*)x;
-  fa.wimg = planes;
-  fa.N = N;
-  fa.pre_l2 = pre_l2 ? 1 : 0;
-  fa.steps_per_slice = pl.steps_per_slice;
-  fa.slab = w.part;
-  fa.colsum = w.colsum;
-  fa.trash = w.trash;
-  fa.gran = w.gran;
-  fa.dbg = (v == 916 || v == 918) ? 16 : 0;   // scripts/vlad_stamps.py
-  fa.stamps = w.stamps;
-  if (save) {
-    fa.assign = save_assign;
-    fa.logit = save_logit;
-    fa.rnorm = save_rnorm;
-  }
+  else
+    planes = vlad_w_planes(w_planes, assign_w, w.wplanes, st);
+  VladFwdArgs fa = vlad_fwd_args(x, planes, N, pre_l2, save, save_assign, save_logit, save_rnorm, w, pl);
+  if (v == 916) fa.dbg = 16;   // scripts/vlad_stamps.py (918: the plan's)
   if (!four_waves())
     SCL_LAUNCH("vlad_fwd8_kernel<stamps>", (vlad_fwd8_kernel<true, true>), dim3(B, pl.S), dim3(512), kVlad8Lds,
                st, fa);
@@ -863,24 +907,14 @@ static bool netvlad_fwd_diag(const void* x, int x_dtype, const float* assign_w, 
   else
     SCL_LAUNCH("vlad_fwd_kernel<false>", vlad_fwd_kernel<false>, dim3(B, pl.S), dim3(256), kVladFusedLds, st,
                fa);
-  float* vlad = save_vlad ? save_vlad : w.vlad;
   if (old_launches()) {
+    float* vlad = save_vlad ? save_vlad : w.vlad;
     SCL_LAUNCH("vlad_finish_sum_kernel", vlad_finish_sum_kernel, dim3(B, 32), dim3(256), 0, st,
                (const float*)w.part, (const float*)w.colsum, centers, pl.S, vlad, w.colsq);
     SCL_LAUNCH("finish_norm_kernel", finish_norm_kernel, dim3(8, B), dim3(256), 0, st, vlad,
                (const float*)w.colsq, 32, out);
   } else {
-    VladFinishArgs na{};
-    na.slab = w.part;
-    na.colsum = w.colsum;
-    na.centers = centers;
-    na.S = pl.S;
-    na.B = B;
-    na.vlad = vlad;
-    na.out = out;
-    na.gran = w.gran;
-    na.spin_limit = spin_limit();
-    SCL_LAUNCH("vlad_finish_kernel", vlad_finish_kernel, dim3(8, B), dim3(256), 0, st, na);
+    launch_vlad_finish(centers, B, out, save_vlad, w, pl, st);
   }
   *rc = scl_launch_status();
   return true;
@@ -890,72 +924,37 @@ static bool netvlad_bwd_diag(const void* x, int x_dtype, const float* assign_w, 
                              const void* w_planes, const float* grad_out, const float* save_assign,
                              const float* save_logit, const float* save_rnorm, float* save_vlad, int B, int N,
                              int pre_l2, void* grad_x, float* grad_w, float* grad_c, const BwdWs& w,
-                             hipStream_t st, int* rc) {
-  const bool fused = x_dtype == SCL_DT_BF16 && use_fused();
-  if (!four_waves() || (!fused && !old_launches())) return false;
+                             const VladPlan& pl, hipStream_t st, int* rc) {
+  const int v = scl_variant();
+  const bool bf16 = x_dtype == SCL_DT_BF16;
+  if (v >= 1 && v <= 8) {
+    if (!bf16) return false;             // a float32 map: the product route is the float32-MFMA one
+    // a bf16 map through the plain float32-MFMA kernels, which read the saved logits
+    *rc = save_logit ? vlad_f32_backward<unsigned short>(x, assign_w, centers, grad_out, save_assign, save_logit,
+                                                         save_rnorm, save_vlad, B, N, pre_l2, grad_x, grad_w,
+                                                         grad_c, w, pl, st)
+                     : SCL_E_NULL;
+    return true;
+  }
+  if (!four_waves() || (!bf16 && !old_launches())) return false;
   if (!save_logit) {                     // the four-wave kernels read the saved logits
     *rc = SCL_E_NULL;
     return true;
   }
-  const unsigned short* wdx = w_planes ? (const unsigned short*)w_planes + VP_FWD_ELEMS : nullptr;
+  const unsigned short* wdx = w.wdximg;
   if (old_launches()) {
     SCL_LAUNCH("bwd_dots_kernel", bwd_dots_kernel, dim3(8, B), dim3(256), 0, st, (const float*)save_vlad,
                grad_out, centers, w.dots);
     SCL_LAUNCH("bwd_du_kernel", bwd_du_kernel, dim3(8, B), dim3(256), 0, st, (const float*)save_vlad,
-               grad_out, (const float*)w.dots, w.du, fused ? (float*)nullptr : w.dut,
-               fused ? w.duimg : (unsigned short*)nullptr, w.dximg, assign_w, w.wdximg, w.cdu);
-    wdx = w.wdximg;
+               grad_out, (const float*)w.dots, w.du, bf16 ? (float*)nullptr : w.dut,
+               bf16 ? w.duimg : (unsigned short*)nullptr, w.dximg, assign_w, w.wdximg, w.cdu);
   } else {
-    if (!wdx) {
-      SCL_LAUNCH("vlad_planes_kernel", vlad_planes_kernel, dim3(VP_WAVES / 4), dim3(256), 0, st, assign_w,
-                 w.wdximg);
-      wdx = w.wdximg + VP_FWD_ELEMS;
-    }
-    VladProArgs pa{};
-    pa.save_vlad = save_vlad;
-    pa.grad_out = grad_out;
-    pa.centers = centers;
-    pa.du = w.du;
-    pa.dut = nullptr;
-    pa.duimg = w.duimg;
-    pa.dximg = w.dximg;
-    pa.cdu = w.cdu;
-    pa.spin_limit = spin_limit();
-    SCL_LAUNCH("vlad_bwd_prologue_kernel", vlad_bwd_prologue_kernel, dim3(8, B), dim3(256), 0, st, pa);
+    wdx = vlad_w_planes(w_planes, assign_w, w.wdximg, st) + VP_FWD_ELEMS;
+    launch_bwd_prologue(grad_out, centers, save_vlad, B, true, w, pl, st);
   }
-  if (!fused) {                          // variant 920, float32 feature maps: the row-tile route
-    RowTileArgs a{};
-    a.x = x;
-    a.bt = w.dut;
-    a.bt_stride = (int64_t)D * K;
-    a.B = B;
-    a.N = N;
-    a.pre_l2 = pre_l2 ? 1 : 0;
-    a.a_in = save_assign;
-    a.logit_in = save_logit;
-    a.rn_in = save_rnorm;
-    a.cdu = w.cdu;
-    a.ds = w.ds;
-    a.rowdot = w.rowdot;
-    const dim3 dxgrid(((N + 15) / 16 + 3) / 4, B);
-    if (x_dtype == SCL_DT_F32) {
-      launch_rowtile<float, DASSIGN>(a, st);
-      SCL_LAUNCH("aggregate_kernel<float>", aggregate_kernel<float>, dim3(D / 64, NSPLIT, B), dim3(256), 0,
-                 st, x, (const float*)w.ds, save_rnorm, N, w.wpart, (float*)nullptr);
-      SCL_LAUNCH("dx16_kernel<float>", dx16_kernel<float>, dxgrid, dim3(256), kDx16Lds, st, x, save_assign,
-                 (const float*)w.ds, save_rnorm, (const float*)w.rowdot, (const float*)w.du, assign_w,
-                 N, pre_l2 ? 1 : 0, grad_x);
-    } else {
-      launch_rowtile<unsigned short, DASSIGN>(a, st);
-      SCL_LAUNCH("aggregate_kernel<bf16>", aggregate_kernel<unsigned short>, dim3(D / 64, NSPLIT, B),
-                 dim3(256), 0, st, x, (const float*)w.ds, save_rnorm, N, w.wpart, (float*)nullptr);
-      SCL_LAUNCH("dx16_kernel<bf16>", dx16_kernel<unsigned short>, dxgrid, dim3(256), kDx16Lds, st, x,
-                 save_assign, (const float*)w.ds, save_rnorm, (const float*)w.rowdot,
-                 (const float*)w.du, assign_w, N, pre_l2 ? 1 : 0, grad_x);
-    }
-    SCL_LAUNCH("wgrad_finish_kernel", wgrad_finish_kernel, dim3(D * K / 64), dim3(256), 0, st,
-               (const float*)w.wpart, (const float*)w.du, save_vlad, B, grad_w, grad_c);
-    *rc = scl_launch_status();
+  if (!bf16) {                           // variant 920, float32 feature maps: the row-tile route
+    *rc = vlad_f32_grads<float>(x, assign_w, save_assign, save_logit, save_rnorm, save_vlad, B, N, pre_l2, grad_x,
+                                grad_w, grad_c, w, st);
     return true;
   }
   static SclDeviceOnce once;
@@ -965,44 +964,11 @@ static bool netvlad_bwd_diag(const void* x, int x_dtype, const float* assign_w, 
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&vlad_dx_kernel),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)kVladDxLds);
   });
-  const VladPlan pl = vlad_plan(B, N);
-  VladBwdArgs ba{};
-  ba.x = (const unsigned short*)x;
-  ba.duimg = w.duimg;
-  ba.a = save_assign;
-  ba.lg = save_logit;
-  ba.rn = save_rnorm;
-  ba.cdu = w.cdu;
-  ba.N = N;
-  ba.steps_per_slice = pl.steps_per_slice;
-  ba.ds = w.ds;
-  ba.rowdot = w.rowdot;
-  ba.slab = w.wpart;
-  ba.trash = w.trash;
+  const VladBwdArgs ba = vlad_bwd_args(x, save_assign, save_logit, save_rnorm, N, w, pl);
   SCL_LAUNCH("vlad_bwd_kernel", vlad_bwd_kernel, dim3(B, pl.S), dim3(256), kVladFusedLds, st, ba);
-  VladDxArgs da{};
-  da.x = (const unsigned short*)x;
-  da.a = save_assign;
-  da.ds = w.ds;
-  da.rn = save_rnorm;
-  da.rowdot = w.rowdot;
-  da.dximg = w.dximg;
-  da.wdximg = wdx;
-  da.N = N;
-  da.pre_l2 = pre_l2 ? 1 : 0;
-  da.steps_per_slice = pl.steps_per_slice;
-  da.gx = (unsigned short*)grad_x;
-  da.trash = (unsigned short*)w.trash;
-  da.stamps = w.stamps;
-  if (!old_launches()) {                 // the parameter gradients ride in the tail of this launch
-    da.wslab = w.wpart;
-    da.nslab = pl.S * B;
-    da.du = w.du;
-    da.save_vlad = save_vlad;
-    da.B = B;
-    da.grad_w = grad_w;
-    da.grad_c = grad_c;
-  }
+  VladDxArgs da =
+      vlad_dx_args(x, wdx, save_assign, save_rnorm, save_vlad, B, N, pre_l2, grad_x, grad_w, grad_c, w, pl);
+  if (old_launches()) da.wslab = nullptr;   // no tail: the two kernels below sum the slabs
   SCL_LAUNCH("vlad_dx_kernel", vlad_dx_kernel, dim3(B, pl.S), dim3(256), kVladDxLds, st, da);
   if (old_launches()) {
     SCL_LAUNCH("vlad_wgrad_partial_kernel", vlad_wgrad_partial_kernel, dim3(32, VW_GROUPS), dim3(256), 0, st,

@@ -94,7 +94,7 @@ def test_forward_bf16_feature_map(dev):
 @pytest.mark.parametrize("b,n,pre_l2", [(1, 1, True), (2, 31, True), (3, 33, True), (4, 196, True),
                                         (2, 165, False), (5, 1200, True), (40, 70, True), (2, 2100, True)])
 def test_fused_bf16_kernels_on_ragged_shapes(dev, b, n, pre_l2):
-    """The fused bf16 kernels (vlad_fwd / vlad_bwd / vlad_dx: 32-location steps, slices of an image
+    """The fused bf16 kernels (vlad_fwd8 / vlad_bwd8 / vlad_dx: 32-location steps, slices of an image
     on different workgroups, the slab sums) at shapes that exercise every edge: a single location,
     a partial last step, one step per slice, more slices than the slab reader takes in one batch of
     loads (2100 locations: 66 slices), many images, no channel norm; training mode (saved rows)
@@ -120,6 +120,59 @@ def test_fused_bf16_kernels_on_ragged_shapes(dev, b, n, pre_l2):
     assert _nrel(gc, c64.grad.numpy()) < 2e-4
     infer = _run(dev, x, w, c, pre_l2=pre_l2, dtype=torch.bfloat16)
     assert _maxrel(infer, out) < 2e-5
+
+
+@pytest.mark.parametrize("b,n,pre_l2", [(1, 1, True), (3, 33, True), (2, 165, False)])
+def test_float32_mfma_kernels_on_a_bf16_map(dev, b, n, pre_l2):
+    """Diagnostic variant 8 sends a bf16 map through the float32-MFMA kernels (the unsigned short
+    instantiations of rowtile16 / aggregate / dx16, which only the diagnostic build has), forward and
+    backward.  Against the float64 twin fed the bf16-rounded map, with the bounds of
+    test_fused_bf16_kernels_on_ragged_shapes: this route is exact float32 arithmetic on the same
+    inputs, so it is not looser than the fused one."""
+    from soft_contrastive_learning_amd import _lib as L
+    from soft_contrastive_learning_amd.model import nets
+    x = U.feature_map(b, n, seed=7 * b + n)
+    if not pre_l2:
+        x = x * 0.1
+    xb = torch.tensor(x).to(torch.bfloat16).float().numpy()
+    w, c = U.vlad_params(seed=8, logit_scale=3.0 if pre_l2 else 1.0)
+    g = np.random.default_rng(2).standard_normal((b, 32768)).astype(np.float32)
+    x64 = torch.tensor(xb, dtype=torch.float64, requires_grad=True)
+    w64 = torch.tensor(w, dtype=torch.float64, requires_grad=True)
+    c64 = torch.tensor(c, dtype=torch.float64, requires_grad=True)
+    o64 = TT.netvlad(x64, w64, c64, pre_l2=pre_l2)
+    o64.backward(torch.tensor(g, dtype=torch.float64))
+    with L.variant(8):
+        with L.KernelTimer(capacity=16) as kt:
+            out, gx, gw, gc = _run(dev, x, w, c, pre_l2=pre_l2, dtype=torch.bfloat16, grad=g)
+            torch.cuda.synchronize()
+    assert {'rowtile16_kernel<ASSIGN>', 'rowtile16_kernel<DASSIGN>', 'aggregate_kernel<bf16>',
+            'dx16_kernel<bf16>'} <= set(kt.summary()), kt.summary()
+    assert _maxrel(out, o64.detach().numpy()) < 1e-4
+    assert _nrel(gx, x64.grad.numpy()) < 6e-3               # grad_x is stored in bf16
+    assert _nrel(gw, w64.grad.numpy()) < 2e-4
+    assert _nrel(gc, c64.grad.numpy()) < 2e-4
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_rowtile_ablations_still_launch(dev, dtype):
+    """Diagnostic variants 1 .. 7 (scripts/ablate_rowtile.py) run the float32-MFMA forward with an
+    ablated row-tile kernel on either map type: the call returns SCL_OK and the stream synchronises.
+    Nothing about values: the variants compute garbage by design."""
+    from soft_contrastive_learning_amd import _lib as L
+    from soft_contrastive_learning_amd.model import nets
+    b, n = 2, 33
+    xt = torch.tensor(U.feature_map(b, n, seed=3), device=dev).to(dtype).reshape(b, 1, n, 512)
+    w, c = U.vlad_params()
+    wt, ct = torch.tensor(w, device=dev), torch.tensor(c, device=dev)
+    for v in range(1, 8):
+        with L.variant(v):
+            with L.KernelTimer(capacity=16) as kt:
+                with torch.no_grad():
+                    out = nets.netvlad(xt, wt, ct, True)      # (raises unless the call returned SCL_OK)
+                torch.cuda.synchronize()
+        assert out.shape == (b, 32768)
+        assert 'rowtile16_kernel<ASSIGN>' in set(kt.summary()), (v, kt.summary())
 
 
 @pytest.mark.parametrize("b,n,pre_l2", [(2, 37, True), (3, 196, True), (2, 64, False), (4, 1200, True)])
