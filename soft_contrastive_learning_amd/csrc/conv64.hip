@@ -1,9 +1,35 @@
-// 3x3 / stride 1 / same-padding convolution with 64 input and 64 output channels on bf16
-// channels-last activations — VGG16's conv1_2 at full resolution (model/nets.py:41-42), the
-// one layer where the library kernels run at half the rate of its equal-FLOP siblings
-// (DESIGN.md §7).  Used for the forward pass and, with the weights transposed and the taps
-// flipped, for the backward-data pass.
+// The first VGG blocks on bf16 channels-last activations: the 3x3 / stride 1 / same-padding
+// convolution whose weights live in REGISTERS (conv1_2 .. conv2_2: 64 -> 64, 64 -> 128, 128 -> 64,
+// 128 -> 128; forward and, with the weights transposed and the taps flipped, backward-data), the
+// weight gradient of EVERY 3x3 layer (channel counts multiples of 64, up to 1024), and the first
+// layer (3 -> 64) with its gradients.  Entry points (include/scl_hip.h), front doors and kernels in
+// launch order; the host side is the end of this file, the diagnostic build's variants are
+// conv64_diag.hip.
 //
+// Convolution — scl_conv3x3_fused / _pool_idx / _masked / _masked_pooled (scl_conv3x3, scl_conv64):
+// each fills a RegConvCall; reg_conv checks it and dispatches on (cin, kout) to launch_conv3x3.
+//   conv3x3_pack_kernel        weights -> register image in the workspace, unless the caller brought
+//                              one (SCL_W_PACKED, scl_conv_pack_batch): reg_weights
+//   conv3x3_kernel<EPI, PL>    one persistent workgroup per CU; EPI 0 plain, 1 + bias (+ ReLU), 2 raw +
+//                              pooled map, 3 * [mask > 0], 4 pooled map + window positions; PL 1 un-pools
+//                              its input while staging: conv_launch
+// Weight gradient — scl_wrw3x3_bias / _pooled (scl_wrw3x3_ex, scl_wrw3x3, scl_wrw64): each fills a
+// WrwCall; wrw3x3_run checks it and cuts the work with ONE WrwPlan (wrw_plan; the workspace: wrw_space).
+//   wrw64_kernel<TWv, NKB, PL> [64 c] x [64 NKB k] blocks over pixel splits -> slabs (+ bias partials);
+//                              tile width, blocks and pooled form chosen once: for_wrw_shape, wrw_launch
+//   wrw64_reduce_kernel<RG>    slabs -> gw at its strides (+ grad_bias): wrw_reduce
+// First layer — scl_conv_first: conv_first_kernel (mean subtraction, cast, conv1_1, bias, ReLU).
+// scl_conv_first_pool_idx: conv3x3_pack_kernel, conv12_kernel (conv1_1 and conv1_2 with the pooling
+// epilogue in one).  scl_conv_first_wrw: conv_first_wrw_kernel -> slabs, then first_wrw_finish:
+//   conv_first_wrw_reduce_kernel   slabs -> gw, gb and the border sums
+//   conv_first_davg_kernel         the trainable mean's gradient from those and the corner pixels
+// scl_conv3x3_masked_pooled_first_wrw: conv3x3_pack_kernel, conv3x3_kernel<64, 64, 3, 1, FW = 1>
+// (conv1_2's backward-data pass with conv1_1's gradient products on the tile), first_wrw_finish.
+// The first-layer gradient workspace is laid out by the kFw* constants below.
+//
+// The register convolution, at its first shape (64 -> 64: VGG16's conv1_2 at full resolution,
+// model/nets.py:41-42, the one layer where the library kernels run at half the rate of its
+// equal-FLOP siblings):
 // Implicit GEMM on v_mfma_f32_32x32x16_bf16: out[p][k] = sum_{tap, c} x[p + s_tap][c] W[tap][c][k],
 // M = pixels, N = 64, K = 9 taps x 64 channels = 36 k-steps of 16.  The contraction index c is
 // the FAST index of x, so an A fragment (pixel r, 8 consecutive channels) is one ds_read_b128
@@ -35,6 +61,24 @@ constexpr int SCR = 32 * SCR_LD;                     // per-wave epilogue scratc
 // Round 5: wrw64_kernel takes the buffer path for tiles whose window columns lie inside the image
 // (DBG & 8 = the round-4 staging, for A/B in the diagnostic build).
 constexpr bool kWrwBufPath = true;
+
+// The first layer's weight-gradient workspace (scl_conv_first_wrw_workspace_bytes), in floats:
+//   [0, kFwAux)             one slab of kFwSlab floats per workgroup: its partial [64 ch][32 columns]
+//                           (27 tap x channel columns, the bias column, four border columns)
+//   [kFwAux, + kFwAuxLen)   the four border-sum rows [4][64], conv_first_wrw_reduce_kernel -> davg kernel
+// conv_first_wrw_kernel runs two workgroups per CU and may fill the slab region.  The fused route
+// (conv3x3_kernel FW = 1) runs ONE per CU: its slabs end below kFwStamps, and the upper half of the
+// region carries what only that route writes:
+//   [kFwStamps, ...)        clock stamps [workgroup][4 tiles][12] uint64 (diagnostic build, 61064)
+//   [kFwCorners, kFwAux)    the corner pixels [B][4][64] bf16 of the map it does not write, B <= kFwMaxBatch
+constexpr int kFwSlab = 2048;
+constexpr int kFwMaxSlabs = 2 * kSclMaxConvCus;
+constexpr size_t kFwAux = (size_t)kFwMaxSlabs * kFwSlab, kFwAuxLen = 256;
+constexpr size_t kFwStamps = kFwAux / 2, kFwCorners = kFwAux / 4 * 3;   // slab 1024, slab 1536
+constexpr int kFwMaxBatch = 8192;
+static_assert((size_t)kSclMaxConvCus * kFwSlab <= kFwStamps, "the fused route's slabs (one per CU) end below the stamps");
+static_assert(kFwStamps + (size_t)kSclMaxConvCus * 4 * 12 * 2 <= kFwCorners, "the stamps end below the corner copy");
+static_assert(kFwCorners + (size_t)kFwMaxBatch * 4 * 64 / 2 <= kFwAux, "the corner copy ends below the border sums");
 
 // Generalisation to the other VGG shapes whose weight slice still fits the register file:
 //   (CIN, KOUT) in {(64,64) conv1_2 fwd+bwd, (64,128) conv2_1 fwd, (128,64) conv2_1 bwd,
@@ -304,7 +348,7 @@ __global__ __launch_bounds__((ConvCfg<CIN, KOUT, GEO>::NTHR), (GEO ? 2 : 1)) voi
   int xpar = 0;
   // dbg & 64 (scl_debug_set_variant(61064), FW only): wave `dbg >> 7` of every workgroup writes
   // s_memtime stamps of its tiles 2 .. 5 behind the slabs ([workgroup][tile][12] at float offset
-  // 1024 * 2048 of the workspace): 0 tile start, 1 K loop done, 2 own loads landed, 3 barrier 1
+  // kFwStamps of the workspace): 0 tile start, 1 K loop done, 2 own loads landed, 3 barrier 1
   // passed, 4 epilogue rows in LDS, 5 barrier 2, 6 im2col built, 7 barrier 3, 8 products done,
   // 9 barrier 4 (scripts/first_wrw_fused_ablate.py --stamps)
   uint64_t fstamp[10];
@@ -453,7 +497,7 @@ __global__ __launch_bounds__((ConvCfg<CIN, KOUT, GEO>::NTHR), (GEO ? 2 : 1)) voi
         // the four corner pixels of the image: what conv_first_davg_kernel reads of this map
         const bool cy0 = oy == 0, cy1 = oy == H - 1, cx0 = ox == 0, cx1 = ox == W - 1;
         if ((cy0 || cy1) && (cx0 || cx1)) {
-          unsigned short* cp = reinterpret_cast<unsigned short*>(fslabs + (size_t)1536 * 2048) +
+          unsigned short* cp = reinterpret_cast<unsigned short*>(fslabs + kFwCorners) +
                                ((int64_t)b * 4 + (cy1 ? 2 : 0) + (cx1 ? 1 : 0)) * C64 + 32 * nt + 8 * hf;
           *reinterpret_cast<u32x4*>(cp) = v0;
           *reinterpret_cast<u32x4*>(cp + 16) = v1;
@@ -570,7 +614,7 @@ __global__ __launch_bounds__((ConvCfg<CIN, KOUT, GEO>::NTHR), (GEO ? 2 : 1)) voi
     if (FW && (dbg & 64)) {
       FW_STAMP(9);
       if ((int)threadIdx.x == 64 * (dbg >> 7) && ftile >= 2 && ftile < 6) {
-        uint64_t* o = reinterpret_cast<uint64_t*>(fslabs + (size_t)1024 * 2048) +
+        uint64_t* o = reinterpret_cast<uint64_t*>(fslabs + kFwStamps) +
                       ((int64_t)blockIdx.x * 4 + (ftile - 2)) * 12;
 #pragma unroll
         for (int k = 0; k < 10; ++k) o[k] = fstamp[k];
@@ -593,8 +637,9 @@ __global__ __launch_bounds__((ConvCfg<CIN, KOUT, GEO>::NTHR), (GEO ? 2 : 1)) voi
       for (int j = 0; j < 4; ++j) red[(pq * 64 + 32 * mt_ + acc_row(4 * v + j, h)) * 32 + r] = t[j];
     }
     __syncthreads();
-    for (int e = threadIdx.x; e < 2048; e += Cfg::NTHR)
-      fslabs[(int64_t)blockIdx.x * 2048 + e] = (red[e] + red[2048 + e]) + (red[4096 + e] + red[6144 + e]);
+    for (int e = threadIdx.x; e < kFwSlab; e += Cfg::NTHR)
+      fslabs[(int64_t)blockIdx.x * kFwSlab + e] =
+          (red[e] + red[kFwSlab + e]) + (red[2 * kFwSlab + e] + red[3 * kFwSlab + e]);
   }
 }
 
@@ -1641,9 +1686,9 @@ __global__ __launch_bounds__(256, 2) void conv_first_wrw_kernel(
     for (int qq = 0; qq < 16; ++qq)
       red[(wid * 64 + 32 * mt + acc_row(qq, h)) * 32 + r] = acc[mt][qq];
   __syncthreads();
-  float* out = slabs + (int64_t)blockIdx.x * 2048;
-  for (int e = threadIdx.x; e < 2048; e += 256)
-    out[e] = (red[e] + red[2048 + e]) + (red[4096 + e] + red[6144 + e]);
+  float* out = slabs + (int64_t)blockIdx.x * kFwSlab;
+  for (int e = threadIdx.x; e < kFwSlab; e += 256)
+    out[e] = (red[e] + red[kFwSlab + e]) + (red[2 * kFwSlab + e] + red[3 * kFwSlab + e]);
 }
 
 // gw / gb from the slabs: grid 32, block 256 = 64 elements x 4 slab groups; element
@@ -1658,10 +1703,10 @@ __global__ __launch_bounds__(256) void conv_first_wrw_reduce_kernel(
   float s0 = 0.f, s1 = 0.f;
   int i = g;
   for (; i + 4 < nslab; i += 8) {
-    s0 += slabs[(int64_t)i * 2048 + e];
-    s1 += slabs[(int64_t)(i + 4) * 2048 + e];
+    s0 += slabs[(int64_t)i * kFwSlab + e];
+    s1 += slabs[(int64_t)(i + 4) * kFwSlab + e];
   }
-  if (i < nslab) s0 += slabs[(int64_t)i * 2048 + e];
+  if (i < nslab) s0 += slabs[(int64_t)i * kFwSlab + e];
   red[g][j] = s0 + s1;
   __syncthreads();
   if (g == 0) {
@@ -1760,82 +1805,91 @@ __global__ __launch_bounds__(64) void conv_first_davg_kernel(
 
 }  // namespace
 
+// ---------------------------------------------------------------------------------------
+// Host side (the file's header lists the entry points and what each launches).
+
+// A call of the register-weights convolution: reg_conv checks it, launch_conv3x3 trusts it.  The first
+// twelve fields are the entry points' leading arguments in their order (initialised by position, every
+// later field by name: new fields go to the END).
+struct RegConvCall {
+  const void *x, *w;
+  int64_t sk, sc, sh, sw;       // weight strides (elements)
+  int flags;                    // SCL_CONV_TRANSPOSED | SCL_W_F32 | SCL_W_PACKED
+  int B, H, W, cin, kout;
+  void* out;                    // [B,H,W,kout]; none with pidx
+  const float* bias;
+  int relu;
+  void* pooled;                 // [B,H/2,W/2,kout]: relu(maxpool(conv) + bias)
+  const void* mask;             // out = conv * [mask > 0]
+  void* pidx;                   // the window position of each maximum of `pooled`
+  const void* uidx;             // x is a POOLED gradient [B,H/2,W/2,cin], these its window positions
+  void* workspace;              // scl_conv3x3_workspace_bytes(), 256-byte aligned
+  hipStream_t stream;
+};
+
+// A call of the weight gradient (wrw3x3_run), the entry points' arguments in scl_wrw3x3_pooled's order.
+// pidx != nullptr: gz is the pooled gradient [B][H/2][W/2][kout], pidx its window positions.
+struct WrwCall {
+  const void *x, *gz;
+  const unsigned char* pidx;
+  int B, H, W, cin, kout;
+  void* gw;
+  int64_t sk, sc, sh, sw;       // strides of gw (elements)
+  int gw_f32;
+  float* grad_bias;             // [kout], or none
+  void* workspace;              // scl_wrw3x3_workspace_bytes(cin, kout), 256-byte aligned
+  hipStream_t stream;
+};
+
 #ifdef SCL_DIAG
 // the diagnostic variants (conv64_diag.hip): true when the variant owns the call, its status in *rc
-static bool conv3x3_diag(const void* x, const void* w, int64_t sk, int64_t sc, int64_t sh, int64_t sw,
-                         int transposed, int B, int H, int W, int cin, int kout, void* out, const float* bias,
-                         int relu, void* pooled, const void* mask, void* pidx, const void* uidx, void* workspace,
-                         hipStream_t st, int* rc);
-static bool wrw3x3_diag(const void* x, const void* gz, const unsigned char* pidx, int B, int H, int W, int cin,
-                        int kout, void* gw, int64_t w_stride_k, int64_t w_stride_c, int64_t w_stride_h,
-                        int64_t w_stride_w, int gw_f32, float* grad_bias, void* workspace, size_t need,
-                        void* stream, int* rc);
+static bool conv3x3_diag(const RegConvCall& c, int* rc);
+static bool wrw3x3_diag(const WrwCall& c, int* rc);
 #endif
 
-template <int CIN, int KOUT, int GEO = 0>
-int launch_conv3x3(const void* x, const void* w, int64_t sk, int64_t sc, int64_t sh, int64_t sw,
-                   int transposed, int B, int H, int W, void* out, const float* bias, int relu,
-                   void* pooled, const void* mask, void* pidx, const void* uidx, void* workspace,
-                   hipStream_t st) {
+// The register image of a weight: the caller's own (SCL_W_PACKED: scl_conv_pack_batch wrote it), or
+// packed into the workspace here; the pack kernel gets `flags` as they are.
+template <int CIN, int KOUT>
+const unsigned short* reg_weights(const void* w, int64_t sk, int64_t sc, int64_t sh, int64_t sw, int flags,
+                                  void* workspace, hipStream_t st) {
+  using Cfg = ConvCfg<CIN, KOUT>;
+  if (flags & SCL_W_PACKED) return (const unsigned short*)w;
+  SCL_LAUNCH("conv3x3_pack_kernel", (conv3x3_pack_kernel<CIN, KOUT>), dim3(Cfg::NT * Cfg::KS * 512 / 256),
+             dim3(256), 0, st, w, sk, sc, sh, sw, flags, (unsigned short*)workspace);
+  return (const unsigned short*)workspace;
+}
+
+// conv3x3_kernel<CIN, KOUT, EPI, PL, 0, GEO> on the persistent grid.  What each epilogue receives besides
+// x, the image and the bias:  0, 1, 2: out, relu, pooled.  3: out and mask, uidx when PL is 1.  4: no
+// out; pooled and pidx.  3 and 4 without the ReLU bit.
+template <int CIN, int KOUT, int GEO, int EPI, int PL>
+void conv_launch(const RegConvCall& c, const unsigned short* packed, int relu) {
   using Cfg = ConvCfg<CIN, KOUT, GEO>;
-  static_assert(pack_reg_shape(CIN, KOUT), "the shapes that scl_conv_pack_batch gives the register image");
-  static SclDeviceOnce once;
-  scl_call_once(once, [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_kernel<CIN, KOUT, 0, 0, 0, GEO>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_kernel<CIN, KOUT, 1, 0, 0, GEO>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_kernel<CIN, KOUT, 2, 0, 0, GEO>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_kernel<CIN, KOUT, 3, 0, 0, GEO>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_kernel<CIN, KOUT, 4, 0, 0, GEO>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS);
-    if (CIN == KOUT)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_kernel<CIN, CIN, 3, 1, 0, GEO>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS);
-  });
+  scl_lds_limit<&conv3x3_kernel<CIN, KOUT, EPI, PL, 0, GEO>>((int)Cfg::LDS);
   const int cus = scl_conv_cus() * (GEO ? 2 : 1);
-  const unsigned short* packed = (const unsigned short*)workspace;
-  if (transposed & SCL_W_PACKED)
-    packed = (const unsigned short*)w;                   // scl_conv_pack_batch wrote it
-  else
-    SCL_LAUNCH("conv3x3_pack_kernel", (conv3x3_pack_kernel<CIN, KOUT>),
-               dim3(Cfg::NT * Cfg::KS * 512 / 256), dim3(256), 0, st, w, sk, sc, sh, sw, transposed,
-               (unsigned short*)workspace);
-  const int tiles = B * ((H + Cfg::TH_ - 1) / Cfg::TH_) * ((W + TW - 1) / TW);
-  const dim3 grid(tiles < cus ? tiles : cus);
+  const int tiles = c.B * ((c.H + Cfg::TH_ - 1) / Cfg::TH_) * ((c.W + TW - 1) / TW);
+  SCL_LAUNCH(PL ? "conv3x3_kernel<pooled>" : "conv3x3_kernel", (conv3x3_kernel<CIN, KOUT, EPI, PL, 0, GEO>),
+             dim3(tiles < cus ? tiles : cus), dim3(Cfg::NTHR), Cfg::LDS, c.stream, (const unsigned short*)c.x,
+             packed, c.B, c.H, c.W, (unsigned short*)(EPI == 4 ? nullptr : c.out), c.bias,
+             EPI >= 3 ? relu & ~1 : relu, (unsigned short*)(EPI == 3 ? nullptr : c.pooled),
+             (const unsigned short*)(EPI == 3 ? c.mask : nullptr), (unsigned char*)(EPI == 4 ? c.pidx : nullptr),
+             (const unsigned char*)(PL ? c.uidx : nullptr));
+}
+
+template <int CIN, int KOUT, int GEO = 0>
+int launch_conv3x3(const RegConvCall& c) {
+  static_assert(pack_reg_shape(CIN, KOUT), "the shapes that scl_conv_pack_batch gives the register image");
+  // by epilogue: 0 plain, 1 bias (+ ReLU), 2 raw + pooled map, 3 masked, 4 pooled map + window positions;
+  // then 3 with x un-pooled by uidx while staging (PL 1: reg_conv lets uidx through for cin == kout only)
+  using Launch = void (*)(const RegConvCall&, const unsigned short*, int);
+  static constexpr Launch by_epi[] = {&conv_launch<CIN, KOUT, GEO, 0, 0>, &conv_launch<CIN, KOUT, GEO, 1, 0>,
+                                      &conv_launch<CIN, KOUT, GEO, 2, 0>, &conv_launch<CIN, KOUT, GEO, 3, 0>,
+                                      &conv_launch<CIN, KOUT, GEO, 4, 0>, &conv_launch<CIN, CIN, GEO, 3, 1>};
+  const int epi = c.pidx ? 4 : c.mask ? 3 : c.pooled ? 2 : c.bias ? 1 : 0;
+  int relu = c.relu ? 1 : 0;
   if (scl_variant() / 1000 == 60) relu |= (scl_variant() & 7) << 1;   // bit 2: setprio experiment
-  if (pidx)
-    SCL_LAUNCH("conv3x3_kernel", (conv3x3_kernel<CIN, KOUT, 4, 0, 0, GEO>), grid, dim3(Cfg::NTHR), Cfg::LDS, st,
-               (const unsigned short*)x, (const unsigned short*)packed, B, H, W,
-               (unsigned short*)nullptr, bias, relu & ~1, (unsigned short*)pooled,
-               (const unsigned short*)nullptr, (unsigned char*)pidx, (const unsigned char*)nullptr);
-  else if (mask && uidx && CIN == KOUT)
-    SCL_LAUNCH("conv3x3_kernel<pooled>", (conv3x3_kernel<CIN, CIN, 3, 1, 0, GEO>), grid, dim3(Cfg::NTHR), Cfg::LDS,
-               st, (const unsigned short*)x, (const unsigned short*)packed, B, H, W,
-               (unsigned short*)out, bias, relu & ~1, (unsigned short*)nullptr,
-               (const unsigned short*)mask, (unsigned char*)nullptr, (const unsigned char*)uidx);
-  else if (mask)
-    SCL_LAUNCH("conv3x3_kernel", (conv3x3_kernel<CIN, KOUT, 3, 0, 0, GEO>), grid, dim3(Cfg::NTHR), Cfg::LDS, st,
-               (const unsigned short*)x, (const unsigned short*)packed, B, H, W,
-               (unsigned short*)out, bias, relu & ~1, (unsigned short*)nullptr,
-               (const unsigned short*)mask, (unsigned char*)nullptr, (const unsigned char*)nullptr);
-  else if (pooled)
-    SCL_LAUNCH("conv3x3_kernel", (conv3x3_kernel<CIN, KOUT, 2, 0, 0, GEO>), grid, dim3(Cfg::NTHR), Cfg::LDS, st,
-               (const unsigned short*)x, (const unsigned short*)packed, B, H, W,
-               (unsigned short*)out, bias, relu, (unsigned short*)pooled,
-               (const unsigned short*)nullptr, (unsigned char*)nullptr, (const unsigned char*)nullptr);
-  else if (bias)
-    SCL_LAUNCH("conv3x3_kernel", (conv3x3_kernel<CIN, KOUT, 1, 0, 0, GEO>), grid, dim3(Cfg::NTHR), Cfg::LDS, st,
-               (const unsigned short*)x, (const unsigned short*)packed, B, H, W,
-               (unsigned short*)out, bias, relu, (unsigned short*)pooled,
-               (const unsigned short*)nullptr, (unsigned char*)nullptr, (const unsigned char*)nullptr);
-  else
-    SCL_LAUNCH("conv3x3_kernel", (conv3x3_kernel<CIN, KOUT, 0, 0, 0, GEO>), grid, dim3(Cfg::NTHR), Cfg::LDS, st,
-               (const unsigned short*)x, (const unsigned short*)packed, B, H, W,
-               (unsigned short*)out, bias, relu, (unsigned short*)pooled,
-               (const unsigned short*)nullptr, (unsigned char*)nullptr, (const unsigned char*)nullptr);
+  by_epi[epi == 3 && c.uidx && CIN == KOUT ? 5 : epi](
+      c, reg_weights<CIN, KOUT>(c.w, c.sk, c.sc, c.sh, c.sw, c.flags, c.workspace, c.stream), relu);
   return scl_launch_status();
 }
 
@@ -1843,105 +1897,102 @@ extern "C" size_t scl_conv3x3_workspace_bytes(void) {
   return scl_round256((size_t)4 * 72 * 512 * sizeof(unsigned short));   // largest packed image
 }
 
-static int conv3x3_dispatch(const void* x, const void* w, int64_t w_stride_k, int64_t w_stride_c,
-                            int64_t w_stride_h, int64_t w_stride_w, int transposed, int B, int H,
-                            int W, int cin, int kout, void* out, const float* bias, int relu,
-                            void* pooled, const void* mask, void* pidx, void* workspace,
-                            size_t workspace_bytes, void* stream, const void* uidx = nullptr) {
-  if (!x || !w || (!out && !pidx) || !workspace) return SCL_E_NULL;
+// The front door of the register convolution.  The checks keep this order: callers see which of two
+// refusals wins.
+static int reg_conv(RegConvCall c, size_t workspace_bytes) {
+  if (!c.x || !c.w || (!c.out && !c.pidx) || !c.workspace) return SCL_E_NULL;
   // un-pooling window staging: the masked backward-data pass of a cin == kout layer, even H, W
-  if (uidx && (!mask || cin != kout || ((H | W) & 1) || ((uintptr_t)uidx % 8))) return SCL_E_SHAPE;
-  if (pidx && (!pooled || !bias || mask || ((uintptr_t)pidx % 8))) return SCL_E_NULL;
-  if (mask && (bias || pooled || ((uintptr_t)mask % 16))) return SCL_E_NULL;
-  if ((int64_t)B * H * W * cin >= (int64_t)1 << 31) return SCL_E_SHAPE;   // 32-bit element offsets
-  if (pooled && (!bias || ((uintptr_t)pooled % 16))) return SCL_E_NULL;
-  if (B < 1 || H < 1 || W < 1 || (int64_t)B * H * W > (int64_t)1 << 30) return SCL_E_SHAPE;
-  if (((uintptr_t)x % 16) || (out && ((uintptr_t)out % 16))) return SCL_E_SHAPE;
-  if (!scl_aligned256(workspace) || workspace_bytes < scl_conv3x3_workspace_bytes())
-    return SCL_E_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-#define SCL_CONV_CASE(CI, KO)                                                                  \
-  if (cin == CI && kout == KO)                                                                 \
-    return launch_conv3x3<CI, KO>(x, w, w_stride_k, w_stride_c, w_stride_h, w_stride_w,        \
-                                  transposed, B, H, W, out, bias, relu ? 1 : 0, pooled,        \
-                                  mask, pidx, uidx, workspace, st);
+  if (c.uidx && (!c.mask || c.cin != c.kout || ((c.H | c.W) & 1) || ((uintptr_t)c.uidx % 8))) return SCL_E_SHAPE;
+  if (c.pidx && (!c.pooled || !c.bias || c.mask || ((uintptr_t)c.pidx % 8))) return SCL_E_NULL;
+  if (c.mask && (c.bias || c.pooled || ((uintptr_t)c.mask % 16))) return SCL_E_NULL;
+  if ((int64_t)c.B * c.H * c.W * c.cin >= (int64_t)1 << 31) return SCL_E_SHAPE;   // 32-bit element offsets
+  if (c.pooled && (!c.bias || ((uintptr_t)c.pooled % 16))) return SCL_E_NULL;
+  if (c.B < 1 || c.H < 1 || c.W < 1 || (int64_t)c.B * c.H * c.W > (int64_t)1 << 30) return SCL_E_SHAPE;
+  if (((uintptr_t)c.x % 16) || (c.out && ((uintptr_t)c.out % 16))) return SCL_E_SHAPE;
+  if (!scl_aligned256(c.workspace) || workspace_bytes < scl_conv3x3_workspace_bytes()) return SCL_E_WORKSPACE;
 #ifdef SCL_DIAG
-  {
-    int rc;
-    if (conv3x3_diag(x, w, w_stride_k, w_stride_c, w_stride_h, w_stride_w, transposed, B, H, W, cin, kout, out,
-                     bias, relu, pooled, mask, pidx, uidx, workspace, st, &rc))
-      return rc;
-  }
+  if (int rc; conv3x3_diag(c, &rc)) return rc;
 #endif
-  SCL_CONV_CASE(64, 64)
-  SCL_CONV_CASE(64, 128)
-  SCL_CONV_CASE(128, 64)
-  SCL_CONV_CASE(128, 128)
-#undef SCL_CONV_CASE
+  if (c.cin == 64 && c.kout == 64) return launch_conv3x3<64, 64>(c);
+  if (c.cin == 64 && c.kout == 128) return launch_conv3x3<64, 128>(c);
+  if (c.cin == 128 && c.kout == 64) return launch_conv3x3<128, 64>(c);
+  if (c.cin == 128 && c.kout == 128) return launch_conv3x3<128, 128>(c);
   return SCL_E_SHAPE;
 }
 
-extern "C" int scl_conv3x3_fused(const void* x, const void* w, int64_t w_stride_k,
-                                 int64_t w_stride_c, int64_t w_stride_h, int64_t w_stride_w,
-                                 int transposed, int B, int H, int W, int cin, int kout,
-                                 void* out, const float* bias, int relu, void* pooled,
-                                 void* workspace, size_t workspace_bytes, void* stream) {
-  return conv3x3_dispatch(x, w, w_stride_k, w_stride_c, w_stride_h, w_stride_w, transposed, B, H,
-                          W, cin, kout, out, bias, relu, pooled, nullptr, nullptr, workspace,
-                          workspace_bytes, stream);
+extern "C" int scl_conv3x3_fused(const void* x, const void* w, int64_t w_stride_k, int64_t w_stride_c,
+    int64_t w_stride_h, int64_t w_stride_w, int transposed, int B, int H, int W, int cin, int kout, void* out,
+    const float* bias, int relu, void* pooled, void* workspace, size_t workspace_bytes, void* stream) {
+  RegConvCall c{x, w, w_stride_k, w_stride_c, w_stride_h, w_stride_w, transposed, B, H, W, cin, kout};
+  c.out = out, c.bias = bias, c.relu = relu, c.pooled = pooled, c.workspace = workspace, c.stream = (hipStream_t)stream;
+  return reg_conv(c, workspace_bytes);
 }
 
-extern "C" int scl_conv3x3_pool_idx(const void* x, const void* w, int64_t w_stride_k,
-                                    int64_t w_stride_c, int64_t w_stride_h, int64_t w_stride_w,
-                                    int flags, int B, int H, int W, int cin, int kout,
-                                    const float* bias, void* pooled, void* pool_idx,
-                                    void* workspace, size_t workspace_bytes, void* stream) {
+extern "C" int scl_conv3x3_pool_idx(const void* x, const void* w, int64_t w_stride_k, int64_t w_stride_c,
+    int64_t w_stride_h, int64_t w_stride_w, int flags, int B, int H, int W, int cin, int kout, const float* bias,
+    void* pooled, void* pool_idx, void* workspace, size_t workspace_bytes, void* stream) {
   if (!pool_idx || !pooled || !bias) return SCL_E_NULL;
-  return conv3x3_dispatch(x, w, w_stride_k, w_stride_c, w_stride_h, w_stride_w, flags & 6, B, H, W, cin,
-                          kout, nullptr, bias, 0, pooled, nullptr, pool_idx, workspace,
-                          workspace_bytes, stream);
+  RegConvCall c{x, w, w_stride_k, w_stride_c, w_stride_h, w_stride_w, flags & 6, B, H, W, cin, kout};
+  c.bias = bias, c.pooled = pooled, c.pidx = pool_idx, c.workspace = workspace, c.stream = (hipStream_t)stream;
+  return reg_conv(c, workspace_bytes);
 }
 
-extern "C" int scl_conv3x3_masked(const void* x, const void* w, int64_t w_stride_k,
-                                  int64_t w_stride_c, int64_t w_stride_h, int64_t w_stride_w,
-                                  int transposed, int B, int H, int W, int cin, int kout,
-                                  void* out, const void* mask, void* workspace,
-                                  size_t workspace_bytes, void* stream) {
+extern "C" int scl_conv3x3_masked(const void* x, const void* w, int64_t w_stride_k, int64_t w_stride_c,
+    int64_t w_stride_h, int64_t w_stride_w, int transposed, int B, int H, int W, int cin, int kout, void* out,
+    const void* mask, void* workspace, size_t workspace_bytes, void* stream) {
   if (!mask) return SCL_E_NULL;
-  return conv3x3_dispatch(x, w, w_stride_k, w_stride_c, w_stride_h, w_stride_w, transposed, B, H,
-                          W, cin, kout, out, nullptr, 0, nullptr, mask, nullptr, workspace,
-                          workspace_bytes, stream);
+  RegConvCall c{x, w, w_stride_k, w_stride_c, w_stride_h, w_stride_w, transposed, B, H, W, cin, kout};
+  c.out = out, c.mask = mask, c.workspace = workspace, c.stream = (hipStream_t)stream;
+  return reg_conv(c, workspace_bytes);
 }
 
 extern "C" int scl_conv3x3_masked_pooled(const void* g_pooled, const void* pool_idx, const void* w,
-                                         int64_t w_stride_k, int64_t w_stride_c,
-                                         int64_t w_stride_h, int64_t w_stride_w, int flags, int B,
-                                         int H, int W, int cin, int kout, void* out,
-                                         const void* mask, void* workspace,
-                                         size_t workspace_bytes, void* stream) {
+    int64_t w_stride_k, int64_t w_stride_c, int64_t w_stride_h, int64_t w_stride_w, int flags, int B, int H, int W,
+    int cin, int kout, void* out, const void* mask, void* workspace, size_t workspace_bytes, void* stream) {
   if (!mask || !pool_idx) return SCL_E_NULL;
-  return conv3x3_dispatch(g_pooled, w, w_stride_k, w_stride_c, w_stride_h, w_stride_w, flags, B, H,
-                          W, cin, kout, out, nullptr, 0, nullptr, mask, nullptr, workspace,
-                          workspace_bytes, stream, pool_idx);
+  RegConvCall c{g_pooled, w, w_stride_k, w_stride_c, w_stride_h, w_stride_w, flags, B, H, W, cin, kout};
+  c.out = out, c.mask = mask, c.uidx = pool_idx, c.workspace = workspace, c.stream = (hipStream_t)stream;
+  return reg_conv(c, workspace_bytes);
 }
 
-extern "C" int scl_conv3x3(const void* x, const void* w, int64_t w_stride_k, int64_t w_stride_c,
-                           int64_t w_stride_h, int64_t w_stride_w, int transposed, int B, int H,
-                           int W, int cin, int kout, void* out, void* workspace,
-                           size_t workspace_bytes, void* stream) {
-  return scl_conv3x3_fused(x, w, w_stride_k, w_stride_c, w_stride_h, w_stride_w, transposed, B, H,
-                           W, cin, kout, out, nullptr, 0, nullptr, workspace, workspace_bytes,
-                           stream);
+extern "C" int scl_conv3x3(const void* x, const void* w, int64_t w_stride_k, int64_t w_stride_c, int64_t w_stride_h,
+    int64_t w_stride_w, int transposed, int B, int H, int W, int cin, int kout, void* out, void* workspace,
+    size_t workspace_bytes, void* stream) {
+  RegConvCall c{x, w, w_stride_k, w_stride_c, w_stride_h, w_stride_w, transposed, B, H, W, cin, kout};
+  c.out = out, c.workspace = workspace, c.stream = (hipStream_t)stream;
+  return reg_conv(c, workspace_bytes);
 }
 
 extern "C" size_t scl_conv64_workspace_bytes(void) { return scl_conv3x3_workspace_bytes(); }
 
-extern "C" int scl_conv64(const void* x, const void* w, int64_t w_stride_k, int64_t w_stride_c,
-                          int64_t w_stride_h, int64_t w_stride_w, int transposed, int B, int H,
-                          int W, void* out, void* workspace, size_t workspace_bytes,
-                          void* stream) {
-  return scl_conv3x3(x, w, w_stride_k, w_stride_c, w_stride_h, w_stride_w, transposed, B, H, W,
-                     64, 64, out, workspace, workspace_bytes, stream);
+extern "C" int scl_conv64(const void* x, const void* w, int64_t w_stride_k, int64_t w_stride_c, int64_t w_stride_h,
+    int64_t w_stride_w, int transposed, int B, int H, int W, void* out, void* workspace, size_t workspace_bytes,
+    void* stream) {
+  RegConvCall c{x, w, w_stride_k, w_stride_c, w_stride_h, w_stride_w, transposed, B, H, W, 64, 64};
+  c.out = out, c.workspace = workspace, c.stream = (hipStream_t)stream;
+  return reg_conv(c, workspace_bytes);
+}
+
+// ---- weight gradient ---------------------------------------------------------------------
+
+// The workspace: two slabs [9][64][64] per workgroup — at most (kSclMaxConvCus CUs rounded up to whole
+// (cb, kb) block sets) workgroups — then the bias partials [slab][kout] of scl_wrw3x3_bias.  Over a
+// null workspace it only measures (`bytes`).
+struct WrwSpace { float *slabs, *bslabs; size_t bytes; };
+static WrwSpace wrw_space(void* workspace, int cin, int kout) {
+  const size_t blocks = (size_t)(cin / 64) * (kout / 64);
+  const size_t p = (kSclMaxConvCus + blocks - 1) / blocks;
+  Carver cv(workspace);
+  WrwSpace s;
+  s.slabs = cv.take(2 * p * blocks * 9 * 64 * 64);
+  s.bslabs = cv.take((2 * p + 2) * (size_t)kout);
+  s.bytes = cv.off;
+  return s;
+}
+
+extern "C" size_t scl_wrw3x3_workspace_bytes(int cin, int kout) {
+  if (cin < 64 || kout < 64 || cin % 64 || kout % 64 || cin > 1024 || kout > 1024) return 0;
+  return wrw_space(nullptr, cin, kout).bytes;
 }
 
 static int wrw_splits(int C, int K, int tiles, int cus) {
@@ -1952,144 +2003,137 @@ static int wrw_splits(int C, int K, int tiles, int cus) {
   return p < 1 ? 1 : p;
 }
 
-extern "C" size_t scl_wrw3x3_workspace_bytes(int cin, int kout) {
-  if (cin < 64 || kout < 64 || cin % 64 || kout % 64 || cin > 1024 || kout > 1024) return 0;
-  // slabs: at most (1024 CUs rounded up to whole (cb, kb) block sets) x 147,456 B
-  const size_t blocks = (size_t)(cin / 64) * (kout / 64);
-  const size_t p = (1024 + blocks - 1) / blocks;
-  // two slabs per workgroup + the bias partials [slab][kout] of scl_wrw3x3_bias
-  return scl_round256(2 * p * blocks * 9 * 64 * 64 * sizeof(float)) +
-         scl_round256((2 * p + 2) * (size_t)kout * sizeof(float));
-}
-static size_t wrw_bias_slab_offset(int cin, int kout) {
-  const size_t blocks = (size_t)(cin / 64) * (kout / 64);
-  const size_t p = (1024 + blocks - 1) / blocks;
-  return scl_round256(2 * p * blocks * 9 * 64 * 64 * sizeof(float));
+// How one weight gradient is cut: [64 c] x [64 nkb k] blocks, each over `splits` pixel ranges of
+// `tiles` tiles — wide (8 or 4 rows x 32), or tall (32 or 16 x 8) where that pads the map less — into
+// `nslab` slabs per 64 x 64 block of the `nblk`.
+struct WrwPlan {
+  int nkb;
+  bool tall;
+  int tiles, splits, nslab, nblk;
+  float *slabs, *bslabs;          // bslabs: none without grad_bias
+};
+static WrwPlan wrw_plan(const WrwCall& c, int nkb, bool may_be_tall = true) {
+  WrwPlan p;
+  p.nkb = nkb;
+  const int th_w = nkb == 1 ? 8 : 4, th_t = nkb == 1 ? 32 : 16;
+  const int tiles_wide = c.B * ((c.H + th_w - 1) / th_w) * ((c.W + 31) / 32);
+  const int tiles_tall = c.B * ((c.H + th_t - 1) / th_t) * ((c.W + 7) / 8);
+  p.tall = tiles_tall < tiles_wide && may_be_tall;
+  p.tiles = p.tall ? tiles_tall : tiles_wide;
+  p.splits = wrw_splits(c.cin, c.kout / nkb, p.tiles, scl_conv_cus());
+  p.nslab = nkb == 1 ? 2 * p.splits : p.splits;
+  p.nblk = (c.cin / 64) * (c.kout / 64);
+  const WrwSpace s = wrw_space(c.workspace, c.cin, c.kout);
+  p.slabs = s.slabs;
+  p.bslabs = c.grad_bias ? s.bslabs : nullptr;
+  return p;
 }
 
-// pidx != nullptr: gz is the pooled gradient [B][H/2][W/2][kout], pidx its window positions
-static int wrw3x3_run(const void* x, const void* gz, const unsigned char* pidx, int B, int H, int W,
-                      int cin, int kout, void* gw, int64_t w_stride_k, int64_t w_stride_c,
-                      int64_t w_stride_h, int64_t w_stride_w, int gw_f32, float* grad_bias,
-                      void* workspace, size_t workspace_bytes, void* stream) {
-  if (!x || !gz || !gw || !workspace) return SCL_E_NULL;
-  if (pidx && ((H | W) & 1 || (uintptr_t)pidx % 8)) return SCL_E_SHAPE;
-  const size_t need = scl_wrw3x3_workspace_bytes(cin, kout);
-  if (need == 0 || B < 1 || H < 1 || W < 1 || (int64_t)B * H * W > (int64_t)1 << 30)
-    return SCL_E_SHAPE;
-  if ((int64_t)B * H * W * (cin > kout ? cin : kout) >= (int64_t)1 << 31)
-    return SCL_E_SHAPE;                                 // 32-bit element offsets in the kernel
-  if (((uintptr_t)x % 16) || ((uintptr_t)gz % 16)) return SCL_E_SHAPE;
-  if (!scl_aligned256(workspace) || workspace_bytes < need) return SCL_E_WORKSPACE;
-  static SclDeviceOnce once;
-  scl_call_once(once, [] {
-#define SCL_WRW_ATTR(D, T, N, PL)                                                              \
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wrw64_kernel<D, T, N, PL>),         \
-                            hipFuncAttributeMaxDynamicSharedMemorySize,                        \
-                            (int)WrwCfg<T, N>::LDS);
-    SCL_WRW_ATTR(0, 32, 1, 0) SCL_WRW_ATTR(0, 8, 1, 0) SCL_WRW_ATTR(0, 32, 2, 0) SCL_WRW_ATTR(0, 8, 2, 0)
-    SCL_WRW_ATTR(0, 32, 1, 1) SCL_WRW_ATTR(0, 8, 1, 1) SCL_WRW_ATTR(0, 32, 2, 1) SCL_WRW_ATTR(0, 8, 2, 1)
-#undef SCL_WRW_ATTR
+template <int DBG, int TWv, int NKB, int PL>
+void wrw_launch(const WrwPlan& p, const WrwCall& c) {
+  scl_lds_limit<&wrw64_kernel<DBG, TWv, NKB, PL>>((int)WrwCfg<TWv, NKB>::LDS);
+  SCL_LAUNCH(PL ? "wrw64_kernel<pooled>" : "wrw64_kernel", (wrw64_kernel<DBG, TWv, NKB, PL>),
+             dim3(p.splits * (c.cin / 64) * (c.kout / (64 * NKB))), dim3(512), (WrwCfg<TWv, NKB>::LDS), c.stream,
+             (const unsigned short*)c.x, (const unsigned short*)c.gz, c.B, c.H, c.W, c.cin, c.kout, p.slabs,
+             p.bslabs, c.pidx);
+}
+// f(TWv, NKB, PL), each a std::integral_constant<int, .>: wrw64_kernel takes the tile width (32 wide,
+// 8 tall), the k blocks and the pooled form as template arguments
+template <class F>
+void for_wrw_shape(const WrwPlan& p, bool pooled, F&& f) {
+  using std::integral_constant;
+  auto tile = [&](auto n, auto pl) {
+    if (!p.tall) f(integral_constant<int, 32>{}, n, pl); else f(integral_constant<int, 8>{}, n, pl);
+  };
+  auto blocks = [&](auto pl) {
+    if (p.nkb == 1) tile(integral_constant<int, 1>{}, pl); else tile(integral_constant<int, 2>{}, pl);
+  };
+  if (!pooled) blocks(integral_constant<int, 0>{}); else blocks(integral_constant<int, 1>{});
+}
+// the product's kernel for the plan
+static void wrw_launch_planned(const WrwPlan& p, const WrwCall& c) {
+  for_wrw_shape(p, c.pidx != nullptr, [&](auto t, auto n, auto pl) {
+    wrw_launch<0, decltype(t)::value, decltype(n)::value, decltype(pl)::value>(p, c);
   });
+}
+
+template <int RG>
+void wrw_reduce_launch(const WrwPlan& p, const WrwCall& c) {
+  SCL_LAUNCH("wrw64_reduce_kernel", wrw64_reduce_kernel<RG>, dim3(9 * 64 * 64 / 256, p.nblk), dim3(64 * RG), 0,
+             c.stream, (const float*)p.slabs, p.nslab, c.kout / 64, c.sk, c.sc, c.sh, c.sw, c.gw,
+             c.gw_f32 ? 1 : 0, (const float*)p.bslabs, c.grad_bias);
+}
+// slabs -> gw (+ grad_bias); 16 slab groups per element where few blocks meet many slabs
+static void wrw_reduce(const WrwPlan& p, const WrwCall& c) {
+  if (p.nblk <= 4 && p.nslab >= 32) wrw_reduce_launch<16>(p, c); else wrw_reduce_launch<4>(p, c);
+}
+
+static int wrw3x3_run(const WrwCall& c, size_t workspace_bytes) {
+  if (!c.x || !c.gz || !c.gw || !c.workspace) return SCL_E_NULL;
+  if (c.pidx && ((c.H | c.W) & 1 || (uintptr_t)c.pidx % 8)) return SCL_E_SHAPE;
+  const size_t need = scl_wrw3x3_workspace_bytes(c.cin, c.kout);
+  if (need == 0 || c.B < 1 || c.H < 1 || c.W < 1 || (int64_t)c.B * c.H * c.W > (int64_t)1 << 30)
+    return SCL_E_SHAPE;
+  if ((int64_t)c.B * c.H * c.W * (c.cin > c.kout ? c.cin : c.kout) >= (int64_t)1 << 31)
+    return SCL_E_SHAPE;                                 // 32-bit element offsets in the kernel
+  if (((uintptr_t)c.x % 16) || ((uintptr_t)c.gz % 16)) return SCL_E_SHAPE;
+  if (!scl_aligned256(c.workspace) || workspace_bytes < need) return SCL_E_WORKSPACE;
 #ifdef SCL_DIAG
-  {
-    int rc;
-    if (wrw3x3_diag(x, gz, pidx, B, H, W, cin, kout, gw, w_stride_k, w_stride_c, w_stride_h, w_stride_w, gw_f32,
-                    grad_bias, workspace, need, stream, &rc))
-      return rc;
-  }
+  if (int rc; wrw3x3_diag(c, &rc)) return rc;
 #endif
-  const int cus = scl_conv_cus();
   // [64 c] x [128 k] blocks wherever the output channels allow (scl_debug_set_variant(2100)
-  // pins the 64 x 64 variant); tile shape: wide, or tall where that pads the map less
-  const int nkb = (kout % 128 == 0 && scl_variant() != 2100) ? 2 : 1;
-  const int th_w = nkb == 1 ? 8 : 4, th_t = nkb == 1 ? 32 : 16;
-  const int tiles_wide = B * ((H + th_w - 1) / th_w) * ((W + 31) / 32);
-  const int tiles_tall = B * ((H + th_t - 1) / th_t) * ((W + 7) / 8);
-  const bool tall = tiles_tall < tiles_wide;
-  const int tiles = tall ? tiles_tall : tiles_wide;
-  const int P = wrw_splits(cin, kout, tiles, cus);
-  hipStream_t st = (hipStream_t)stream;
-#define SCL_WRW_LAUNCH(D, T, N, PL)                                                            \
-  SCL_LAUNCH(PL ? "wrw64_kernel<pooled>" : "wrw64_kernel", (wrw64_kernel<D, T, N, PL>),        \
-             dim3(PP * (cin / 64) * (kout / (64 * N))), dim3(512), (WrwCfg<T, N>::LDS), st,    \
-             (const unsigned short*)x, (const unsigned short*)gz, B, H, W, cin, kout,          \
-             (float*)workspace, bslabs, pidx)
-  float* bslabs = grad_bias ? (float*)((char*)workspace + wrw_bias_slab_offset(cin, kout)) : nullptr;
-  int PP = P;
-  if (nkb == 2) {
-    PP = wrw_splits(cin, kout / 2, tiles, cus);
-    if (pidx) {
-      if (tall) SCL_WRW_LAUNCH(0, 8, 2, 1); else SCL_WRW_LAUNCH(0, 32, 2, 1);
-    } else {
-      if (tall) SCL_WRW_LAUNCH(0, 8, 2, 0); else SCL_WRW_LAUNCH(0, 32, 2, 0);
-    }
-  } else if (pidx) {
-    if (tall) SCL_WRW_LAUNCH(0, 8, 1, 1); else SCL_WRW_LAUNCH(0, 32, 1, 1);
-  } else if (tall) SCL_WRW_LAUNCH(0, 8, 1, 0);
-  else SCL_WRW_LAUNCH(0, 32, 1, 0);
-#undef SCL_WRW_LAUNCH
-  const int nslab = nkb == 1 ? 2 * PP : PP, nblk = (cin / 64) * (kout / 64);
-#define SCL_WRW_REDUCE(RG)                                                                     \
-  SCL_LAUNCH("wrw64_reduce_kernel", wrw64_reduce_kernel<RG>, dim3(9 * 64 * 64 / 256, nblk),    \
-             dim3(64 * RG), 0, st, (const float*)workspace, nslab, kout / 64, w_stride_k,      \
-             w_stride_c, w_stride_h, w_stride_w, gw, gw_f32 ? 1 : 0, (const float*)bslabs,     \
-             grad_bias)
-  if (nblk <= 4 && nslab >= 32) SCL_WRW_REDUCE(16); else SCL_WRW_REDUCE(4);
-#undef SCL_WRW_REDUCE
+  // pins the 64 x 64 variant)
+  const int nkb = (c.kout % 128 == 0 && scl_variant() != 2100) ? 2 : 1;
+  const WrwPlan p = wrw_plan(c, nkb);
+  wrw_launch_planned(p, c);
+  wrw_reduce(p, c);
   return scl_launch_status();
 }
 
-extern "C" int scl_wrw3x3_bias(const void* x, const void* gz, int B, int H, int W, int cin,
-                               int kout, void* gw, int64_t w_stride_k, int64_t w_stride_c,
-                               int64_t w_stride_h, int64_t w_stride_w, int gw_f32,
-                               float* grad_bias, void* workspace, size_t workspace_bytes,
-                               void* stream) {
-  return wrw3x3_run(x, gz, nullptr, B, H, W, cin, kout, gw, w_stride_k, w_stride_c, w_stride_h,
-                    w_stride_w, gw_f32, grad_bias, workspace, workspace_bytes, stream);
+extern "C" int scl_wrw3x3_bias(const void* x, const void* gz, int B, int H, int W, int cin, int kout, void* gw,
+    int64_t w_stride_k, int64_t w_stride_c, int64_t w_stride_h, int64_t w_stride_w, int gw_f32, float* grad_bias,
+    void* workspace, size_t workspace_bytes, void* stream) {
+  return wrw3x3_run(WrwCall{x, gz, nullptr, B, H, W, cin, kout, gw, w_stride_k, w_stride_c, w_stride_h,
+                            w_stride_w, gw_f32, grad_bias, workspace, (hipStream_t)stream}, workspace_bytes);
 }
 
-extern "C" int scl_wrw3x3_pooled(const void* x, const void* g_pooled, const void* pool_idx, int B,
-                                 int H, int W, int cin, int kout, void* gw, int64_t w_stride_k,
-                                 int64_t w_stride_c, int64_t w_stride_h, int64_t w_stride_w,
-                                 int gw_f32, float* grad_bias, void* workspace,
-                                 size_t workspace_bytes, void* stream) {
+extern "C" int scl_wrw3x3_pooled(const void* x, const void* g_pooled, const void* pool_idx, int B, int H, int W,
+    int cin, int kout, void* gw, int64_t w_stride_k, int64_t w_stride_c, int64_t w_stride_h, int64_t w_stride_w,
+    int gw_f32, float* grad_bias, void* workspace, size_t workspace_bytes, void* stream) {
   if (!pool_idx) return SCL_E_NULL;
-  return wrw3x3_run(x, g_pooled, (const unsigned char*)pool_idx, B, H, W, cin, kout, gw,
-                    w_stride_k, w_stride_c, w_stride_h, w_stride_w, gw_f32, grad_bias, workspace,
-                    workspace_bytes, stream);
+  return wrw3x3_run(WrwCall{x, g_pooled, (const unsigned char*)pool_idx, B, H, W, cin, kout, gw, w_stride_k,
+                            w_stride_c, w_stride_h, w_stride_w, gw_f32, grad_bias, workspace, (hipStream_t)stream},
+                    workspace_bytes);
 }
 
-extern "C" int scl_wrw3x3_ex(const void* x, const void* gz, int B, int H, int W, int cin, int kout,
-                             void* gw, int64_t w_stride_k, int64_t w_stride_c, int64_t w_stride_h,
-                             int64_t w_stride_w, int gw_f32, void* workspace,
-                             size_t workspace_bytes, void* stream) {
+extern "C" int scl_wrw3x3_ex(const void* x, const void* gz, int B, int H, int W, int cin, int kout, void* gw,
+    int64_t w_stride_k, int64_t w_stride_c, int64_t w_stride_h, int64_t w_stride_w, int gw_f32, void* workspace,
+    size_t workspace_bytes, void* stream) {
   return scl_wrw3x3_bias(x, gz, B, H, W, cin, kout, gw, w_stride_k, w_stride_c, w_stride_h,
                          w_stride_w, gw_f32, nullptr, workspace, workspace_bytes, stream);
 }
 
-extern "C" int scl_wrw3x3(const void* x, const void* gz, int B, int H, int W, int cin, int kout,
-                          void* gw, int64_t w_stride_k, int64_t w_stride_c, int64_t w_stride_h,
-                          int64_t w_stride_w, void* workspace, size_t workspace_bytes,
-                          void* stream) {
-  return scl_wrw3x3_ex(x, gz, B, H, W, cin, kout, gw, w_stride_k, w_stride_c, w_stride_h,
-                       w_stride_w, 0, workspace, workspace_bytes, stream);
+extern "C" int scl_wrw3x3(const void* x, const void* gz, int B, int H, int W, int cin, int kout, void* gw,
+    int64_t w_stride_k, int64_t w_stride_c, int64_t w_stride_h, int64_t w_stride_w, void* workspace,
+    size_t workspace_bytes, void* stream) {
+  return scl_wrw3x3_bias(x, gz, B, H, W, cin, kout, gw, w_stride_k, w_stride_c, w_stride_h,
+                         w_stride_w, 0, nullptr, workspace, workspace_bytes, stream);
 }
 
 extern "C" size_t scl_wrw64_workspace_bytes(void) { return scl_wrw3x3_workspace_bytes(64, 64); }
 
-extern "C" int scl_wrw64(const void* x, const void* gz, int B, int H, int W, void* gw,
-                         int64_t w_stride_k, int64_t w_stride_c, int64_t w_stride_h,
-                         int64_t w_stride_w, void* workspace, size_t workspace_bytes,
-                         void* stream) {
-  return scl_wrw3x3(x, gz, B, H, W, 64, 64, gw, w_stride_k, w_stride_c, w_stride_h, w_stride_w,
-                    workspace, workspace_bytes, stream);
+extern "C" int scl_wrw64(const void* x, const void* gz, int B, int H, int W, void* gw, int64_t w_stride_k,
+    int64_t w_stride_c, int64_t w_stride_h, int64_t w_stride_w, void* workspace, size_t workspace_bytes,
+    void* stream) {
+  return scl_wrw3x3_bias(x, gz, B, H, W, 64, 64, gw, w_stride_k, w_stride_c, w_stride_h, w_stride_w,
+                         0, nullptr, workspace, workspace_bytes, stream);
 }
 
+// ---- first layer -------------------------------------------------------------------------
+
 extern "C" int scl_conv_first(const float* img, const float* avg, const void* w, int64_t w_stride_k,
-                              int64_t w_stride_c, int64_t w_stride_h, int64_t w_stride_w,
-                              int w_f32, const float* bias, int B, int H, int W, void* x0,
-                              void* y, void* stream) {
+    int64_t w_stride_c, int64_t w_stride_h, int64_t w_stride_w, int w_f32, const float* bias, int B, int H, int W,
+    void* x0, void* y, void* stream) {
   if (!img || !avg || !w || !bias || !x0 || !y) return SCL_E_NULL;
   if (B < 1 || H < 1 || W < 1 || (int64_t)B * H * W > (int64_t)1 << 30) return SCL_E_SHAPE;
   if ((uintptr_t)y % 16) return SCL_E_SHAPE;
@@ -2106,15 +2150,11 @@ extern "C" int scl_conv_first(const float* img, const float* avg, const void* w,
   return scl_launch_status();
 }
 
-extern "C" int scl_conv_first_pool_idx(const float* img, const float* avg, const void* w1,
-                                       int64_t w1_stride_k, int64_t w1_stride_c,
-                                       int64_t w1_stride_h, int64_t w1_stride_w, int w1_f32,
-                                       const float* bias1, const void* w2, int64_t w2_stride_k,
-                                       int64_t w2_stride_c, int64_t w2_stride_h,
-                                       int64_t w2_stride_w, int w2_flags, const float* bias2, int B,
-                                       int H, int W, void* x0, void* y1, void* pooled,
-                                       void* pool_idx, void* workspace, size_t workspace_bytes,
-                                       void* stream) {
+extern "C" int scl_conv_first_pool_idx(const float* img, const float* avg, const void* w1, int64_t w1_stride_k,
+    int64_t w1_stride_c, int64_t w1_stride_h, int64_t w1_stride_w, int w1_f32, const float* bias1, const void* w2,
+    int64_t w2_stride_k, int64_t w2_stride_c, int64_t w2_stride_h, int64_t w2_stride_w, int w2_flags,
+    const float* bias2, int B, int H, int W, void* x0, void* y1, void* pooled, void* pool_idx, void* workspace,
+    size_t workspace_bytes, void* stream) {
   if (!img || !avg || !w1 || !bias1 || !w2 || !bias2 || !x0 || !y1 || !pooled || !pool_idx ||
       !workspace)
     return SCL_E_NULL;
@@ -2123,20 +2163,10 @@ extern "C" int scl_conv_first_pool_idx(const float* img, const float* avg, const
   if (w2_flags & SCL_CONV_TRANSPOSED) return SCL_E_SHAPE;
   if (!scl_aligned256(workspace) || workspace_bytes < scl_conv3x3_workspace_bytes())
     return SCL_E_WORKSPACE;
-  using Cfg = ConvCfg<64, 64>;
-  static SclDeviceOnce once;
-  scl_call_once(once, [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv12_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kConv12Lds);
-  });
+  scl_lds_limit<&conv12_kernel>((int)kConv12Lds);
   hipStream_t st = (hipStream_t)stream;
-  const unsigned short* packed = (const unsigned short*)workspace;
-  if (w2_flags & SCL_W_PACKED)
-    packed = (const unsigned short*)w2;                  // scl_conv_pack_batch wrote it
-  else
-    SCL_LAUNCH("conv3x3_pack_kernel", (conv3x3_pack_kernel<64, 64>),
-               dim3(Cfg::NT * Cfg::KS * 512 / 256), dim3(256), 0, st, w2, w2_stride_k, w2_stride_c,
-               w2_stride_h, w2_stride_w, w2_flags & SCL_W_F32, (unsigned short*)workspace);
+  const unsigned short* packed = reg_weights<64, 64>(w2, w2_stride_k, w2_stride_c, w2_stride_h, w2_stride_w,
+                                                     w2_flags & (SCL_W_F32 | SCL_W_PACKED), workspace, st);
   const int cus = scl_conv_cus();
   const int tiles = B * ((H + TH - 1) / TH) * ((W + TW - 1) / TW);
   SCL_LAUNCH("conv12_kernel", conv12_kernel, dim3(tiles < cus ? tiles : cus), dim3(512), kConv12Lds,
@@ -2146,42 +2176,50 @@ extern "C" int scl_conv_first_pool_idx(const float* img, const float* avg, const
   return scl_launch_status();
 }
 
-static int first_wrw_grid(int tiles, int cus) { return tiles < 2 * cus ? tiles : 2 * cus; }
-
 extern "C" size_t scl_conv_first_wrw_workspace_bytes(void) {
-  // up to 2048 slabs [64][32] + the four border-sum rows
-  return scl_round256(((size_t)2 * 1024 * 2048 + 256) * sizeof(float));
+  return scl_round256((kFwAux + kFwAuxLen) * sizeof(float));   // the slabs + the four border-sum rows
 }
 
-extern "C" int scl_conv_first_wrw(const void* x0, const void* gz, int B, int H, int W, void* gw,
-                                  int64_t w_stride_k, int64_t w_stride_c, int64_t w_stride_h,
-                                  int64_t w_stride_w, int w_f32, float* gb, const void* w,
-                                  float* davg, void* workspace, size_t workspace_bytes,
-                                  void* stream) {
+// Where the first layer's gradients go: gw (its strides, bf16 or float32), gb [64], and — with the layer's
+// weight w, which has gw's strides and type — the mean gradient davg [3]
+struct FirstGrads {
+  void* gw;
+  int64_t sk, sc, sh, sw;
+  int w_f32;
+  float* gb;
+  const void* w;
+  float* davg;
+};
+// The tail of both first-layer routes: `nslab` slabs of the workspace -> gw, gb and the border sums,
+// then davg from those and the corner pixels (compact = 0: of the gradient map gz; 1: the corner copy)
+static void first_wrw_finish(const FirstGrads& g, void* workspace, int nslab, const unsigned short* corners,
+                             int compact, int B, int H, int W, hipStream_t st) {
+  float* aux = (float*)workspace + kFwAux;
+  SCL_LAUNCH("conv_first_wrw_reduce_kernel", conv_first_wrw_reduce_kernel, dim3(32), dim3(256), 0,
+             st, (const float*)workspace, nslab, g.sk, g.sc, g.sh, g.sw, g.gw, g.w_f32, g.gb, aux);
+  if (g.davg)
+    SCL_LAUNCH("conv_first_davg_kernel", conv_first_davg_kernel, dim3(1), dim3(64), 0, st, corners, g.w,
+               g.w_f32, g.sk, g.sc, g.sh, g.sw, (const float*)g.gb, (const float*)aux, B, H, W, g.davg, compact);
+}
+
+extern "C" int scl_conv_first_wrw(const void* x0, const void* gz, int B, int H, int W, void* gw, int64_t w_stride_k,
+    int64_t w_stride_c, int64_t w_stride_h, int64_t w_stride_w, int w_f32, float* gb, const void* w, float* davg,
+    void* workspace, size_t workspace_bytes, void* stream) {
   if (!x0 || !gz || !gw || !gb || !workspace || (davg && !w)) return SCL_E_NULL;
   if (B < 1 || H < 1 || W < 1 || (int64_t)B * H * W * 64 >= (int64_t)1 << 31) return SCL_E_SHAPE;
   if ((uintptr_t)gz % 16) return SCL_E_SHAPE;
   if (!scl_aligned256(workspace) || workspace_bytes < scl_conv_first_wrw_workspace_bytes())
     return SCL_E_WORKSPACE;
-  static SclDeviceOnce once;
-  scl_call_once(once, [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_first_wrw_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFirstWrwLds);
-  });
+  scl_lds_limit<&conv_first_wrw_kernel>((int)kFirstWrwLds);
   const int cus = scl_conv_cus();
   const int tiles = B * ((H + TH - 1) / TH) * ((W + TW - 1) / TW);
-  const int grid = first_wrw_grid(tiles, cus);
+  const int grid = tiles < 2 * cus ? tiles : 2 * cus;          // two workgroups per CU: <= kFwMaxSlabs slabs
   hipStream_t st = (hipStream_t)stream;
-  float* aux = (float*)workspace + (size_t)2 * 1024 * 2048;
   SCL_LAUNCH("conv_first_wrw_kernel", conv_first_wrw_kernel, dim3(grid), dim3(256), kFirstWrwLds,
              st, (const unsigned short*)x0, (const unsigned short*)gz, B, H, W, (float*)workspace);
-  SCL_LAUNCH("conv_first_wrw_reduce_kernel", conv_first_wrw_reduce_kernel, dim3(32), dim3(256), 0,
-             st, (const float*)workspace, grid, w_stride_k, w_stride_c, w_stride_h, w_stride_w,
-             gw, w_f32 ? 1 : 0, gb, aux);
-  if (davg)      // w has the strides of gw (the layer's bf16 weight)
-    SCL_LAUNCH("conv_first_davg_kernel", conv_first_davg_kernel, dim3(1), dim3(64), 0, st,
-               (const unsigned short*)gz, w, w_f32 ? 1 : 0, w_stride_k, w_stride_c, w_stride_h,
-               w_stride_w, (const float*)gb, (const float*)aux, B, H, W, davg, 0);
+  // w has the strides of gw (the layer's bf16 weight)
+  first_wrw_finish(FirstGrads{gw, w_stride_k, w_stride_c, w_stride_h, w_stride_w, w_f32 ? 1 : 0, gb, w, davg},
+                   workspace, grid, (const unsigned short*)gz, 0, B, H, W, st);
   return scl_launch_status();
 }
 
@@ -2189,16 +2227,15 @@ extern "C" int scl_conv_first_wrw(const void* x0, const void* gz, int B, int H, 
 // out of the same launch (conv3x3_kernel<64, 64, 3, 1, FW = 1>; then the two small kernels of
 // scl_conv_first_wrw).  g_pooled / pool_idx / w2 / mask as scl_conv3x3_masked_pooled (64 -> 64
 // channels, H and W even); x0 / gw1 / gb1 / w1 / davg / fw_workspace as scl_conv_first_wrw.
-extern "C" int scl_conv3x3_masked_pooled_first_wrw(
-    const void* g_pooled, const void* pool_idx, const void* w2, int64_t w2_stride_k, int64_t w2_stride_c,
-    int64_t w2_stride_h, int64_t w2_stride_w, int flags, int B, int H, int W, const void* mask,
-    const void* x0, void* gw1, int64_t w1_stride_k, int64_t w1_stride_c, int64_t w1_stride_h,
-    int64_t w1_stride_w, int w1_f32, float* gb1, const void* w1, float* davg, void* workspace,
-    size_t workspace_bytes, void* fw_workspace, size_t fw_workspace_bytes, void* stream) {
+extern "C" int scl_conv3x3_masked_pooled_first_wrw(const void* g_pooled, const void* pool_idx, const void* w2,
+    int64_t w2_stride_k, int64_t w2_stride_c, int64_t w2_stride_h, int64_t w2_stride_w, int flags, int B, int H,
+    int W, const void* mask, const void* x0, void* gw1, int64_t w1_stride_k, int64_t w1_stride_c, int64_t w1_stride_h,
+    int64_t w1_stride_w, int w1_f32, float* gb1, const void* w1, float* davg, void* workspace, size_t workspace_bytes,
+    void* fw_workspace, size_t fw_workspace_bytes, void* stream) {
   if (!g_pooled || !pool_idx || !w2 || !mask || !x0 || !gw1 || !gb1 || !workspace || !fw_workspace ||
       (davg && !w1))
     return SCL_E_NULL;
-  if (B < 1 || B > 8192 || H < 2 || W < 2 || ((H | W) & 1) ||
+  if (B < 1 || B > kFwMaxBatch || H < 2 || W < 2 || ((H | W) & 1) ||
       (int64_t)B * H * W * 64 >= (int64_t)1 << 31)
     return SCL_E_SHAPE;
   if (((uintptr_t)g_pooled % 16) || ((uintptr_t)mask % 16) || ((uintptr_t)pool_idx % 8)) return SCL_E_SHAPE;
@@ -2208,37 +2245,21 @@ extern "C" int scl_conv3x3_masked_pooled_first_wrw(
   using Cfg = ConvCfg<64, 64>;
   constexpr size_t kLds = Cfg::LDS + (size_t)Cfg::WAVES * 1024 * sizeof(float) +
                           2 * (size_t)WR * WC * 4 * sizeof(unsigned short);
-  static SclDeviceOnce once;
-  scl_call_once(once, [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_kernel<64, 64, 3, 1, 1>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds);
-  });
+  scl_lds_limit<&conv3x3_kernel<64, 64, 3, 1, 1>>((int)kLds);
   hipStream_t st = (hipStream_t)stream;
-  const int cus = scl_conv_cus();
-  const unsigned short* packed = (const unsigned short*)workspace;
   const int transposed = (flags & (SCL_W_F32 | SCL_W_PACKED)) | SCL_CONV_TRANSPOSED;
-  if (flags & SCL_W_PACKED)
-    packed = (const unsigned short*)w2;
-  else
-    SCL_LAUNCH("conv3x3_pack_kernel", (conv3x3_pack_kernel<64, 64>), dim3(Cfg::NT * Cfg::KS * 512 / 256),
-               dim3(256), 0, st, w2, w2_stride_k, w2_stride_c, w2_stride_h, w2_stride_w, transposed,
-               (unsigned short*)workspace);
+  const unsigned short* packed =
+      reg_weights<64, 64>(w2, w2_stride_k, w2_stride_c, w2_stride_h, w2_stride_w, transposed, workspace, st);
+  const int cus = scl_conv_cus();
   const int tiles = B * ((H + Cfg::TH_ - 1) / Cfg::TH_) * ((W + TW - 1) / TW);
-  const int grid = tiles < cus ? tiles : cus;
-  float* aux = (float*)fw_workspace + (size_t)2 * 1024 * 2048;
-  const unsigned short* corners = (const unsigned short*)((float*)fw_workspace + (size_t)1536 * 2048);
+  const int grid = tiles < cus ? tiles : cus;                  // one workgroup per CU: slabs below kFwStamps
   SCL_LAUNCH("conv3x3_kernel<pooled+first_wrw>", (conv3x3_kernel<64, 64, 3, 1, 1>), dim3(grid),
              dim3(Cfg::NTHR), kLds, st, (const unsigned short*)g_pooled, packed, B, H, W,
              (unsigned short*)nullptr, (const float*)nullptr,
              scl_variant() / 1000 == 61 ? (scl_variant() % 1000) << 1 : 0,     // timing ablations / stamps (diagnostic build)
              (unsigned short*)x0, (const unsigned short*)mask, (unsigned char*)fw_workspace,
              (const unsigned char*)pool_idx);
-  SCL_LAUNCH("conv_first_wrw_reduce_kernel", conv_first_wrw_reduce_kernel, dim3(32), dim3(256), 0,
-             st, (const float*)fw_workspace, grid, w1_stride_k, w1_stride_c, w1_stride_h, w1_stride_w,
-             gw1, w1_f32 ? 1 : 0, gb1, aux);
-  if (davg)
-    SCL_LAUNCH("conv_first_davg_kernel", conv_first_davg_kernel, dim3(1), dim3(64), 0, st, corners, w1,
-               w1_f32 ? 1 : 0, w1_stride_k, w1_stride_c, w1_stride_h, w1_stride_w, (const float*)gb1,
-               (const float*)aux, B, H, W, davg, 1);
+  first_wrw_finish(FirstGrads{gw1, w1_stride_k, w1_stride_c, w1_stride_h, w1_stride_w, w1_f32 ? 1 : 0, gb1, w1, davg},
+                   fw_workspace, grid, (const unsigned short*)((float*)fw_workspace + kFwCorners), 1, B, H, W, st);
   return scl_launch_status();
 }

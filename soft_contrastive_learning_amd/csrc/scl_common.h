@@ -307,10 +307,12 @@ static inline int scl_device_cus() {
 }
 
 // CUs the persistent convolution grids may fill: the device's, minus the reserve AS IT IS NOW (it may
-// change between calls: bench.py tries 0 and 8 at N > 1), at most the 1024 the wrw workspace is sized for.
+// change between calls: bench.py tries 0 and 8 at N > 1), at most the kSclMaxConvCus the wrw workspaces
+// are sized for.
+constexpr int kSclMaxConvCus = 1024;
 static inline int scl_conv_cus() {
   const int u = scl_usable_cus(scl_device_cus());
-  return u > 1024 ? 1024 : u;
+  return u > kSclMaxConvCus ? kSclMaxConvCus : u;
 }
 
 // One-time function attributes (dynamic LDS limits) are set once PER DEVICE: a function object

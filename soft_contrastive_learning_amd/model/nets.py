@@ -312,6 +312,27 @@ def _packed_for(w, transposed):
     return ent[3]
 
 
+def _weight_arg(w, transposed):
+    """(tensor to point at, flag word without the direction bit) of the weight ``w`` for one
+    direction: its up-to-date packed image with ``W_PACKED``, or ``w`` itself with ``_wflag``.  The
+    caller holds the tensor until the call has returned."""
+    pk = _packed_for(w, transposed)
+    return (w, _wflag(w)) if pk is None else (pk, L.W_PACKED)
+
+
+_CONV_ENTRY = {'plain': ('scl_conv3x3_fused', 'scl_convg'), 'masked': ('scl_conv3x3_masked', 'scl_convg_masked'),
+               'pool_idx': ('scl_conv3x3_pool_idx', 'scl_convg_pool_idx')}
+
+
+def _conv_entry(lib, form, cin, kout, device):
+    """(entry point, workspace) of an own convolution in one of the forms of ``_CONV_ENTRY``: the
+    register-weights kernels for ``_OWN_CONV_SHAPES``, the LDS-weights kernels for the rest."""
+    reg, lds = _CONV_ENTRY[form]
+    if (cin, kout) in _OWN_CONV_SHAPES:
+        return getattr(lib, reg), L.workspace(lib.scl_conv3x3_workspace_bytes(), device)
+    return getattr(lib, lds), L.workspace(lib.scl_convg_workspace_bytes(cin, kout), device)
+
+
 def _lib_weight(w, x):
     """The weight as the library convolution wants it: activation dtype, channels-last."""
     if w.dtype == x.dtype and w.is_contiguous(memory_format=_CL):
@@ -485,9 +506,8 @@ def conv64(x, w, transposed=False, bias=None, relu=False, pool=False, mask=None,
               2.0 * px * (cin + kout * (1 + (mask is not None) + 0.25 * bool(pool))))
     else:
         _lds_work(2.0 * px * cin * kout * 9, 2.0 * px * (cin + kout * (1 + (mask is not None))))
-    pk = _packed_for(w, transposed)
-    wp = L.ptr(w) if pk is None else L.ptr(pk)            # the weight, or its packed image
-    wflags = (int(bool(transposed)) | _wflag(w)) if pk is None else (int(bool(transposed)) | L.W_PACKED)
+    wt, wflags = _weight_arg(w, transposed)
+    wp, wflags = L.ptr(wt), int(bool(transposed)) | wflags
     if mask is not None:
         if bias is not None or pool or relu:
             raise ValueError("mask excludes the forward tails (bias / relu / pool)")
@@ -503,25 +523,17 @@ def conv64(x, w, transposed=False, bias=None, relu=False, pool=False, mask=None,
                 L.ptr(x), L.ptr(pool_idx.contiguous(memory_format=_CL)), wp, sk, sc, sh, sw, wflags,
                 b, h, wd, cin, kout, L.ptr(out), L.ptr(mask), L.ptr(ws), ws.numel(), L.stream_of(x)))
             return out
-        ws = L.workspace(lib.scl_conv3x3_workspace_bytes() if own
-                         else lib.scl_convg_workspace_bytes(cin, kout), x.device)
-        fn = lib.scl_conv3x3_masked if own else lib.scl_convg_masked
+        fn, ws = _conv_entry(lib, 'masked', cin, kout, x.device)
         L.check(fn(L.ptr(x), wp, sk, sc, sh, sw, wflags, b, h, wd,
                    cin, kout, L.ptr(out), L.ptr(mask), L.ptr(ws), ws.numel(), L.stream_of(x)))
         return out
-    if (cin, kout) not in _OWN_CONV_SHAPES:
-        if pool:
-            raise ValueError("the fused pooling epilogue exists for the register kernels only")
-        ws = L.workspace(lib.scl_convg_workspace_bytes(cin, kout), x.device)
-        L.check(lib.scl_convg(L.ptr(x), wp, sk, sc, sh, sw, wflags,
-                              b, h, wd, cin, kout, L.ptr(out), L.ptr(bias), int(bool(relu)),
-                              L.ptr(ws), ws.numel(), L.stream_of(x)))
-        return out
-    ws = L.workspace(lib.scl_conv3x3_workspace_bytes(), x.device)
-    L.check(lib.scl_conv3x3_fused(L.ptr(x), wp, sk, sc, sh, sw,
-                                  wflags, b, h, wd, cin, kout,
-                                  L.ptr(out), L.ptr(bias), int(bool(relu)), L.ptr(pooled),
-                                  L.ptr(ws), ws.numel(), L.stream_of(x)))
+    own = (cin, kout) in _OWN_CONV_SHAPES
+    if pool and not own:
+        raise ValueError("the fused pooling epilogue exists for the register kernels only")
+    fn, ws = _conv_entry(lib, 'plain', cin, kout, x.device)
+    tail = (L.ptr(pooled),) if own else ()                # (scl_convg has no pooled output)
+    L.check(fn(L.ptr(x), wp, sk, sc, sh, sw, wflags, b, h, wd, cin, kout, L.ptr(out), L.ptr(bias),
+               int(bool(relu)), *tail, L.ptr(ws), ws.numel(), L.stream_of(x)))
     return (out, pooled) if pool else out
 
 
@@ -675,12 +687,9 @@ def conv_pool_idx(x, w, bias, out=None):
               b * h * wd * (2.0 * cin + 0.75 * kout))       # in + pooled bf16 / 4 + index / 4
     else:
         _lds_work(2.0 * b * h * wd * cin * kout * 9, b * h * wd * (2.0 * cin + 0.75 * kout))
-    ws = L.workspace(lib.scl_conv3x3_workspace_bytes() if own
-                     else lib.scl_convg_workspace_bytes(cin, kout), x.device)
-    fn = lib.scl_conv3x3_pool_idx if own else lib.scl_convg_pool_idx
-    pk = _packed_for(w, False)
-    L.check(fn(L.ptr(x), L.ptr(w) if pk is None else L.ptr(pk), sk, sc, sh, sw,
-               _wflag(w) if pk is None else L.W_PACKED, b, h, wd, cin, kout,
+    fn, ws = _conv_entry(lib, 'pool_idx', cin, kout, x.device)
+    wt, wflags = _weight_arg(w, False)
+    L.check(fn(L.ptr(x), L.ptr(wt), sk, sc, sh, sw, wflags, b, h, wd, cin, kout,
                L.ptr(bias.float().contiguous()), L.ptr(a), L.ptr(idx), L.ptr(ws), ws.numel(),
                L.stream_of(x)))
     return a, idx
@@ -788,9 +797,8 @@ def _masked_pooled_first_wrw(ga, idx, w2, y1, first):
     if w1c.stride() != gw1.stride() or w1c.dtype != gw1.dtype:
         w1c = w1.to(gw1.dtype).contiguous(memory_format=_CL) if gw1.is_contiguous(memory_format=_CL) \
             else w1.to(gw1.dtype).contiguous()
-    pk = _packed_for(w2, True)
-    wp = L.ptr(w2) if pk is None else L.ptr(pk)
-    wflags = _wflag(w2) if pk is None else L.W_PACKED
+    wt2, wflags = _weight_arg(w2, True)
+    wp = L.ptr(wt2)
     s2 = w2.stride()
     s1 = gw1.stride()
     ws = L.workspace(lib.scl_conv3x3_workspace_bytes(), y1.device)
@@ -1120,7 +1128,7 @@ class _FirstConv(torch.autograd.Function):
                                   memory_format=_CL)
                 a_nhwc, idx_nhwc = a.permute(0, 2, 3, 1), idx.permute(0, 2, 3, 1)
                 bias2_f = bias2.float().contiguous()
-                pk2 = _packed_for(w2, False)
+                wt2, w2flags = _weight_arg(w2, False)
                 ws = L.workspace(lib.scl_conv3x3_workspace_bytes(), img.device)
                 s2 = w2.stride()
             for stream, lo, hi in (_split_halves(b) or [(None, 0, b)]):
@@ -1136,8 +1144,7 @@ class _FirstConv(torch.autograd.Function):
                         L.check(lib.scl_conv_first_pool_idx(
                             L.ptr(img[lo:hi]), L.ptr(avg_f), L.ptr(w), sk, sc, sh, sw,
                             int(w.dtype == torch.float32), L.ptr(bias_f),
-                            L.ptr(w2) if pk2 is None else L.ptr(pk2), s2[0], s2[1], s2[2], s2[3],
-                            _wflag(w2) if pk2 is None else L.W_PACKED, L.ptr(bias2_f), n, h, wd,
+                            L.ptr(wt2), s2[0], s2[1], s2[2], s2[3], w2flags, L.ptr(bias2_f), n, h, wd,
                             L.ptr(x0[lo:hi]), L.ptr(y_nhwc[lo:hi]), L.ptr(a_nhwc[lo:hi]),
                             L.ptr(idx_nhwc[lo:hi]), L.ptr(ws), ws.numel(), L.stream_of(img)))
                         continue

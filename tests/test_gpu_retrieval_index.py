@@ -13,6 +13,7 @@ import torch
 
 from oracle import topn_np as TN
 from tests import util_data as U
+from tests.util_guard import FILL, Guarded as _Guarded
 
 pytestmark = pytest.mark.gpu
 
@@ -292,8 +293,7 @@ def test_command_writes_top_n_mains_pickle(dev, tmp_path, monkeypatch, capsys):
 # 4096 bytes on either side must come back untouched; the lists must be the oracle's with nothing handed
 # to the exact fallback (the entry points are called directly: there is none), and a run on a buffer
 # full of 0xA5 must equal a run on a zeroed one — nothing is read before it is written.
-GUARD, FILL = 4096, 0xA5
-F32, BF = 0, 1
+F32, BF = 0, 1    # (the bands: tests/util_guard.py)
 
 
 @functools.lru_cache(maxsize=None)
@@ -304,21 +304,6 @@ def _guard_sets(r, q, n=5):
     for a in out:
         a.setflags(write=False)
     return out
-
-
-class _Guarded:
-    """``nbytes`` device bytes (``.inner``) between two guard bands, all filled with ``fill``."""
-
-    def __init__(self, dev, nbytes, fill):
-        self.fill = fill
-        self.buf = torch.full((nbytes + 2 * GUARD,), fill, dtype=torch.uint8, device=dev)
-        self.inner = self.buf[GUARD:GUARD + nbytes]
-        assert self.inner.data_ptr() % 256 == 0 and self.inner.numel() == nbytes
-
-    def assert_bands_intact(self):
-        torch.cuda.synchronize()
-        assert bool((self.buf[:GUARD] == self.fill).all()), "bytes before the block were written"
-        assert bool((self.buf[-GUARD:] == self.fill).all()), "bytes behind the block were written"
 
 
 def _outputs(dev, q, n, certify=True):
