@@ -311,6 +311,34 @@ int scl_topn_index_query(const float* ref, int R, int d, const void* index, size
                          double* dist_out, unsigned char* uncertified, double* bound_sq,
                          void* workspace, size_t workspace_bytes, int flags, void* stream);
 
+/* A query with a position prior: exact top-n among the references within a radius of a centre.
+ * Reference j has a position (x_j, y_j), query q a centre (cx_q, cy_q) and a radius rad_q, all
+ * float64.  The window of q is W_q = { j : rad_q >= 0 and dx*dx + dy*dy <= rad_q*rad_q } with
+ * dx = x_j - cx_q, dy = y_j - cy_q, evaluated in float64 with every operation rounded on its own
+ * (no fused multiply-add); a negative or NaN radius gives the empty window.  Row q of the outputs
+ * is what scl_topn_l2_cert returns for the rows of W_q (ascending j, so ties still go to the lower
+ * index) and min(n, |W_q|) hits, mapped back to the rows of `ref` (+ idx_offset); the columns from
+ * count_out[q] = min(n, |W_q|) on are index -1 (no offset) and distance +inf.  uncertified /
+ * bound_sq (both or neither) are the certificate over W_q: resolve a flagged query from the
+ * scl_topn_exact_filter candidates that lie inside its window.
+ *
+ * The positions live in a caller-owned geo block beside the index block (scl_topn_geo_bytes; 0:
+ * R < 1): xy [R][2] and one bounding box per 32-reference tile, written by scl_topn_geo_build and
+ * read-only afterwards.  The query is the stream route (Q <= SCL_TOPN_STREAM_MAX_Q, more is
+ * SCL_E_SHAPE; d and n as scl_topn_index_query; workspace as that route's): a tile that no
+ * query's circle can reach is neither loaded nor multiplied, so a call costs what its windows
+ * cover when rows that are close in list order are close on the ground.  center [Q][2] and
+ * radius [Q] are device memory. */
+size_t scl_topn_geo_bytes(int R);
+int scl_topn_geo_build(const double* xy, int R, void* geo, size_t geo_bytes, void* stream);
+size_t scl_topn_index_query_window_workspace_bytes(int R, int Q, int d, int n, int flags);
+int scl_topn_index_query_window(const float* ref, int R, int d, const void* index, size_t index_bytes,
+                                const void* geo, size_t geo_bytes, const float* query, int Q,
+                                const double* center, const double* radius, int n,
+                                int64_t idx_offset, int64_t* idx_out, double* dist_out,
+                                int* count_out, unsigned char* uncertified, double* bound_sq,
+                                void* workspace, size_t workspace_bytes, int flags, void* stream);
+
 /* Exact resolution of uncertified queries: for each listed query, float64 sum (q - r)^2 against
  * EVERY reference row (d <= 256, d % 4 == 0); rows with squared distance <= bound_sq[query] are
  * appended (unordered) to that query's candidate list.  The true top-n are the n smallest

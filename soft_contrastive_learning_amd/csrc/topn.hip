@@ -920,6 +920,137 @@ __global__ __launch_bounds__(256) void topn_stream_score_kernel(const float* __r
   }
 }
 
+// ---- the windowed stream route (scl_topn_index_query_window) ----
+// Every query has a window: the references whose position lies within `radius` of `center`.
+// One query's window against one point, in float64 with every operation rounded on its own (no
+// fused multiply-add): what NumPy's `dx*dx + dy*dy <= r2` decides, bit for bit.  r2 = rad * rad,
+// -1 for a negative radius, NaN for a NaN one: both compare false with everything.
+__device__ __forceinline__ bool window_holds(double x, double y, double cx, double cy, double r2) {
+#pragma clang fp contract(off)
+  const double dx = x - cx, dy = y - cy;
+  return dx * dx + dy * dy <= r2;
+}
+// The same operations on the point of a box [xmin, ymin, xmax, ymax] nearest the centre.  For a
+// reference inside the box |x - cx| >= max(xmin - cx, 0, cx - xmax) holds exactly and rounding is
+// monotone, so the sum here is <= the reference's own: "false" holds for every reference of the box.
+__device__ __forceinline__ bool window_reaches(const double* __restrict__ box, double cx, double cy,
+                                               double r2) {
+#pragma clang fp contract(off)
+  const double dx = fmax(fmax(box[0] - cx, cx - box[2]), 0.0);
+  const double dy = fmax(fmax(box[1] - cy, cy - box[3]), 0.0);
+  return dx * dx + dy * dy <= r2;
+}
+// the float32 whose score_key is all ones, the selection's "empty" key: a score the window masks
+constexpr unsigned kEmptyScoreBits = 0x7fffffffu;
+
+// topn_stream_score_kernel with windows.  xy [R][2] are the references' positions and box [tiles][4]
+// bounds those of each 32-reference tile (the geo block, topn_geo_at).  A wave passes over a tile that
+// no query's circle reaches: no row loads, no products, its [Q][32] scores are the empty marker.  In
+// the other tiles a (query, reference) pair outside the window gets the marker instead of its score,
+// decided per accumulator register from the lane's reference position and the row's circle in LDS
+// (win [32][4] doubles: cx, cy, r2).  Tiles, fragments, prefetch and arithmetic are that kernel's.
+template <int D8>
+__global__ __launch_bounds__(256) void topn_stream_score_window_kernel(
+    const float* __restrict__ ref, const float* __restrict__ refnorm, int R,
+    const float* __restrict__ query, int Q, float* __restrict__ scores, const double* __restrict__ xy,
+    const double* __restrict__ box, const double* __restrict__ center,
+    const double* __restrict__ radius) {
+  constexpr int d = D8 * 8, H = D8 / 2;
+  __shared__ double win[32 * 4];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int r = lane & 31, h = lane >> 5;
+  const int ntiles = (R + 31) / 32;
+  const int nw = gridDim.x * 4;
+  double wcx = 0.0, wcy = 0.0, wr2 = -1.0;                   // lane r: query r's circle (none past Q)
+  if (r < Q) {
+#pragma clang fp contract(off)
+    const double rad = radius[r];
+    wcx = center[2 * r];
+    wcy = center[2 * r + 1];
+    wr2 = rad < 0.0 ? -1.0 : rad * rad;
+  }
+  if (threadIdx.x < 32) {
+    win[4 * r] = wcx;
+    win[4 * r + 1] = wcy;
+    win[4 * r + 2] = wr2;
+  }
+  __syncthreads();
+  // the wave's first tile from `tile` on that some query reaches; the ones passed over get the marker
+  auto reached = [&](int tile) {
+    for (; tile < ntiles; tile += nw) {
+      if (__ballot(window_reaches(box + 4 * (int64_t)tile, wcx, wcy, wr2))) break;   // (wave-uniform)
+      const int ridx = tile * 32 + r;
+      if (ridx < R) {
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+          const int row = acc_row(q, h);
+          if (row < Q) scores[(int64_t)row * R + ridx] = __uint_as_float(kEmptyScoreBits);
+        }
+      }
+    }
+    return tile;
+  };
+  int t = reached(blockIdx.x * 4 + wid);
+  if (t >= ntiles) return;                                   // wave-uniform; no block barriers below
+  f32x4 qf[D8];
+  {
+    const float* qp = query + (int64_t)(r < Q ? r : 0) * d + 4 * h;
+#pragma unroll
+    for (int u = 0; u < D8; ++u) {
+      qf[u] = *reinterpret_cast<const f32x4*>(qp + 8 * u);
+      if (r >= Q) qf[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+  }
+  auto row_of = [&](int tile) {
+    const int row = tile * 32 + r;
+    return ref + (int64_t)(row < R ? row : R - 1) * d + 4 * h;
+  };
+  f32x4 a[H], b[H];
+  {
+    const float* p = row_of(t);
+#pragma unroll
+    for (int u = 0; u < H; ++u) a[u] = *reinterpret_cast<const f32x4*>(p + 8 * u);
+#pragma unroll
+    for (int u = 0; u < H; ++u) b[u] = *reinterpret_cast<const f32x4*>(p + 8 * (H + u));
+  }
+  while (t < ntiles) {
+    const int tn = reached(t + nw);
+    const bool more = tn < ntiles;                           // wave-uniform
+    const float* pn = row_of(more ? tn : t);
+    const int ridx = t * 32 + r;
+    const int rclamp = ridx < R ? ridx : R - 1;
+    const float rn = refnorm[rclamp];
+    const double px = xy[2 * (int64_t)rclamp], py = xy[2 * (int64_t)rclamp + 1];
+    f32x16 acc = zero16();
+#pragma unroll
+    for (int u = 0; u < H; ++u)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) acc = mfma32(qf[u][c], a[u][c], acc);
+    if (more) {
+#pragma unroll
+      for (int u = 0; u < H; ++u) a[u] = *reinterpret_cast<const f32x4*>(pn + 8 * u);
+    }
+#pragma unroll
+    for (int u = 0; u < H; ++u)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) acc = mfma32(qf[H + u][c], b[u][c], acc);
+    if (more) {
+#pragma unroll
+      for (int u = 0; u < H; ++u) b[u] = *reinterpret_cast<const f32x4*>(pn + 8 * (H + u));
+    }
+    if (ridx < R) {
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        const int row = acc_row(q, h);
+        const double* w = win + 4 * row;
+        const bool in = window_holds(px, py, w[0], w[1], w[2]);
+        if (row < Q) scores[(int64_t)row * R + ridx] = in ? rn - 2.0f * acc[q] : __uint_as_float(kEmptyScoreBits);
+      }
+    }
+    t = tn;
+  }
+}
+
 // order-preserving image of a float32 score in the unsigned integers, and back
 __device__ __forceinline__ unsigned score_key(float v) {
   const unsigned bits = __float_as_uint(v);
@@ -1023,7 +1154,11 @@ __device__ __forceinline__ void select_finish(const unsigned (&key)[NS], const i
 
 // One step of the selection wave over NE * 64 scores from `base` (NE = 16 for whole steps; the
 // ragged last step of a split takes the smallest of 1, 2, 4, 8, 16 that covers it).
-template <int NE>
+// WIN: a score with the empty key (kEmptyScoreBits: masked by the query's window) is an empty slot,
+// index -1 — never a candidate, however few the split holds — and a step of empty slots only leaves
+// the carried list as it is.  The pre-filter's argument needs no change: with fewer than KEEP lanes
+// that hold a score at all, tub is the empty key and every score of the step survives.
+template <int NE, bool WIN = false>
 __device__ __forceinline__ void stream_select_step(const float* __restrict__ sc, int base, int end,
                                                    int lane, unsigned* lk, int* li, unsigned& ck,
                                                    int& ci) {
@@ -1038,6 +1173,13 @@ __device__ __forceinline__ void stream_select_step(const float* __restrict__ sc,
     const float v = ok ? sc[e] : 0.f;
     key[k + 1] = ok ? score_key(v) : 0xffffffffu;
     idx[k + 1] = ok ? e : -1;
+    if constexpr (WIN) idx[k + 1] = key[k + 1] != 0xffffffffu ? e : -1;
+  }
+  if constexpr (WIN) {
+    bool any = false;
+#pragma unroll
+    for (int k = 1; k <= NE; ++k) any |= idx[k] >= 0;
+    if (!__ballot(any)) return;                              // (wave-uniform)
   }
   if constexpr (NE >= 4) {
     // Pre-filter.  tub = the KEEP-th smallest of the 64 lanes' minima (every lane holds NE >= 4
@@ -1120,6 +1262,188 @@ __global__ __launch_bounds__(256) void topn_stream_select_kernel(const float* __
     const int64_t o = ((int64_t)qi * S + s) * KEEP + lane;
     cand_sc[o] = ci >= 0 ? key_score(ck) : INFINITY;
     cand_ix[o] = ci;
+  }
+}
+
+// topn_stream_select_kernel over a score matrix with masked entries (stream_select_step<NE, true>)
+__global__ __launch_bounds__(256) void topn_stream_select_window_kernel(
+    const float* __restrict__ scores, int R, int S, int per, float* __restrict__ cand_sc,
+    int* __restrict__ cand_ix) {
+  __shared__ unsigned lkey[4][kSelBuf];
+  __shared__ int lidx[4][kSelBuf];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int s = blockIdx.x * 4 + wid, qi = blockIdx.y;
+  if (s >= S) return;                                        // wave-uniform; no block barriers below
+  const float* sc = scores + (int64_t)qi * R;
+  const int begin = s * per;
+  const int end = begin + per < R ? begin + per : R;
+  unsigned ck = 0xffffffffu;
+  int ci = -1;
+  for (int base = begin; base < end; base += 64 * kSelNE) {
+    const int rem = end - base;                              // wave-uniform
+#define SCL_SEL_STEP(NE) stream_select_step<NE, true>(sc, base, end, lane, lkey[wid], lidx[wid], ck, ci)
+    if (rem > 512)
+      SCL_SEL_STEP(16);
+    else if (rem > 256)
+      SCL_SEL_STEP(8);
+    else if (rem > 128)
+      SCL_SEL_STEP(4);
+    else if (rem > 64)
+      SCL_SEL_STEP(2);
+    else
+      SCL_SEL_STEP(1);
+#undef SCL_SEL_STEP
+  }
+  if (lane < KEEP) {
+    const int64_t o = ((int64_t)qi * S + s) * KEEP + lane;
+    cand_sc[o] = ci >= 0 ? key_score(ck) : INFINITY;
+    cand_ix[o] = ci;
+  }
+}
+
+// topn_rerank_kernel<NE> for the windowed stream route: the lists [Q][splits][KEEP] hold members of
+// the query's window only, maybe fewer than n in all.  The stages, their arithmetic (stage 2 sums in
+// that kernel's lane order: the distances are its bits) and the certificate are that kernel's; here
+//   count_out[q] = min(n, nominated), and columns from there on are written as (-1, +inf);
+//   with fewer than n nominated — then every member of the window was, and no list is full — the
+//   n-th distance is +inf, not an unwritten word of LDS, and the query is certified.
+// The certificate holds over the window: a list only drops members that score no better than its
+// largest entry, and the global norm bound covers any subset.
+template <int NE>
+__global__ __launch_bounds__(256) void topn_rerank_window_kernel(
+    const float* __restrict__ ref, const float* __restrict__ query, int Q, int d, int splits, int n,
+    int64_t idx_offset, const float* __restrict__ cand_sc, const int* __restrict__ cand_ix,
+    int64_t* __restrict__ idx_out, double* __restrict__ dist_out, int* __restrict__ count_out,
+    const unsigned* __restrict__ rmax_bits, float eps_q, float eps_r,
+    unsigned char* __restrict__ uncertified, double* __restrict__ bound_sq) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int M = splits * KEEP;                               // <= 64 NE
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int per_wave = 2 * M + KEEP + 2 * (KEEP + 1) + 2 + 66;  // floats: topn_rerank_kernel's (rerank_lds_bytes)
+  int* best_ix = reinterpret_cast<int*>(lds + wid * per_wave + 2 * M);
+  double* best_d = reinterpret_cast<double*>(best_ix + KEEP);   // [KEEP + 1], 8-byte aligned
+  const int qi = blockIdx.x * 4 + wid;
+  if (qi >= Q) return;                                   // wave-uniform; no block barriers below
+
+  float es[NE];
+  int ei[NE];
+  unsigned eu[NE];
+  int nvalid = 0;
+#pragma unroll
+  for (int k = 0; k < NE; ++k) {
+    const int e = k * 64 + lane;
+    es[k] = e < M ? cand_sc[(int64_t)qi * M + e] : INFINITY;
+    ei[k] = e < M ? cand_ix[(int64_t)qi * M + e] : -1;
+    eu[k] = ei[k] >= 0 ? score_key(es[k]) : 0xffffffffu;
+    nvalid += __popcll(__ballot(ei[k] >= 0));
+  }
+  if (lane < KEEP) best_ix[lane] = -1;
+  if (lane == 0) best_d[KEEP] = INFINITY;
+  __builtin_amdgcn_wave_barrier();
+  // stage 1: the KEEP smallest scores (at most KEEP entries: all of them)
+  const unsigned tau_key = nvalid > KEEP ? radix_kth<NE>(eu, KEEP) : 0xffffffffu;
+  // smallest approximate score a window member OUTSIDE the nominated KEEP can have: the merge
+  // threshold when the merge dropped candidates, and the LARGEST entry of every full list (half-wave
+  // = list).  Not its last entry: a list that never saw more than KEEP members is in index order.
+  float tau_excl = nvalid > KEEP ? key_score(tau_key) : INFINITY;
+#pragma unroll
+  for (int k = 0; k < NE; ++k) {
+    const unsigned long long v = __ballot(ei[k] >= 0);
+    const bool full = (lane < 32 ? (unsigned)v : (unsigned)(v >> 32)) == 0xffffffffu;
+    float mx = es[k];
+#pragma unroll
+    for (int m = 1; m < KEEP; m <<= 1) mx = fmaxf(mx, __shfl_xor(mx, m, 64));
+    if (full) tau_excl = fminf(tau_excl, mx);
+  }
+  tau_excl = wave_min(tau_excl);
+  {
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    int base = 0;
+#pragma unroll
+    for (int k = 0; k < NE; ++k) {                        // strictly below the threshold
+      const bool sel = ei[k] >= 0 && eu[k] < tau_key;
+      const unsigned long long m = __ballot(sel);
+      if (sel) best_ix[base + __popcll(m & lt)] = ei[k];
+      base += __popcll(m);
+    }
+#pragma unroll
+    for (int k = 0; k < NE; ++k) {                        // ties at the threshold fill the rest
+      const bool sel = ei[k] >= 0 && eu[k] == tau_key;
+      const unsigned long long m = __ballot(sel);
+      const int pos = base + __popcll(m & lt);
+      if (sel && pos < KEEP) best_ix[pos] = ei[k];
+      base += __popcll(m);
+    }
+  }
+  __builtin_amdgcn_wave_barrier();
+
+  // stage 2: exact float64 distances, four 16-lane groups on four candidates at a time
+  const int grp = lane >> 4, gl = lane & 15;
+  const float* qp = query + (int64_t)qi * d;
+#pragma unroll 2
+  for (int t = 0; t < KEEP / 4; ++t) {
+    const int c = 4 * t + grp;
+    const int ri = best_ix[c];
+    double s = 0.0;
+    if (ri >= 0) {
+      const float* rp = ref + (int64_t)ri * d;
+      for (int e = 4 * gl; e < d; e += 64) {
+        const f32x4 qv = *reinterpret_cast<const f32x4*>(qp + e);
+        const f32x4 rv = *reinterpret_cast<const f32x4*>(rp + e);
+#pragma unroll
+        for (int cc = 0; cc < 4; ++cc) {
+          const double df = (double)qv[cc] - (double)rv[cc];
+          s = fma(df, df, s);
+        }
+      }
+    }
+#pragma unroll
+    for (int m = 1; m < 16; m <<= 1) s += __shfl_xor(s, m, 64);
+    if (gl == 0) best_d[c] = ri >= 0 ? s : INFINITY;
+  }
+  __builtin_amdgcn_wave_barrier();
+  // stage 3: order by (distance, index), emit the first n; (-1, +inf) where the window has no more
+  const int found = nvalid < KEEP ? nvalid : KEEP;
+  const int cnt = found < n ? found : n;
+  if (lane >= cnt && lane < n) {                             // (n <= kMaxN < 64)
+    idx_out[(int64_t)qi * n + lane] = -1;
+    dist_out[(int64_t)qi * n + lane] = INFINITY;
+  }
+  if (lane == 0) count_out[qi] = cnt;
+  if (lane < KEEP) {
+    const double md = best_d[lane];
+    const int mi = best_ix[lane];
+    if (mi >= 0) {
+      int rk = 0;
+      for (int o = 0; o < KEEP; ++o) {
+        const int oi = best_ix[o];
+        const double od = best_d[o];
+        rk += oi >= 0 && ((od < md) || (od == md && oi < mi));
+      }
+      if (rk < n) {
+        idx_out[(int64_t)qi * n + rk] = (int64_t)mi + idx_offset;
+        dist_out[(int64_t)qi * n + rk] = sqrt(md);
+      }
+      if (rk == n - 1) best_d[KEEP] = md;                 // exact n-th smallest of the nominated
+    }
+  }
+  if (!uncertified) return;
+  // the certificate of topn_rerank_kernel
+  double qq = 0.0;
+  for (int e = lane; e < d; e += 64) {
+    const double v = (double)qp[e];
+    qq = fma(v, v, qq);
+  }
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) qq += __shfl_xor(qq, m, 64);
+  __builtin_amdgcn_wave_barrier();
+  if (lane == 0) {
+    const double dn = best_d[KEEP];
+    const double rmax = sqrt((double)__uint_as_float(*rmax_bits));
+    const double eps = (double)eps_q * sqrt(qq) * rmax + (double)eps_r * rmax * rmax;
+    const bool ok = !(tau_excl < INFINITY) || dn < (double)tau_excl + qq - eps;
+    uncertified[qi] = ok ? 0 : 1;
+    bound_sq[qi] = dn;
   }
 }
 
@@ -1337,6 +1661,54 @@ hipError_t topn_prepare(const TopnIndex& x, const float* ref, int R, int d, int 
   return hipSuccess;
 }
 
+// The geo block, what a windowed query needs of the references' positions: filled by topn_geo_kernel
+// (scl_topn_geo_build), read-only afterwards.
+struct TopnGeo {
+  double* xy;            // [R][2] positions
+  double* box;           // [ceil(R / 32)][4]: xmin, ymin, xmax, ymax of the stream score kernel's tile
+  size_t bytes;
+};
+inline TopnGeo topn_geo_at(const void* block, int R) {   // nullptr: for .bytes
+  Carver c(const_cast<void*>(block));
+  TopnGeo g{};
+  g.xy = c.take<double>((size_t)R * 2);
+  g.box = c.take<double>((size_t)((R + 31) / 32) * 4);
+  g.bytes = c.off;
+  return g;
+}
+// grid ceil(R / 256), block 256: thread = reference row, half-wave = tile.  A NaN coordinate (a
+// reference no window holds) leaves the box to the others; a tile of NaNs only gets +inf / -inf.
+__global__ __launch_bounds__(256) void topn_geo_kernel(const double* __restrict__ xy, int R,
+                                                       double* __restrict__ xy_out,
+                                                       double* __restrict__ box) {
+  const int row = blockIdx.x * 256 + threadIdx.x;
+  double lo[2] = {INFINITY, INFINITY}, hi[2] = {-INFINITY, -INFINITY};
+  if (row < R) {
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      const double v = xy[2 * (int64_t)row + c];
+      xy_out[2 * (int64_t)row + c] = v;
+      lo[c] = fmin(lo[c], v);
+      hi[c] = fmax(hi[c], v);
+    }
+  }
+#pragma unroll
+  for (int m = 1; m < 32; m <<= 1) {
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      lo[c] = fmin(lo[c], __shfl_xor(lo[c], m, 64));
+      hi[c] = fmax(hi[c], __shfl_xor(hi[c], m, 64));
+    }
+  }
+  if ((threadIdx.x & 31) == 0 && row < R) {
+    double* b = box + 4 * (int64_t)(row / 32);
+    b[0] = lo[0];
+    b[1] = lo[1];
+    b[2] = hi[0];
+    b[3] = hi[1];
+  }
+}
+
 // The stream route's split of the reference axis: at most 32 lists per query (the re-rank keeps
 // 32 * KEEP candidates per query in LDS), each over at least one step of the selection wave.
 struct StreamPlan {
@@ -1349,6 +1721,15 @@ inline StreamPlan stream_plan(int R) {
   p.per = (R + s - 1) / s;
   p.splits = (R + p.per - 1) / p.per;
   return p;
+}
+
+// Workgroups of the stream score kernel: one wave per 32-reference tile until the chip is full: 4
+// waves per CU at d = 256 (a wave holds the query fragment and a tile: 332 registers), 8 at d = 128
+// (204), 12 at d = 64 (140), 16 at 32
+inline int stream_score_wgs(int R, int d) {
+  const int ntiles = (R + 31) / 32;
+  const int max_wg = d == 256 ? 256 : (d == 128 ? 512 : (d == 64 ? 768 : 1024));
+  return (ntiles + 3) / 4 < max_wg ? (ntiles + 3) / 4 : max_wg;
 }
 
 // The candidate lists of a route and what it computes on the way to them:
@@ -1535,11 +1916,7 @@ extern "C" int scl_topn_index_query(const float* ref, int R, int d, const void* 
   // stream route: always scores from the float32 rows (the score flag only sizes the index)
   const StreamPlan sp = stream_plan(R);
   const TopnLists w = topn_lists_at(workspace, R, Q, 0, kStream);
-  // one wave per 32-reference tile until the chip is full: 4 waves per CU at d = 256 (a wave holds
-  // the query fragment and a tile: 332 registers), 8 at d = 128 (204), 12 at d = 64 (140), 16 at 32
-  const int ntiles = (R + 31) / 32;
-  const int max_wg = d == 256 ? 256 : (d == 128 ? 512 : (d == 64 ? 768 : 1024));
-  const int wgs = (ntiles + 3) / 4 < max_wg ? (ntiles + 3) / 4 : max_wg;
+  const int wgs = stream_score_wgs(R, d);
   for_width(d, [&](auto d8) {
     SCL_LAUNCH("topn_stream_score_kernel", topn_stream_score_kernel<decltype(d8)::value>, dim3(wgs),
                dim3(256), 0, st, ref, (const float*)x.refnorm, R, query, Q, w.scores);
@@ -1548,6 +1925,79 @@ extern "C" int scl_topn_index_query(const float* ref, int R, int d, const void* 
              dim3(256), 0, st, (const float*)w.scores, R, sp.splits, sp.per, w.cs, w.ci);
   launch_rerank(ref, query, Q, d, sp.splits, n, idx_offset, w.cs, w.ci, idx_out, dist_out, x.rmax_bits,
                 topn_eps(d, 0), uncertified, bound_sq, st);
+  return scl_launch_status();
+}
+
+// ---- the windowed query: the stream route over the references inside each query's circle ----
+// (the geo block: topn_geo_at)
+extern "C" size_t scl_topn_geo_bytes(int R) { return R >= 1 ? topn_geo_at(nullptr, R).bytes : 0; }
+
+extern "C" int scl_topn_geo_build(const double* xy, int R, void* geo, size_t geo_bytes, void* stream) {
+  if (!xy || !geo) return SCL_E_NULL;
+  if (R < 1 || ((uintptr_t)xy % 8)) return SCL_E_SHAPE;
+  const TopnGeo g = topn_geo_at(geo, R);
+  if (!scl_aligned256(geo) || geo_bytes < g.bytes) return SCL_E_WORKSPACE;
+  SCL_LAUNCH("topn_geo_kernel", topn_geo_kernel, dim3((R + 255) / 256), dim3(256), 0,
+             (hipStream_t)stream, xy, R, g.xy, g.box);
+  return scl_launch_status();
+}
+
+// the stream route's score matrix and lists (topn_lists_at)
+extern "C" size_t scl_topn_index_query_window_workspace_bytes(int R, int Q, int d, int n, int flags) {
+  if (!topn_shape_ok(R, Q, d, n) || Q > SCL_TOPN_STREAM_MAX_Q || !topn_flags_ok(flags)) return 0;
+  return topn_lists_at(nullptr, R, Q, 0, kStream).bytes;
+}
+
+extern "C" int scl_topn_index_query_window(const float* ref, int R, int d, const void* index,
+                                           size_t index_bytes, const void* geo, size_t geo_bytes,
+                                           const float* query, int Q, const double* center,
+                                           const double* radius, int n, int64_t idx_offset,
+                                           int64_t* idx_out, double* dist_out, int* count_out,
+                                           unsigned char* uncertified, double* bound_sq,
+                                           void* workspace, size_t workspace_bytes, int flags,
+                                           void* stream) {
+  if (!ref || !index || !geo || !query || !center || !radius || !idx_out || !dist_out || !count_out ||
+      !workspace)
+    return SCL_E_NULL;
+  if ((uncertified == nullptr) != (bound_sq == nullptr)) return SCL_E_NULL;
+  if (!topn_shape_ok(R, Q, d, n) || Q > SCL_TOPN_STREAM_MAX_Q) return SCL_E_SHAPE;
+  if (((uintptr_t)ref % 16) || ((uintptr_t)query % 16) || ((uintptr_t)center % 8) ||
+      ((uintptr_t)radius % 8))
+    return SCL_E_SHAPE;
+  const int bf = flags & SCL_TOPN_SCORE_BF16X3;
+  const TopnIndex x = topn_index_at(index, R, d, bf);   // read-only here, like the geo block
+  const TopnGeo g = topn_geo_at(geo, R);
+  if (!scl_aligned256(index) || index_bytes < x.bytes) return SCL_E_WORKSPACE;
+  if (!scl_aligned256(geo) || geo_bytes < g.bytes) return SCL_E_WORKSPACE;
+  if (!scl_aligned256(workspace) || workspace_bytes < topn_lists_at(nullptr, R, Q, 0, kStream).bytes)
+    return SCL_E_WORKSPACE;
+  if (!topn_flags_ok(flags)) return SCL_E_KIND;
+  hipStream_t st = (hipStream_t)stream;
+  const StreamPlan sp = stream_plan(R);
+  const TopnLists w = topn_lists_at(workspace, R, Q, 0, kStream);
+  const int wgs = stream_score_wgs(R, d);
+  for_width(d, [&](auto d8) {
+    SCL_LAUNCH("topn_stream_score_window_kernel", topn_stream_score_window_kernel<decltype(d8)::value>,
+               dim3(wgs), dim3(256), 0, st, ref, (const float*)x.refnorm, R, query, Q, w.scores,
+               (const double*)g.xy, (const double*)g.box, center, radius);
+  });
+  SCL_LAUNCH("topn_stream_select_window_kernel", topn_stream_select_window_kernel,
+             dim3((sp.splits + 3) / 4, Q), dim3(256), 0, st, (const float*)w.scores, R, sp.splits, sp.per,
+             w.cs, w.ci);
+  const int M = sp.splits * KEEP;
+  const TopnEps eps = topn_eps(d, 0);
+#define SCL_RERANK(NE)                                                                              \
+  SCL_LAUNCH("topn_rerank_window_kernel", topn_rerank_window_kernel<NE>, dim3((Q + 3) / 4), dim3(256), \
+             rerank_lds_bytes(M), st, ref, query, Q, d, sp.splits, n, idx_offset, (const float*)w.cs, \
+             (const int*)w.ci, idx_out, dist_out, count_out, (const unsigned*)x.rmax_bits, eps.q,   \
+             eps.r, uncertified, bound_sq)
+  if (M <= 256)
+    SCL_RERANK(4);
+  else if (M <= 512)
+    SCL_RERANK(8);
+  else
+    SCL_RERANK(16);
+#undef SCL_RERANK
   return scl_launch_status();
 }
 

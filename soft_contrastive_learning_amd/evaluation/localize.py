@@ -8,6 +8,11 @@ the references (``top_n.thin_reference``, evaluation/top-n.py:91-94), whitens th
 (``retrieval.RetrievalIndex``) and then answers every call with one streaming pass of
 csrc/topn.hip over the index.  The lists are the certified exact ones of ``retrieval.topn_l2``.
 
+A tracking caller knows roughly where the vehicle is: ``near`` / ``radius`` restrict a call to the
+references within ``radius`` metres of ``near`` (``RetrievalIndex.query``'s window: still the exact
+top-n, of those references), so a look-alike place elsewhere on the map cannot match and the pass
+over the index costs what the window covers.
+
 The command feeds a query set through a ``Localizer`` ``--batch`` frames at a time and writes the
 pickle ``top_n.main`` writes (evaluation/top-n.py:119), so the two can be compared file by file.
 """
@@ -27,8 +32,8 @@ class Localizer:
     hits per frame, ``l`` the thinning distance in metres.
 
     ``query_fn(ref_f, query_f, n) -> (dist [Q,n], idx [Q,n])`` on NumPy arrays replaces the index
-    in the CPU tests of the bookkeeping around it; the product path has no such argument and no
-    CPU fallback."""
+    in the CPU tests of the bookkeeping around it (a window is applied there by subsetting the
+    rows on the host); the product path has no such argument and no CPU fallback."""
 
     def __init__(self, ref_desc, ref_xy, pca=None, model=None, n=5, l=0.0, score='f32', device='cuda',
                  query_fn=None):
@@ -51,7 +56,8 @@ class Localizer:
             self._index = None
             return
         self.device = torch.device(device)
-        self._index = retrieval.RetrievalIndex(self._whiten(rows), 0, score)
+        self._index = retrieval.RetrievalIndex(self._whiten(rows), 0, score,
+                                               positions=self.ref_xy[self._orig])
 
     def _whiten(self, rows):
         """[m, E] NumPy or tensor -> what the index holds: device float32 rows (NumPy with query_fn)."""
@@ -62,32 +68,60 @@ class Localizer:
         t = rows if isinstance(rows, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(rows))
         return t.to(self.device, torch.float32).contiguous()
 
-    def query_thinned(self, desc):
-        """desc [Q, E] -> (feature_dist [Q, n] float64, rows of the THINNED list [Q, n] int64), NumPy."""
+    def query_thinned(self, desc, near=None, radius=None):
+        """desc [Q, E] -> (feature_dist [Q, n] float64, rows of the THINNED list [Q, n] int64), NumPy.
+        ``near`` [Q, 2] (or one [2] for all) and ``radius`` (a scalar or [Q]), in the units of ref_xy:
+        only references within ``radius`` of ``near`` are searched; a frame with fewer than n of
+        them gets row -1 and distance inf in the columns that are left."""
         f = self._whiten(desc if isinstance(desc, torch.Tensor) else np.asarray(desc, dtype=np.float32))
-        if self._query_fn is not None:
-            dist, idx = self._query_fn(self._ref_f, f, self.n)
-            return np.asarray(dist, dtype=np.float64), np.asarray(idx, dtype=np.int64)
-        stats = {}
-        dist, idx = self._index.query(f, self.n, stats=stats)
-        self.uncertified += stats.get('uncertified') or 0
-        return dist.cpu().numpy(), idx.cpu().numpy()
+        if near is None and radius is None:
+            if self._query_fn is not None:
+                dist, idx = self._query_fn(self._ref_f, f, self.n)
+                return np.asarray(dist, dtype=np.float64), np.asarray(idx, dtype=np.int64)
+            stats = {}
+            dist, idx = self._index.query(f, self.n, stats=stats)
+            self.uncertified += stats.get('uncertified') or 0
+            return dist.cpu().numpy(), idx.cpu().numpy()
+        if near is None or radius is None:
+            raise ValueError('a window needs both near and radius')
+        q = len(f)
+        near = np.array(np.broadcast_to(np.asarray(near, dtype=np.float64), (q, 2)))
+        radius = np.array(np.broadcast_to(np.asarray(radius, dtype=np.float64), (q,)))
+        if self._query_fn is None:
+            stats = {}
+            dist, idx = self._index.query(f, self.n, stats=stats, near=near, radius=radius)
+            self.uncertified += stats.get('uncertified') or 0
+            return dist.cpu().numpy(), idx.cpu().numpy()
+        xy = self.ref_xy[self._orig]
+        dist = np.full((q, self.n), np.inf, dtype=np.float64)
+        idx = np.full((q, self.n), -1, dtype=np.int64)
+        for k in range(q):
+            dx, dy = xy[:, 0] - near[k, 0], xy[:, 1] - near[k, 1]
+            member = np.nonzero((radius[k] >= 0) & (dx * dx + dy * dy <= radius[k] * radius[k]))[0]
+            m = min(self.n, len(member))
+            if m:
+                dd, ii = self._query_fn(self._ref_f[member], f[k:k + 1], m)
+                dist[k, :m], idx[k, :m] = np.asarray(dd)[0], member[np.asarray(ii)[0]]
+        return dist, idx
 
-    def locate_descriptors(self, desc):
+    def locate_descriptors(self, desc, near=None, radius=None):
         """desc [Q, E] -> (idx [Q, n] original reference indices, feature_dist [Q, n] float64,
-        xy [Q, n, 2]); ``xy[:, 0]`` is the position estimate."""
-        dist, local = self.query_thinned(desc)
-        idx = self._orig[local]
-        return idx, dist, self.ref_xy[idx]
+        xy [Q, n, 2]); ``xy[:, 0]`` is the position estimate.  With ``near`` / ``radius`` (see
+        ``query_thinned``) a missing hit is index -1, distance inf and position NaN."""
+        dist, local = self.query_thinned(desc, near, radius)
+        found = local >= 0
+        idx = np.where(found, self._orig[np.where(found, local, 0)], -1)
+        xy = np.where(found[..., None], self.ref_xy[np.where(found, idx, 0)], np.nan)
+        return idx, dist, xy
 
-    def locate(self, images):
+    def locate(self, images, near=None, radius=None):
         """images [B, H, W, {1|3}] raw 0..255 -> ``locate_descriptors`` of ``nets.output``."""
         from ..model import nets
         model = self.model or nets.default_model()
         with torch.no_grad():
             t = images if isinstance(images, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(images))
             desc = nets.output(t.to(next(model.parameters()).device), model=model).float()
-        return self.locate_descriptors(desc)
+        return self.locate_descriptors(desc, near, radius)
 
     def prepare_raw(self, frames, rule='resize_img', **kw):
         """Frames as the camera or the decoder delivers them (uint8 [SH,SW,C] or [n,SH,SW,C],
@@ -102,9 +136,9 @@ class Localizer:
             self._resizer = DeviceResizer('cpu' if device is None else device)   # a CPU device raises
         return self._resizer.apply(frames, rule, torch.float32, **kw)
 
-    def locate_raw(self, frames, rule='resize_img', **kw):
+    def locate_raw(self, frames, rule='resize_img', near=None, radius=None, **kw):
         """``locate`` of ``prepare_raw(frames, rule, **kw)``."""
-        return self.locate(self.prepare_raw(frames, rule, **kw))
+        return self.locate(self.prepare_raw(frames, rule, **kw), near, radius)
 
     def payload(self, local_idx, feature_dist, full_xy_dists):
         """``top_n.retrieve``'s output list [top_i, top_g_dists, top_f_dists, gt_i, gt_g_dist, ref_idx]
@@ -122,14 +156,30 @@ class Localizer:
         return [top_i, top_g_dists, np.asarray(feature_dist, dtype=np.float64), gt_i, gt_g_dist, ref_idx]
 
 
-def localize_set(loc, query_f, full_xy_dists, batch=1):
-    """Feed the rows of query_f through ``loc`` in list order, ``batch`` at a time -> the payload."""
+def localize_set(loc, query_f, full_xy_dists, batch=1, prior_radius=0.0, stats=None):
+    """Feed the rows of query_f through ``loc`` in list order, ``batch`` at a time -> the payload.
+
+    ``prior_radius`` > 0: every call but the first searches within that many metres of the position
+    estimate (first hit) of the last frame of the call before; a frame whose window holds fewer
+    than n references is searched again without a window.  ``stats['researched']`` counts those."""
     batch = max(int(batch), 1)
     dists, idxs = [], []
+    prior, again = None, 0
     for s in range(0, len(query_f), batch):
-        d, i = loc.query_thinned(query_f[s:s + batch])
+        rows = query_f[s:s + batch]
+        if prior_radius > 0 and prior is not None:
+            d, i = loc.query_thinned(rows, prior, prior_radius)
+            short = np.nonzero(i[:, -1] < 0)[0]
+            if len(short):
+                d[short], i[short] = loc.query_thinned(rows[short])
+                again += len(short)
+        else:
+            d, i = loc.query_thinned(rows)
+        prior = loc.ref_xy[loc._orig[i[-1, 0]]]
         dists.append(d)
         idxs.append(i)
+    if stats is not None:
+        stats['researched'] = again
     return loc.payload(np.concatenate(idxs), np.concatenate(dists), full_xy_dists)
 
 
@@ -147,8 +197,10 @@ class _SklearnRows:
 def main(argv=None, query_fn=None):
     """The flags of ``top_n.main`` with a single --L and --D (0: no whitening), plus --batch: the
     query descriptors go through a ``Localizer`` in list order, --batch at a time; the payload of
-    ``top_n.main`` goes to ``top_n.out_pickle_path``.  Prints queries per second and how many
-    queries needed the exact fallback.  Returns the path written (None: fewer than N references)."""
+    ``top_n.main`` goes to ``top_n.out_pickle_path``.  --prior_radius M (0: off) searches every call but
+    the first within M metres of the call before's last position estimate (``localize_set``).  Prints
+    queries per second, how many queries needed the exact fallback and, with a prior, how many frames
+    were searched a second time.  Returns the path written (None: fewer than N references)."""
     import argparse
     import os
     import time
@@ -170,6 +222,8 @@ def main(argv=None, query_fn=None):
     p.add_argument('--score', default='bf16x3', choices=['f32', 'bf16x3'],
                    help='nomination arithmetic of queries beyond the stream route (the lists are exact either way)')
     p.add_argument('--batch', default=1, type=int, help='frames per call')
+    p.add_argument('--prior_radius', default=0.0, type=float,
+                   help='metres around the previous call\'s last position estimate to search in (0: everywhere)')
     flags = p.parse_args(argv)
     out = out_pickle_path(flags.out_root, flags.query_lv_pickle, flags.L, flags.D)
     if os.path.exists(out):
@@ -195,12 +249,16 @@ def main(argv=None, query_fn=None):
     if query_fn is None:
         torch.cuda.synchronize()
     t0 = time.perf_counter()
-    payload = localize_set(loc, full_query_f, full_xy_dists, flags.batch)
+    stats = {}
+    payload = localize_set(loc, full_query_f, full_xy_dists, flags.batch, flags.prior_radius, stats)
     dt = time.perf_counter() - t0
     os.makedirs(os.path.dirname(out), exist_ok=True)
     io.save_pickle(payload, out)
     print('{} queries, {} per call: {:.1f} queries/s, uncertified {}'.format(
         len(full_query_f), max(flags.batch, 1), len(full_query_f) / max(dt, 1e-9), loc.uncertified))
+    if flags.prior_radius > 0:
+        print('prior radius {:g} m: {} frames searched again without it'.format(
+            flags.prior_radius, stats['researched']))
     return out
 
 

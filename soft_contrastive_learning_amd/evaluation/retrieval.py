@@ -121,9 +121,21 @@ class RetrievalIndex:
     ``stats`` also receives ``route``: 'stream', 'scan', or 'delegate' for what the index does not
     cover (descriptors wider than 256, n > 25: ``topn_l2`` on the stored rows).  A width that is not
     32, 64, 128 or 256 is zero-padded, once here and per query.  The index block and the workspace
-    are tensors owned by the object; use one object per stream."""
+    are tensors owned by the object; use one object per stream.
 
-    def __init__(self, ref, idx_offset=0, score='f32'):
+    ``positions`` [R, 2] (any float type, host or device; kept as float64) gives every reference a
+    place on the ground and lets ``query(.., near=, radius=)`` restrict each query to the references
+    within ``radius`` of its centre — a localiser's position prior.  With ``W_q = {j : radius_q >= 0
+    and dx*dx + dy*dy <= radius_q*radius_q}`` (float64, every operation rounded on its own, as NumPy
+    evaluates that expression; a negative or NaN radius: empty), row q of the answer is
+    ``topn_l2(ref[W_q], query[q:q+1], min(n, |W_q|), 0, score)`` with its indices mapped back to the
+    rows of ``ref`` (+ ``idx_offset``), filled up to n columns with index -1 (no offset) and distance
+    +inf.  ``stats`` then receives ``route='window'``, ``count`` (int32 tensor [Q]: min(n, |W_q|))
+    and ``uncertified``.  The call (``scl_topn_index_query_window``, 32 queries at a time) skips
+    every 32-reference tile that no query's circle reaches, so on a traverse it costs what the
+    windows cover."""
+
+    def __init__(self, ref, idx_offset=0, score='f32', positions=None):
         if score not in SCORE_MODES:
             raise ValueError("score must be one of %s, got %r" % (sorted(SCORE_MODES), score))
         L.require_device(ref)
@@ -136,6 +148,13 @@ class RetrievalIndex:
         self._flags = SCORE_MODES[score]
         self._ws = None
         self._index = None
+        self._geo = None
+        self.positions = None
+        if positions is not None:
+            xy = torch.as_tensor(positions).to(ref.device, torch.float64).contiguous()
+            if xy.dim() != 2 or tuple(xy.shape) != (ref.shape[0], 2):
+                raise ValueError("positions %s must be [%d,2]" % (tuple(xy.shape), ref.shape[0]))
+            self.positions = xy
         if self.width > 256:
             self.ref = ref                             # (topn_l2's wide path; nothing to prepare)
             return
@@ -148,10 +167,17 @@ class RetrievalIndex:
         self._index = L.workspace(nbytes, ref.device)
         L.check(lib.scl_topn_index_build(L.ptr(ref), r, d, L.ptr(self._index), self._index.numel(),
                                          self._flags, L.stream_of(ref)))
+        if self.positions is not None:
+            self._geo = L.workspace(lib.scl_topn_geo_bytes(r), ref.device)
+            L.check(lib.scl_topn_geo_build(L.ptr(self.positions), r, L.ptr(self._geo), self._geo.numel(),
+                                           L.stream_of(ref)))
 
-    def query(self, query, n, certify=True, stats=None):
-        """query [Q, width] float32 on the index's device -> (dist [Q,n] float64, idx [Q,n] int64)."""
+    def query(self, query, n, certify=True, stats=None, near=None, radius=None):
+        """query [Q, width] float32 on the index's device -> (dist [Q,n] float64, idx [Q,n] int64).
+        ``near`` [Q, 2] with ``radius`` (a scalar or [Q]): among the references of each query's window."""
         ref, query = _checked(self.ref, query, n, self.width)
+        if near is not None or radius is not None:
+            return self._query_window(query, n, certify, stats, near, radius)
         if self._index is None or n > MAX_N:
             if stats is not None:
                 stats['route'] = 'delegate'
@@ -173,12 +199,75 @@ class RetrievalIndex:
         return _run(ref, query, n, self.idx_offset, certify, stats, call)
 
 
+    def _query_window(self, query, n, certify, stats, near, radius):
+        """``query`` with windows: ``scl_topn_index_query_window`` on groups of at most
+        ``_lib.TOPN_STREAM_MAX_Q`` queries, then the exact resolution of the flagged ones."""
+        ref = self.ref
+        q, dev = query.shape[0], ref.device
+        if near is None or radius is None:
+            raise ValueError("a window needs both near and radius")
+        if self.positions is None:
+            raise ValueError("near/radius need an index built with positions")
+        if self._geo is None or n > MAX_N:
+            raise ValueError("a windowed query takes descriptors of at most 256 columns and n <= %d, "
+                             "got width %d, n=%d" % (MAX_N, self.width, n))
+        near = torch.as_tensor(near).to(dev, torch.float64).contiguous()
+        if tuple(near.shape) != (q, 2):
+            raise ValueError("near %s must be [%d,2]" % (tuple(near.shape), q))
+        radius = torch.as_tensor(radius).to(dev, torch.float64)
+        if radius.dim() == 0:
+            radius = radius.expand(q)
+        if tuple(radius.shape) != (q,):
+            raise ValueError("radius %s must be a scalar or [%d]" % (tuple(radius.shape), q))
+        radius = radius.contiguous()
+        lib = L.load()
+        r, d = ref.shape
+        query = _pad_width(query, d)
+        idx = torch.empty((q, n), dtype=torch.int64, device=dev)
+        dist = torch.empty((q, n), dtype=torch.float64, device=dev)
+        count = torch.empty(q, dtype=torch.int32, device=dev)
+        flag = torch.empty(q, dtype=torch.uint8, device=dev) if certify else None
+        bound = torch.empty(q, dtype=torch.float64, device=dev) if certify else None
+        step = L.TOPN_STREAM_MAX_Q
+        for s in range(0, q, step):
+            g = min(step, q - s)
+            nbytes = _sized(lib.scl_topn_index_query_window_workspace_bytes(r, g, d, n, self._flags), r, g, d, n)
+            if self._ws is None or self._ws.numel() < nbytes:
+                self._ws = L.workspace(nbytes, dev)
+            part = slice(s, s + g)
+            L.check(lib.scl_topn_index_query_window(
+                L.ptr(ref), r, d, L.ptr(self._index), self._index.numel(), L.ptr(self._geo),
+                self._geo.numel(), L.ptr(query[part]), g, L.ptr(near[part]), L.ptr(radius[part]), n,
+                self.idx_offset, L.ptr(idx[part]), L.ptr(dist[part]), L.ptr(count[part]),
+                None if flag is None else L.ptr(flag[part]), None if bound is None else L.ptr(bound[part]),
+                L.ptr(self._ws), self._ws.numel(), self._flags, L.stream_of(ref)))
+        if stats is not None:
+            stats['route'] = 'window'
+            stats['count'] = count
+        if certify:
+            bad = torch.nonzero(flag).reshape(-1)                      # (synchronises; usually empty)
+            if stats is not None:
+                stats['uncertified'] = int(bad.numel())
+            if bad.numel():
+                _resolve_exactly(ref, query, n, self.idx_offset, bad, bound, dist, idx,
+                                 window=(self.positions, near, radius))
+        return dist, idx
+
+
 _FILTER_CAP = 2048      # candidates within the bound kept per uncertified query
 
 
-def _resolve_exactly(ref, query, n, idx_offset, bad, bound, dist, idx):
+def _in_window(xy, cx, cy, rad):
+    """The window's predicate on float64 tensors that broadcast: every operation rounded on its own."""
+    dx, dy = xy[..., 0] - cx, xy[..., 1] - cy
+    return (rad >= 0) & (dx * dx + dy * dy <= rad * rad)
+
+
+def _resolve_exactly(ref, query, n, idx_offset, bad, bound, dist, idx, window=None):
     """Rows ``bad`` of (dist, idx) recomputed from the exact float64 distances to every
-    reference that lies within the query's bound."""
+    reference that lies within the query's bound.  ``window`` = (positions, near, radius): among
+    the references inside each query's window only (a flagged query's window holds at least n
+    within its bound: the bound is the n-th distance of nominated MEMBERS)."""
     lib = L.load()
     r, d = ref.shape
     dev = ref.device
@@ -191,6 +280,14 @@ def _resolve_exactly(ref, query, n, idx_offset, bad, bound, dist, idx):
         L.check(lib.scl_topn_exact_filter(L.ptr(ref), r, L.ptr(query), d, L.ptr(ql), nq,
                                           L.ptr(bound), _FILTER_CAP, L.ptr(count), L.ptr(cd),
                                           L.ptr(ci), L.stream_of(ref)))
+        if window is not None:
+            xy, near, radius = window
+            rows = ql.long()
+            stored = ci < 2 ** 31 - 1
+            inside = _in_window(xy[ci.clamp(max=r - 1).long()], near[rows, 0:1], near[rows, 1:2],
+                                radius[rows, None]) & stored
+            cd = cd.masked_fill(~inside, float('inf'))
+            ci = ci.masked_fill(~inside, 2 ** 31 - 1)
         # order by (distance, index): stable sort by index first, then by distance
         o = torch.argsort(ci, dim=1, stable=True)
         cd, ci = torch.gather(cd, 1, o), torch.gather(ci, 1, o)
@@ -203,7 +300,13 @@ def _resolve_exactly(ref, query, n, idx_offset, bad, bound, dist, idx):
             # more than _FILTER_CAP references within the n-th distance (thousands of exact
             # duplicates): plain float64 brute force for that query, in reference chunks
             qi = int(ql[k])
-            best_d, best_i = _brute_force_f64(ref, query[qi], n)
+            if window is not None:
+                # (a flagged query: at least n members)
+                member = torch.nonzero(_in_window(xy, near[qi, 0], near[qi, 1], radius[qi])).reshape(-1)
+                best_d, best_i = _brute_force_f64(ref[member], query[qi], n)
+                best_i = member[best_i]
+            else:
+                best_d, best_i = _brute_force_f64(ref, query[qi], n)
             dist[qi] = best_d.sqrt()
             idx[qi] = best_i + idx_offset
 
