@@ -918,6 +918,51 @@ int scl_grad_stats(const float* g, long long n, double* out, unsigned* flag, voi
                    size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Geographic ground truth and hit distances (csrc/geo_eval.hip; evaluation/geo.py): what
+ * evaluation/top-n.py:110-113 reads out of its [Q, R] table of position distances, without the
+ * table.
+ *
+ *   ref_xy    float64 [R][2], query_xy float64 [Q][2]: positions, device memory, 16-byte aligned
+ *   d2(q, j) = dx*dx + dy*dy with dx = x_j - qx, dy = y_j - qy, in float64 with every operation
+ *   rounded on its own (no fused multiply-add).
+ *
+ * scl_geo_nearest: the lexicographically smallest pair (d2(q, j), j) over j = 0 .. R-1, so a tie
+ * goes to the lower row (np.argmin's choice) and the winner is decided on d2, never on its root
+ * (distinct d2 often share one).  idx_out[q] = j, dist_out[q] = sqrt(d2), correctly rounded.  A NaN
+ * d2 never wins, +inf can; where nothing wins (every d2 NaN) idx_out[q] = -1, dist_out[q] = +inf.
+ * Partial winners per (query, reference split) go to the workspace and one small second launch
+ * merges them by the same rule: no atomics, the same bits on every call.  Two routes, chosen from
+ * Q alone: Q <= SCL_GEO_SMALL_Q puts the lanes over the references (one workgroup per query and
+ * split); more queries take one query per lane (SCL_GEO_BLOCK_QUERIES per workgroup) against slabs
+ * of SCL_GEO_SLAB references broadcast from LDS.  Either way a split is a whole number of slabs:
+ *   qblocks = Q <= SCL_GEO_SMALL_Q ? Q : ceil(Q / SCL_GEO_BLOCK_QUERIES)
+ *   slabs = ceil(R / SCL_GEO_SLAB);  want = max(1, SCL_GEO_TARGET_BLOCKS / qblocks)
+ *   slabs_per_split = ceil(slabs / want);  splits = ceil(slabs / slabs_per_split)
+ * workspace: scl_geo_nearest_workspace_bytes(R, Q) bytes (a pure host function; 0: R < 1 or
+ * Q < 1), 256-byte aligned: round256(8 P) + round256(4 P) for P = min(Q slabs, max(Q,
+ * SCL_GEO_TARGET_BLOCKS SCL_GEO_BLOCK_QUERIES)) pairs, a bound on Q splits that grows with Q and
+ * with R (Q splits itself does not: one query more can halve the split count).
+ *
+ * scl_geo_hit_dist: idx int64 [Q][n] (the hit lists of a retrieval call, device memory),
+ * dist_out float64 [Q][n]: dist_out[q][k] = sqrt(d2(q, idx[q][k])) for 0 <= idx[q][k] < R and +inf
+ * for every other index — the -1 a windowed query pads with, and anything out of range: the
+ * launcher cannot see the list, so the kernel reads nothing outside ref_xy whatever it holds.
+ *
+ * Returns SCL_E_NULL for a NULL operand; SCL_E_SHAPE for R < 1, Q < 1, n < 1, Q n > 2^38 or
+ * positions that are not 16-byte aligned; SCL_E_WORKSPACE for a workspace that is too small or not
+ * 256-byte aligned; nothing is launched then.
+ * ------------------------------------------------------------------------- */
+#define SCL_GEO_SLAB 256            /* references per LDS slab; the granule of a split */
+#define SCL_GEO_BLOCK_QUERIES 256   /* queries per workgroup of the query-per-lane route */
+#define SCL_GEO_SMALL_Q 32          /* at most this many queries: lanes over references */
+#define SCL_GEO_TARGET_BLOCKS 1024  /* workgroups the split count aims at */
+size_t scl_geo_nearest_workspace_bytes(int R, int Q);
+int scl_geo_nearest(const double* ref_xy, int R, const double* query_xy, int Q, int64_t* idx_out,
+                    double* dist_out, void* workspace, size_t workspace_bytes, void* stream);
+int scl_geo_hit_dist(const double* ref_xy, int R, const double* query_xy, int Q, const int64_t* idx,
+                     int n, double* dist_out, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Host utility for the checkpoint bundle reader / writer (tf_bundle.py; the reference
  * restores and saves through tf.train.Saver, train/train.py:882-905, 984, 1079, 1102):
  * CRC-32C (Castagnoli, reflected 0x82F63B78) of n bytes continued from `crc` (0 to start),

@@ -41,6 +41,10 @@ PACK_VLAD_W = 16           # SclPackJob.flags: the job writes the NetVLAD plane 
 OPTIM_CHUNK_GROUPS = 1024  # SCL_OPTIM_CHUNK_GROUPS: 16-byte groups per workgroup of scl_apply_*
 FRAMES_U8, FRAMES_F32 = 0, 1   # out_kind of scl_frames_resize
 OPTIM_SEG_WORDS = 6       # SclOptimSeg as int64 words: var, grad, slot0, slot1, n, first_chunk
+GEO_SLAB = 256             # SCL_GEO_SLAB: references per LDS slab of scl_geo_nearest; the granule of a split
+GEO_BLOCK_QUERIES = 256    # SCL_GEO_BLOCK_QUERIES: queries per workgroup of its query-per-lane route
+GEO_SMALL_Q = 32           # SCL_GEO_SMALL_Q: at most this many queries put the lanes over the references
+GEO_TARGET_BLOCKS = 1024   # SCL_GEO_TARGET_BLOCKS: workgroups the split count aims at
 
 _p = ctypes.c_void_p
 _i = ctypes.c_int
@@ -167,6 +171,9 @@ SIGNATURES = {
     "scl_apply_momentum": (_i, [_p, _i, _l, _p, _f, _p, _p]),
     "scl_grad_stats_workspace_bytes": (_z, [_l]),
     "scl_grad_stats": (_i, [_p, _l, _p, _p, _p, _z, _p]),
+    "scl_geo_nearest_workspace_bytes": (_z, [_i, _i]),
+    "scl_geo_nearest": (_i, [_p, _i, _p, _i, _p, _p, _p, _z, _p]),
+    "scl_geo_hit_dist": (_i, [_p, _i, _p, _i, _p, _i, _p, _p]),
 }
 
 _libs = {}

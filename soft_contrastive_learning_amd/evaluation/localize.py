@@ -140,11 +140,27 @@ class Localizer:
         """``locate`` of ``prepare_raw(frames, rule, **kw)``."""
         return self.locate(self.prepare_raw(frames, rule, **kw), near, radius)
 
-    def payload(self, local_idx, feature_dist, full_xy_dists):
+    def payload(self, local_idx, feature_dist, full_xy_dists=None, query_xy=None):
         """``top_n.retrieve``'s output list [top_i, top_g_dists, top_f_dists, gt_i, gt_g_dist, ref_idx]
         (evaluation/top-n.py:110-119) from the hits of ``query_thinned`` for every query, in order, and
-        the queries' geographic distances to ALL references [Q, M]."""
+        either the queries' geographic distances to ALL references [Q, M] (``full_xy_dists``: the
+        reference's table, read bit for bit) or the queries' positions [Q, 2] (``query_xy``: hit
+        distances and ground truth from the index's own positions on the device, evaluation/geo.py —
+        the direct form ``sqrt(dx*dx + dy*dy)``; a missing hit, row -1, is index -1 and distance inf)."""
         ref_idx = self.ref_idx
+        if query_xy is not None:
+            if full_xy_dists is not None:
+                raise ValueError('payload takes full_xy_dists or query_xy, not both')
+            if self._index is None:
+                raise ValueError('query_xy needs the resident index: a Localizer made with query_fn has '
+                                 'no device positions')
+            from .top_n import device_ground_truth
+            hits = torch.from_numpy(np.ascontiguousarray(local_idx, dtype=np.int64)).to(self.device)
+            top_i, top_g_dists, gt_i, gt_g_dist = device_ground_truth(
+                self._index.positions, query_xy, hits, ref_idx)
+            return [top_i, top_g_dists, np.asarray(feature_dist, dtype=np.float64), gt_i, gt_g_dist, ref_idx]
+        if full_xy_dists is None:
+            raise ValueError('payload needs full_xy_dists or query_xy')
         xy_dists = np.asarray(full_xy_dists)[:, ref_idx]
         top_i = np.asarray(local_idx).astype(int)
         num_q = top_i.shape[0]
@@ -156,8 +172,9 @@ class Localizer:
         return [top_i, top_g_dists, np.asarray(feature_dist, dtype=np.float64), gt_i, gt_g_dist, ref_idx]
 
 
-def localize_set(loc, query_f, full_xy_dists, batch=1, prior_radius=0.0, stats=None):
-    """Feed the rows of query_f through ``loc`` in list order, ``batch`` at a time -> the payload.
+def localize_set(loc, query_f, full_xy_dists=None, batch=1, prior_radius=0.0, stats=None, query_xy=None):
+    """Feed the rows of query_f through ``loc`` in list order, ``batch`` at a time -> the payload
+    (``Localizer.payload``: from the table ``full_xy_dists``, or from the positions ``query_xy``).
 
     ``prior_radius`` > 0: every call but the first searches within that many metres of the position
     estimate (first hit) of the last frame of the call before; a frame whose window holds fewer
@@ -180,7 +197,7 @@ def localize_set(loc, query_f, full_xy_dists, batch=1, prior_radius=0.0, stats=N
         idxs.append(i)
     if stats is not None:
         stats['researched'] = again
-    return loc.payload(np.concatenate(idxs), np.concatenate(dists), full_xy_dists)
+    return loc.payload(np.concatenate(idxs), np.concatenate(dists), full_xy_dists, query_xy)
 
 
 class _SklearnRows:
@@ -194,20 +211,10 @@ class _SklearnRows:
         return self._pca.transform(x).astype(np.float32)
 
 
-def main(argv=None, query_fn=None):
-    """The flags of ``top_n.main`` with a single --L and --D (0: no whitening), plus --batch: the
-    query descriptors go through a ``Localizer`` in list order, --batch at a time; the payload of
-    ``top_n.main`` goes to ``top_n.out_pickle_path``.  --prior_radius M (0: off) searches every call but
-    the first within M metres of the call before's last position estimate (``localize_set``).  Prints
-    queries per second, how many queries needed the exact fallback and, with a prior, how many frames
-    were searched a second time.  Returns the path written (None: fewer than N references)."""
+def main_parser():
+    """The flags of ``main``."""
     import argparse
-    import os
-    import time
-    from sklearn.metrics import pairwise_distances
-    from ..util import io
-    from ..util.meta import get_xy
-    from .pca import PCAWhitening
+    from .top_n import GEO_ROUTES
     p = argparse.ArgumentParser()
     p.add_argument('--pca_lv_pickle', required=True)
     p.add_argument('--query_lv_pickle', required=True)
@@ -224,7 +231,30 @@ def main(argv=None, query_fn=None):
     p.add_argument('--batch', default=1, type=int, help='frames per call')
     p.add_argument('--prior_radius', default=0.0, type=float,
                    help='metres around the previous call\'s last position estimate to search in (0: everywhere)')
-    flags = p.parse_args(argv)
+    p.add_argument('--geo', default='table', choices=list(GEO_ROUTES),
+                   help='geographic distances: read out of the [Q, M] table of the reference, or computed from '
+                        'the index\'s positions on the device (no table is built)')
+    return p
+
+
+def main(argv=None, query_fn=None):
+    """The flags of ``top_n.main`` with a single --L and --D (0: no whitening), plus --batch: the
+    query descriptors go through a ``Localizer`` in list order, --batch at a time; the payload of
+    ``top_n.main`` goes to ``top_n.out_pickle_path``.  --prior_radius M (0: off) searches every call but
+    the first within M metres of the call before's last position estimate (``localize_set``).
+    --geo device takes the payload's geographic part from the index's positions (``Localizer.payload``
+    with ``query_xy``) and builds no [Q, M] table; it needs the resident index, so together with
+    ``query_fn`` it raises.  Prints queries per second, how many queries needed the exact fallback
+    and, with a prior, how many frames were searched a second time.  Returns the path written (None:
+    fewer than N references)."""
+    import os
+    import time
+    from ..util import io
+    from ..util.meta import get_xy
+    from .pca import PCAWhitening
+    flags = main_parser().parse_args(argv)
+    if flags.geo == 'device' and query_fn is not None:
+        raise ValueError('--geo device needs the resident index; query_fn (the CPU stand-in) has none')
     out = out_pickle_path(flags.out_root, flags.query_lv_pickle, flags.L, flags.D)
     if os.path.exists(out):
         print('{} already exists. Skipping.'.format(out))
@@ -233,7 +263,10 @@ def main(argv=None, query_fn=None):
     full_query_xy = get_xy(io.load_csv(flags.query_csv))
     full_ref_f = np.array(io.load_pickle(flags.ref_lv_pickle), dtype=np.float32)
     full_query_f = np.array(io.load_pickle(flags.query_lv_pickle), dtype=np.float32)
-    full_xy_dists = pairwise_distances(full_query_xy, full_ref_xy, metric='euclidean')
+    full_xy_dists = None
+    if flags.geo == 'table':
+        from sklearn.metrics import pairwise_distances
+        full_xy_dists = pairwise_distances(full_query_xy, full_ref_xy, metric='euclidean')
     pca = None
     if flags.D > 0:
         pca_f = np.array(io.load_pickle(flags.pca_lv_pickle), dtype=np.float32)
@@ -250,7 +283,8 @@ def main(argv=None, query_fn=None):
         torch.cuda.synchronize()
     t0 = time.perf_counter()
     stats = {}
-    payload = localize_set(loc, full_query_f, full_xy_dists, flags.batch, flags.prior_radius, stats)
+    payload = localize_set(loc, full_query_f, full_xy_dists, flags.batch, flags.prior_radius, stats,
+                           full_query_xy if flags.geo == 'device' else None)
     dt = time.perf_counter() - t0
     os.makedirs(os.path.dirname(out), exist_ok=True)
     io.save_pickle(payload, out)

@@ -198,6 +198,30 @@ class RetrievalIndex:
                                              self._flags, L.stream_of(ref)))
         return _run(ref, query, n, self.idx_offset, certify, stats, call)
 
+    def nearest_position(self, query_xy):
+        """query_xy [Q, 2] (NumPy or a tensor on the index's device) -> (row int64 [Q], dist float64
+        [Q]): the reference whose position is nearest each query's and its distance
+        (``geo.nearest`` on the positions the index was built with: ties to the lower row; rows of
+        ``ref``, + ``idx_offset``)."""
+        from . import geo
+        if self.positions is None:
+            raise ValueError("nearest_position needs an index built with positions")
+        row, dist = geo.nearest(self.positions, query_xy)
+        if self.idx_offset:
+            row = torch.where(row >= 0, row + self.idx_offset, row)
+        return row, dist
+
+    def hit_distances(self, query_xy, idx):
+        """query_xy [Q, 2], idx [Q, n] as ``query`` returns it -> float64 [Q, n]: the distance on the
+        ground between each query and each of its hits (``geo.hit_distances``); +inf for the -1 a
+        windowed query pads with."""
+        from . import geo
+        if self.positions is None:
+            raise ValueError("hit_distances needs an index built with positions")
+        if self.idx_offset:
+            idx = torch.as_tensor(idx).to(self.positions.device)
+            idx = torch.where(idx >= 0, idx - self.idx_offset, idx)
+        return geo.hit_distances(self.positions, query_xy, idx)
 
     def _query_window(self, query, n, certify, stats, near, radius):
         """``query`` with windows: ``scl_topn_index_query_window`` on groups of at most
