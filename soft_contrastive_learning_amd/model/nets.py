@@ -17,6 +17,7 @@ the reference's checkpoint names and shapes (HWIO kernels, [1,1,512,64] assignme
 """
 import math
 
+import collections
 import contextlib
 import os
 import threading
@@ -147,6 +148,14 @@ def _grad_out(p_like):
         if v is not None and v.dtype == p_like.dtype and v.stride() == p_like.stride():
             return v
     return torch.empty_like(p_like)
+
+
+def _bias_grad_out(bias):
+    """Float32 vector to write a bias gradient into: ``_grad_out`` for a float32 parameter, a
+    scratch vector (autograd casts it) for any other."""
+    if bias.dtype == torch.float32:
+        return _grad_out(bias)
+    return torch.empty(bias.numel(), dtype=torch.float32, device=bias.device)
 
 
 def _grad_ret(g, p_like):
@@ -320,17 +329,48 @@ def _weight_arg(w, transposed):
     return (w, _wflag(w)) if pk is None else (pk, L.W_PACKED)
 
 
-_CONV_ENTRY = {'plain': ('scl_conv3x3_fused', 'scl_convg'), 'masked': ('scl_conv3x3_masked', 'scl_convg_masked'),
-               'pool_idx': ('scl_conv3x3_pool_idx', 'scl_convg_pool_idx')}
+# form -> (register-weights entry point, LDS-weights entry point)    after the shape arguments:
+_CONV_ENTRY = {'plain': ('scl_conv3x3_fused', 'scl_convg'),          # out, bias, relu (, pooled: register kernels)
+               'masked': ('scl_conv3x3_masked', 'scl_convg_masked'),                    # out, mask
+               'masked_pooled': ('scl_conv3x3_masked_pooled', None),                    # out, mask
+               'pool_idx': ('scl_conv3x3_pool_idx', 'scl_convg_pool_idx')}              # bias, pooled, idx
 
 
-def _conv_entry(lib, form, cin, kout, device):
-    """(entry point, workspace) of an own convolution in one of the forms of ``_CONV_ENTRY``: the
-    register-weights kernels for ``_OWN_CONV_SHAPES``, the LDS-weights kernels for the rest."""
-    reg, lds = _CONV_ENTRY[form]
-    if (cin, kout) in _OWN_CONV_SHAPES:
-        return getattr(lib, reg), L.workspace(lib.scl_conv3x3_workspace_bytes(), device)
-    return getattr(lib, lds), L.workspace(lib.scl_convg_workspace_bytes(cin, kout), device)
+def _own_conv(form, x, w, transposed, dims, args, idx=None, pool=False):
+    """One launch of an own convolution in a form of ``_CONV_ENTRY``: the register-weights kernels
+    for ``_OWN_CONV_SHAPES``, the LDS-weights kernels for the rest.  ``dims`` = (B, H, W) of the
+    full-size map, ``args`` what the form takes after the shape (tensors, None or ints), ``idx`` the
+    window positions of 'masked_pooled'.  Checks that the form exists for the shape; picks the
+    weight image, the workspace and the entry point; books the work."""
+    lib = L.load()
+    b, h, wd = dims
+    cin, kout = (w.shape[0], w.shape[1]) if transposed else (w.shape[1], w.shape[0])
+    reg = (cin, kout) in _OWN_CONV_SHAPES
+    if x.shape[1] != cin:
+        raise ValueError("input has %d channels, the weight contracts %d" % (x.shape[1], cin))
+    if form == 'masked_pooled' and not (reg and cin == kout):
+        raise ValueError("un-pooling window staging exists for the 64->64 and 128->128 kernels")
+    if pool and not reg:
+        raise ValueError("the fused pooling epilogue exists for the register kernels only")
+    px = b * h * wd
+    if form == 'masked_pooled':             # pooled gradient bf16 / 4 + index / 4; mask; output
+        name, nbytes = 'conv3x3_kernel<pooled>', px * (0.75 * cin + 4.0 * kout)
+    elif form == 'pool_idx':                # in + pooled bf16 / 4 + index / 4
+        name, nbytes = 'conv3x3_kernel', px * (2.0 * cin + 0.75 * kout)
+    else:
+        name, nbytes = 'conv3x3_kernel', 2.0 * px * (cin + kout * (1 + (form == 'masked') + 0.25 * bool(pool)))
+    if reg:
+        _work(name, 2.0 * px * cin * kout * 9, nbytes)
+        ws = L.workspace(lib.scl_conv3x3_workspace_bytes(), x.device)
+    else:
+        _lds_work(2.0 * px * cin * kout * 9, nbytes)
+        ws = L.workspace(lib.scl_convg_workspace_bytes(cin, kout), x.device)
+    wt, wflags = _weight_arg(w, transposed)
+    sk, sc, sh, sw = w.stride()
+    L.check(getattr(lib, _CONV_ENTRY[form][0 if reg else 1])(
+        L.ptr(x), *(() if idx is None else (L.ptr(idx),)), L.ptr(wt), sk, sc, sh, sw,
+        int(bool(transposed)) | wflags, b, h, wd, cin, kout,
+        *(a if isinstance(a, int) else L.ptr(a) for a in args), L.ptr(ws), ws.numel(), L.stream_of(x)))
 
 
 def _lib_weight(w, x):
@@ -338,6 +378,15 @@ def _lib_weight(w, x):
     if w.dtype == x.dtype and w.is_contiguous(memory_format=_CL):
         return w
     return w.to(dtype=x.dtype, memory_format=_CL)
+
+
+def _weight_like_grad(w, gw):
+    """The weight in the dtype and strides of its gradient ``gw``: what the first-layer gradient
+    kernels read next to the gradient they write (for the gradient of the mean)."""
+    if w.stride() == gw.stride() and w.dtype == gw.dtype:
+        return w
+    w = w.to(gw.dtype)
+    return w.contiguous(memory_format=_CL) if gw.is_contiguous(memory_format=_CL) else w.contiguous()
 
 
 def _own_conv_kind(x, w, transposed=False):
@@ -356,7 +405,7 @@ def _own_conv_kind(x, w, transposed=False):
     return None
 
 
-def _lds_conv_pays(x, transposed=False, fused_tail=False, kout=512):
+def _lds_conv_pays(x, transposed=False, kout=512):
     """Own LDS-weights kernel (csrc/conv_lds.hip -> csrc/convh.hip) or the library?  Measured on MI355X
     (scripts/conv_layers.py; profiles/r02 for the bench shapes, profiles/r05/conv_layers_*.txt for
     the small maps): what decides is how many workgroup tiles ([8 rows x 40 px] x 128 output
@@ -380,6 +429,13 @@ def _lds_conv_pays(x, transposed=False, fused_tail=False, kout=512):
 
 def _conv64_ok(x, w, transposed=False):
     return _own_conv_kind(x, w, transposed) is not None
+
+
+def _fwd_route(x, w):
+    """What serves a layer's forward convolution: 'reg' or 'lds' (own kernels) or None (library).
+    Decided here once per layer; the layer functions read the answer."""
+    kind = _own_conv_kind(x, w)
+    return kind if kind != 'lds' or _lds_conv_pays(x, kout=w.shape[0]) else None
 
 
 # The forward pass of the backbone as two half-batches on two streams.  Every kernel of the
@@ -465,7 +521,6 @@ def conv64(x, w, transposed=False, bias=None, relu=False, pool=False, mask=None,
     ``mask``, register kernels with cin == kout): ``x`` is the gradient at the POOLED map and the
     kernel un-pools it by the forward pass's window positions while staging
     (``scl_conv3x3_masked_pooled``)."""
-    lib = L.load()
     L.require_device(x, w, bias, mask, pool_idx)
     x = x.contiguous(memory_format=_CL)
     b, _, h, wd = x.shape
@@ -497,43 +552,19 @@ def conv64(x, w, transposed=False, bias=None, relu=False, pool=False, mask=None,
                 conv64(x[lo:hi], w, False, bias, relu, pool, None, out[lo:hi],
                        pooled[lo:hi] if pool else None)
         return (out, pooled) if pool else out
-    sk, sc, sh, sw = w.stride()
-    px = b * h * wd
-    if pool_idx is not None:                # pooled gradient bf16 / 4 + index / 4; mask; output
-        _work('conv3x3_kernel<pooled>', 2.0 * px * cin * kout * 9, px * (0.75 * cin + 4.0 * kout))
-    elif (cin, kout) in _OWN_CONV_SHAPES:
-        _work('conv3x3_kernel', 2.0 * px * cin * kout * 9,
-              2.0 * px * (cin + kout * (1 + (mask is not None) + 0.25 * bool(pool))))
-    else:
-        _lds_work(2.0 * px * cin * kout * 9, 2.0 * px * (cin + kout * (1 + (mask is not None))))
-    wt, wflags = _weight_arg(w, transposed)
-    wp, wflags = L.ptr(wt), int(bool(transposed)) | wflags
     if mask is not None:
         if bias is not None or pool or relu:
             raise ValueError("mask excludes the forward tails (bias / relu / pool)")
         if tuple(mask.shape) != tuple(out.shape) or mask.dtype != x.dtype:
             raise ValueError("mask must have the output's shape and dtype")
         mask = mask.contiguous(memory_format=_CL)
-        own = (cin, kout) in _OWN_CONV_SHAPES
         if pool_idx is not None:
-            if not (own and cin == kout):
-                raise ValueError("un-pooling window staging exists for the 64->64 and 128->128 kernels")
-            ws = L.workspace(lib.scl_conv3x3_workspace_bytes(), x.device)
-            L.check(lib.scl_conv3x3_masked_pooled(
-                L.ptr(x), L.ptr(pool_idx.contiguous(memory_format=_CL)), wp, sk, sc, sh, sw, wflags,
-                b, h, wd, cin, kout, L.ptr(out), L.ptr(mask), L.ptr(ws), ws.numel(), L.stream_of(x)))
-            return out
-        fn, ws = _conv_entry(lib, 'masked', cin, kout, x.device)
-        L.check(fn(L.ptr(x), wp, sk, sc, sh, sw, wflags, b, h, wd,
-                   cin, kout, L.ptr(out), L.ptr(mask), L.ptr(ws), ws.numel(), L.stream_of(x)))
+            pool_idx = pool_idx.contiguous(memory_format=_CL)
+        _own_conv('masked' if pool_idx is None else 'masked_pooled', x, w, transposed, (b, h, wd),
+                  (out, mask), idx=pool_idx)
         return out
-    own = (cin, kout) in _OWN_CONV_SHAPES
-    if pool and not own:
-        raise ValueError("the fused pooling epilogue exists for the register kernels only")
-    fn, ws = _conv_entry(lib, 'plain', cin, kout, x.device)
-    tail = (L.ptr(pooled),) if own else ()                # (scl_convg has no pooled output)
-    L.check(fn(L.ptr(x), wp, sk, sc, sh, sw, wflags, b, h, wd, cin, kout, L.ptr(out), L.ptr(bias),
-               int(bool(relu)), *tail, L.ptr(ws), ws.numel(), L.stream_of(x)))
+    tail = (pooled,) if (cin, kout) in _OWN_CONV_SHAPES else ()       # (scl_convg has no pooled output)
+    _own_conv('plain', x, w, transposed, (b, h, wd), (out, bias, int(bool(relu))) + tail, pool=pool)
     return (out, pooled) if pool else out
 
 
@@ -581,10 +612,10 @@ def wrw64(x, gz, w_like, bias_grad=None, pool_idx=None):
     return gw
 
 
-def _conv3x3(x, w):
-    """3x3 / stride 1 / same-padding convolution without bias (MIOpen, or conv64)."""
-    kind = _own_conv_kind(x, w)
-    if kind == 'reg' or (kind == 'lds' and _lds_conv_pays(x, kout=w.shape[0])):
+def _conv3x3(x, w, route):
+    """3x3 / stride 1 / same-padding convolution without bias: conv64 or, with ``route`` None
+    (``_fwd_route``), the library."""
+    if route is not None:
         return conv64(x, w, False)
     return torch.ops.aten.convolution(x, _lib_weight(w, x), None, _ONES, _ONES, _ONES, False,
                                       [0, 0], 1)
@@ -661,10 +692,9 @@ def conv_pool_idx(x, w, bias, out=None):
     """conv -> +bias -> max-pool 2x2 -> ReLU with the pooling in the convolution's epilogue and
     NO full-size output: returns (pooled bf16 [B,K,H/2,W/2], idx uint8 of the same shape: the
     window position of each maximum) — ``scl_conv3x3_pool_idx``."""
-    lib = L.load()
     L.require_device(x, w, bias)
     x = x.contiguous(memory_format=_CL)
-    b, cin, h, wd = x.shape
+    b, _, h, wd = x.shape
     kout = w.shape[0]
     if out is None:
         a = torch.empty((b, kout, h // 2, wd // 2), dtype=x.dtype, device=x.device, memory_format=_CL)
@@ -680,23 +710,8 @@ def conv_pool_idx(x, w, bias, out=None):
             with torch.cuda.stream(stream):
                 conv_pool_idx(x[lo:hi], w, bias, (a[lo:hi], idx[lo:hi]))
         return a, idx
-    sk, sc, sh, sw = w.stride()
-    own = (cin, kout) in _OWN_CONV_SHAPES
-    if own:
-        _work('conv3x3_kernel', 2.0 * b * h * wd * cin * kout * 9,
-              b * h * wd * (2.0 * cin + 0.75 * kout))       # in + pooled bf16 / 4 + index / 4
-    else:
-        _lds_work(2.0 * b * h * wd * cin * kout * 9, b * h * wd * (2.0 * cin + 0.75 * kout))
-    fn, ws = _conv_entry(lib, 'pool_idx', cin, kout, x.device)
-    wt, wflags = _weight_arg(w, False)
-    L.check(fn(L.ptr(x), L.ptr(wt), sk, sc, sh, sw, wflags, b, h, wd, cin, kout,
-               L.ptr(bias.float().contiguous()), L.ptr(a), L.ptr(idx), L.ptr(ws), ws.numel(),
-               L.stream_of(x)))
+    _own_conv('pool_idx', x, w, False, (b, h, wd), (bias, a, idx))
     return a, idx
-
-
-def _own_wrw_used(x, gz, w):
-    return _own_wrw_ok(x, gz, w) and _wrw_pays(x)
 
 
 # Weight gradients on a second stream.  Nothing in the backward chain reads a weight gradient:
@@ -790,13 +805,9 @@ def _masked_pooled_first_wrw(ga, idx, w2, y1, first):
     y1 = y1.contiguous(memory_format=_CL)
     b, _, h, wd = y1.shape
     gw1 = _grad_out(w1)
-    gb1 = _grad_out(bias1) if bias1.dtype == torch.float32 else torch.empty(
-        64, dtype=torch.float32, device=y1.device)
+    gb1 = _bias_grad_out(bias1)
     davg = torch.empty(3, dtype=torch.float32, device=y1.device)
-    w1c = w1
-    if w1c.stride() != gw1.stride() or w1c.dtype != gw1.dtype:
-        w1c = w1.to(gw1.dtype).contiguous(memory_format=_CL) if gw1.is_contiguous(memory_format=_CL) \
-            else w1.to(gw1.dtype).contiguous()
+    w1c = _weight_like_grad(w1, gw1)
     wt2, wflags = _weight_arg(w2, True)
     wp = L.ptr(wt2)
     s2 = w2.stride()
@@ -812,85 +823,70 @@ def _masked_pooled_first_wrw(ga, idx, w2, y1, first):
     return gw1, gb1, davg
 
 
-def _conv3x3_backward(gz, x, w, need_x, link=None, gb=None, pooled=None):
-    """(gx, gw) of a 3x3 convolution.  With ``link`` (x is a post-ReLU map whose producer
-    holds the other end) an own backward-data kernel returns gx * [x > 0] and marks the
-    link.  ``gb`` (only where ``_own_wrw_used``): the weight-gradient kernel also writes the
-    bias gradient there.  ``pooled`` = (gradient at the pooled map, window positions) of a layer
-    that ends in the 2x2 max-pooling: the own weight-gradient kernel reads that instead of the
-    full-size ``gz``, and so does the backward-data kernel where it can (then ``gz`` may be
-    None: see ``_pooled_consumers``)."""
-    ga, idx = pooled if pooled is not None else (None, None)
-    g_any = ga if gz is None else gz                      # (channels and dtype are what is looked at)
-    kind = _own_conv_kind(g_any, w, True)
-    own_gx = kind == 'reg' or (kind == 'lds' and _lds_conv_pays(x, True, kout=w.shape[1]))
-    own_gw = _own_wrw_used(x, g_any, w)
-    if gb is not None and not own_gw:
-        raise RuntimeError("bias gradient requested from a weight-gradient pass that is not own")
-    if pooled is not None and not own_gw:
-        raise RuntimeError("pooled gradient handed to a weight-gradient pass that is not own")
+# How one convolution node's backward runs.  gx / gw: 'own' (conv64 / wrw64), 'lib' (the library) or,
+# for gx, None (not needed).  masked: the own backward-data kernel applies the ReLU' of the layer below
+# (mask = x) and marks the link.  pool_w / pool_x: the weight-gradient / backward-data kernel reads the
+# gradient at the POOLED map and un-pools it while staging (pool_x only with pool_w: the full-size
+# gradient is then never written).  first: x is conv1_1's output and the backward-data kernel computes conv1_1's parameter
+# gradients instead of writing gx.
+_BwdRoute = collections.namedtuple('_BwdRoute', 'gx gw masked pool_w pool_x first')
 
-    def own_wrw():
-        if pooled is not None:
-            return _wrw_maybe_async(x, ga, w, gb, pool_idx=idx)
-        return _wrw_maybe_async(x, gz, w, gb)
-    if own_gx and need_x and link is not None and USE_MASKED_BWD:
-        if (gz is None and _fused_first_wrw_wanted() and link.first is not None and own_gw
-                and tuple(w.shape) == (64, 64, 3, 3) and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0):
+
+def _bwd_route(x, g, w, need_x, link=None, pooled=False):
+    """The ``_BwdRoute`` of a 3x3 convolution node, decided once: its backward reads it and hands it
+    to ``_conv3x3_backward``.  ``g``: the gradient at the node's output, full-size or pooled (its
+    channels and dtype are what is looked at); ``link``: x is a post-ReLU map whose producer holds
+    the other end; ``pooled``: the gradient at the pooled map, already masked, and the window
+    positions are at hand.  Which consumers of a pooled gradient can un-pool while they stage —
+    weight gradient: every own shape (csrc/conv64.hip, wrw64_kernel<.., 1>); backward-data: the
+    register kernels with cin == kout — conv1_2 and conv2_2 — in their masked form; conv3_3 /
+    conv4_3 fill their windows by LDS-DMA, which copies bytes as they lie."""
+    kind = _own_conv_kind(g, w, True)
+    own_gx = kind == 'reg' or (kind == 'lds' and _lds_conv_pays(x, True, kout=w.shape[1]))
+    own_gw = _own_wrw_ok(x, g, w) and _wrw_pays(x)
+    masked = bool(need_x) and own_gx and link is not None and USE_MASKED_BWD
+    pool_w = (bool(pooled) and USE_POOLED_BWD and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0
+              and own_gw)
+    pool_x = pool_w and (not need_x or (masked and kind == 'reg' and w.shape[0] == w.shape[1]))
+    first = (pool_x and masked and _fused_first_wrw_wanted() and link.first is not None
+             and tuple(w.shape) == (64, 64, 3, 3))
+    return _BwdRoute(('own' if own_gx else 'lib') if need_x else None, 'own' if own_gw else 'lib',
+                     masked, pool_w, pool_x, first)
+
+
+def _conv3x3_backward(route, gz, x, w, link=None, gb=None, pooled=None):
+    """(gx, gw) of a 3x3 convolution along ``route`` (``_bwd_route``).  ``gb`` (where route.gw is
+    'own'): the weight-gradient kernel also writes the bias gradient there.  ``pooled`` = (gradient
+    at the pooled map, window positions) where route.pool_w; with route.pool_x nothing reads the
+    full-size ``gz``, which may then be None."""
+    ga, idx = pooled if pooled is not None else (None, None)
+    if gz is None and not route.pool_x:
+        raise RuntimeError("the full-size gradient is needed for this backward-data pass")
+    gx = gw = None
+    if route.masked:
+        if route.first:
             # x is conv1_1's output: its gradient map has ONE consumer, the first layer's weight /
             # bias / mean gradient — computed here, the map itself never exists.  What autograd
             # carries down is an UNINITIALISED tensor of its shape that _FirstConv.backward must
             # recognise (same hand-off as the ReLU' mark) and never read.
             gx = torch.empty_like(x)
             link.first_done = _masked_pooled_first_wrw(ga, idx, w, x, link.first)
-            link.mark(gx)
-            return gx, own_wrw()
-        if gz is None:
+        elif route.pool_x:
             gx = conv64(ga, w, True, mask=x, pool_idx=idx)
         else:
             gx = conv64(gz, w, True, mask=x)
         link.mark(gx)
-        if own_gw:
-            return gx, own_wrw()
-        _, gw, _ = torch.ops.aten.convolution_backward(gz, x, _lib_weight(w, gz), None, _ONES,
-                                                       _ONES, _ONES, False, [0, 0], 1,
-                                                       [False, True, False])
-        return gx, gw.to(w.dtype)
-    if gz is None:
-        if need_x:
-            raise RuntimeError("the full-size gradient is needed for this backward-data pass")
-        return None, own_wrw()
-    if own_gx and own_gw:
-        gw = own_wrw()
-        return (conv64(gz, w, True) if need_x else None), gw
-    if own_gx or own_gw:
-        gx = conv64(gz, w, True) if (own_gx and need_x) else None
-        gw = own_wrw() if own_gw else None
-        if (gx is None and need_x) or gw is None:
-            lx, lw, _ = torch.ops.aten.convolution_backward(
-                gz, x, _lib_weight(w, gz), None, _ONES, _ONES, _ONES, False, [0, 0], 1,
-                [bool(need_x) and gx is None, gw is None, False])
-            gx = lx if gx is None else gx
-            gw = lw.to(w.dtype) if gw is None else gw
-        return gx, gw
-    gx, gw, _ = torch.ops.aten.convolution_backward(gz, x, _lib_weight(w, gz), None, _ONES, _ONES,
-                                                    _ONES, False, [0, 0], 1,
-                                                    [bool(need_x), True, False])
-    return gx, gw.to(w.dtype)
-
-
-def _pooled_consumers(x, ga, w, need_x, link):
-    """Which consumers of a pooling layer's gradient can un-pool while they stage:
-    (weight gradient, backward-data).  Weight gradient: every own shape (csrc/conv64.hip,
-    wrw64_kernel<.., 1>).  Backward-data: the register kernels with cin == kout — conv1_2 and
-    conv2_2 — in their masked form; conv3_3 / conv4_3 fill their windows by LDS-DMA, which
-    copies bytes as they lie."""
-    h, wd = x.shape[2], x.shape[3]
-    if not (USE_POOLED_BWD and h % 2 == 0 and wd % 2 == 0 and _own_wrw_used(x, ga, w)):
-        return False, False
-    kind = _own_conv_kind(ga, w, True)
-    return True, (not need_x) or (kind == 'reg' and w.shape[0] == w.shape[1]
-                                  and link is not None and USE_MASKED_BWD)
+    if route.gw == 'own':
+        gw = _wrw_maybe_async(x, ga if route.pool_w else gz, w, gb, idx if route.pool_w else None)
+    if route.gx == 'own' and not route.masked:
+        gx = conv64(gz, w, True)
+    if route.gx == 'lib' or route.gw == 'lib':              # whatever is still missing: the library
+        lx, lw, _ = torch.ops.aten.convolution_backward(
+            gz, x, _lib_weight(w, gz), None, _ONES, _ONES, _ONES, False, [0, 0], 1,
+            [route.gx == 'lib', route.gw == 'lib', False])
+        gx = lx if route.gx == 'lib' else gx
+        gw = lw.to(w.dtype) if route.gw == 'lib' else gw
+    return gx, gw
 
 
 def _glue_dtype(t):
@@ -911,12 +907,12 @@ class _ConvBiasAct(torch.autograd.Function):
         lib = L.load()
         ctx.link_in, ctx.link_out = link_in, (link_out if relu else None)
         ctx.slot = _pack_slot()
-        kind = _own_conv_kind(x, w)
-        if kind == 'reg' or (kind == 'lds' and _lds_conv_pays(x, False, True, kout=w.shape[0])):
+        route = _fwd_route(x, w)
+        if route is not None:
             y = conv64(x, w, False, bias=bias, relu=relu)         # tail fused in the epilogue
         else:
             with _whole_batch_op():
-                y = _conv3x3(x, w).contiguous(memory_format=_CL)
+                y = _conv3x3(x, w, route).contiguous(memory_format=_CL)
                 b, c, h, wd = y.shape
                 _work('bias_act_kernel', 0.0, 2.0 * y.numel() * y.element_size())
                 L.check(lib.scl_vgg_bias_act(L.ptr(y), _glue_dtype(y), L.ptr(bias), b * h * wd, c,
@@ -931,16 +927,16 @@ class _ConvBiasAct(torch.autograd.Function):
         x, w, y, bias = ctx.saved_tensors
         gy = gy.contiguous(memory_format=_CL)
         b, c, h, wd = gy.shape
-        gb = _grad_out(bias) if bias.dtype == torch.float32 else torch.empty(
-            c, dtype=torch.float32, device=gy.device)
+        gb = _bias_grad_out(bias)
         ws = L.workspace(lib.scl_vgg_workspace_bytes(c), gy.device)
         # ReLU' already applied by the layer above (its backward-data epilogue)?
         masked = ctx.link_out is not None and ctx.link_out.take(gy)
         mask_here = ctx.relu and not masked
         gz = torch.empty_like(gy) if mask_here else gy
+        route = _bwd_route(x, gy, w, ctx.needs_input_grad[0], ctx.link_in)
         # nothing to mask: the bias gradient (column sums of gy) comes out of the own
         # weight-gradient kernel, which has gy in LDS anyway — no separate pass over the map
-        fold = USE_BIAS_IN_WRW and not mask_here and _own_wrw_used(x, gy, w)
+        fold = USE_BIAS_IN_WRW and not mask_here and route.gw == 'own'
         if not fold:
             _work('act_bwd_kernel', 0.0, (3.0 if mask_here else 1.0) * gy.numel() * gy.element_size())
             L.check(lib.scl_vgg_act_bwd(L.ptr(gy), L.ptr(y) if mask_here else None,
@@ -948,8 +944,7 @@ class _ConvBiasAct(torch.autograd.Function):
                                         L.ptr(gz) if mask_here else None, L.ptr(gb), L.ptr(ws),
                                         ws.numel(), L.stream_of(gy)))
         with _in_slot(ctx.slot):
-            gx, gw = _conv3x3_backward(gz, x, w, ctx.needs_input_grad[0], ctx.link_in,
-                                       gb if fold else None)
+            gx, gw = _conv3x3_backward(route, gz, x, w, ctx.link_in, gb if fold else None)
         return gx, _grad_ret(gw, w), _grad_ret(gb, bias), None, None, None
 
 
@@ -974,21 +969,21 @@ class _ConvBiasPoolReLU(torch.autograd.Function):
                 ctx.save_for_backward(x, w, idx, a, bias)
                 return a
             raise RuntimeError("fused conv1_1 + conv1_2 results do not belong to this layer")
-        kind = _own_conv_kind(x, w)
-        if USE_POOL_IDX and ((kind == 'reg' and w.shape[0] == w.shape[1])
-                             or (kind == 'lds' and _lds_conv_pays(x, kout=w.shape[0]))):
+        route = _fwd_route(x, w)
+        square_reg = route == 'reg' and w.shape[0] == w.shape[1]
+        if USE_POOL_IDX and (square_reg or route == 'lds'):
             # conv1_2 .. conv4_3: pooled map and the position of each maximum from the epilogue;
             # the full-size convolution output is never written
             a, idx = conv_pool_idx(x, w, bias)
             ctx.by_idx = True
             ctx.save_for_backward(x, w, idx, a, bias)
             return a
-        if _own_conv_kind(x, w) == 'reg' and w.shape[0] == w.shape[1]:
+        if square_reg:
             # pooled map from the epilogue (no pooling pass over z)
             z, a = conv64(x, w, False, bias=bias, pool=True)
         else:
             with _whole_batch_op():
-                z = _conv3x3(x, w).contiguous(memory_format=_CL)
+                z = _conv3x3(x, w, route).contiguous(memory_format=_CL)
                 b, c, h, wd = z.shape
                 a = torch.empty((b, c, h // 2, wd // 2), dtype=z.dtype, device=z.device,
                                 memory_format=_CL)
@@ -1005,8 +1000,7 @@ class _ConvBiasPoolReLU(torch.autograd.Function):
         ga = ga.contiguous(memory_format=_CL)
         b, c = a.shape[0], a.shape[1]
         h, wd = x.shape[2], x.shape[3]
-        gb = _grad_out(bias) if bias.dtype == torch.float32 else torch.empty(
-            c, dtype=torch.float32, device=a.device)
+        gb = _bias_grad_out(bias)
         # ReLU' of this layer already applied by the layer above (its backward-data epilogue
         # masks with its own input, which is this layer's output a)?  Then a is not read.
         masked = ctx.by_idx and ctx.link_out is not None and ctx.link_out.take(ga)
@@ -1016,23 +1010,20 @@ class _ConvBiasPoolReLU(torch.autograd.Function):
         # gradient comes out of the weight-gradient kernel.  Otherwise (conv3_3, conv4_3) the
         # pass runs for the backward-data kernel and the weight gradient still reads the pooled
         # form.
-        need_x = ctx.needs_input_grad[0]
-        pool_w, pool_x = _pooled_consumers(x, ga, w, need_x, ctx.link_in) if masked else (False, False)
-        if pool_w and pool_x:
-            with _in_slot(ctx.slot):
-                gx, gw = _conv3x3_backward(None, x, w, need_x, ctx.link_in, gb, pooled=(ga, z))
-            return gx, _grad_ret(gw, w), _grad_ret(gb, bias), None, None
-        gz = torch.empty((b, c, h, wd), dtype=a.dtype, device=a.device, memory_format=_CL)
-        ws = L.workspace(lib.scl_vgg_workspace_bytes(c), a.device)
-        fn = lib.scl_vgg_pool_bwd_idx if ctx.by_idx else lib.scl_vgg_pool_bwd
-        # read g, a (1/4 each) and the index bytes (1/8) or z (1); write gz
-        _work('pool_bwd_idx_kernel' if ctx.by_idx else 'pool_bwd_kernel', 0.0,
-              ((1.375 if masked else 1.625) if ctx.by_idx else 2.5) * gz.numel() * gz.element_size())
-        L.check(fn(L.ptr(ga), None if masked else L.ptr(a), L.ptr(z), _glue_dtype(a), b, h, wd, c,
-                   L.ptr(gz), L.ptr(gb), L.ptr(ws), ws.numel(), L.stream_of(a)))
+        route = _bwd_route(x, ga, w, ctx.needs_input_grad[0], ctx.link_in, pooled=masked)
+        gz = None
+        if not route.pool_x:
+            gz = torch.empty((b, c, h, wd), dtype=a.dtype, device=a.device, memory_format=_CL)
+            ws = L.workspace(lib.scl_vgg_workspace_bytes(c), a.device)
+            fn = lib.scl_vgg_pool_bwd_idx if ctx.by_idx else lib.scl_vgg_pool_bwd
+            # read g, a (1/4 each) and the index bytes (1/8) or z (1); write gz
+            _work('pool_bwd_idx_kernel' if ctx.by_idx else 'pool_bwd_kernel', 0.0,
+                  ((1.375 if masked else 1.625) if ctx.by_idx else 2.5) * gz.numel() * gz.element_size())
+            L.check(fn(L.ptr(ga), None if masked else L.ptr(a), L.ptr(z), _glue_dtype(a), b, h, wd, c,
+                       L.ptr(gz), L.ptr(gb), L.ptr(ws), ws.numel(), L.stream_of(a)))
         with _in_slot(ctx.slot):
-            gx, gw = _conv3x3_backward(gz, x, w, need_x, ctx.link_in,
-                                       pooled=(ga, z) if pool_w else None)
+            gx, gw = _conv3x3_backward(route, gz, x, w, ctx.link_in, gb if route.pool_x else None,
+                                       (ga, z) if route.pool_w else None)
         return gx, _grad_ret(gw, w), _grad_ret(gb, bias), None, None
 
 
@@ -1082,9 +1073,7 @@ def first_wrw(x0, gz, w_like, gb=None, w=None):
     sk, sc, sh, sw = gw.stride()
     davg = None
     if w is not None:
-        if w.stride() != gw.stride() or w.dtype != gw.dtype:
-            w = w.to(gw.dtype).contiguous(memory_format=_CL) if gw.is_contiguous(memory_format=_CL) \
-                else w.to(gw.dtype).contiguous()
+        w = _weight_like_grad(w, gw)
         if w.stride() != gw.stride():
             raise ValueError("w must have the strides of w_like")
         davg = torch.empty(3, dtype=torch.float32, device=gz.device)
@@ -1161,7 +1150,7 @@ class _FirstConv(torch.autograd.Function):
         else:
             with _whole_batch_op():
                 x0 = (img_nhwc - avg.to(img_nhwc.dtype)).to(dtype).permute(0, 3, 1, 2)
-                y = _conv3x3(x0, w).contiguous(memory_format=_CL)
+                y = _conv3x3(x0, w, _fwd_route(x0, w)).contiguous(memory_format=_CL)
                 b, c, h, wd = y.shape
                 L.check(lib.scl_vgg_bias_act(L.ptr(y), _glue_dtype(y), L.ptr(bias), b * h * wd, c, 1,
                                              L.stream_of(y)))
@@ -1174,8 +1163,7 @@ class _FirstConv(torch.autograd.Function):
         x0, w, y, bias = ctx.saved_tensors
         gy = gy.contiguous(memory_format=_CL)
         b, c, h, wd = gy.shape
-        gb = _grad_out(bias) if bias.dtype == torch.float32 else torch.empty(
-            c, dtype=torch.float32, device=gy.device)
+        gb = _bias_grad_out(bias)
         ws = L.workspace(lib.scl_vgg_workspace_bytes(c), gy.device)
         done = ctx.link_out.first_done if ctx.link_out is not None else None
         masked = ctx.link_out is not None and ctx.link_out.take(gy)
@@ -1203,7 +1191,7 @@ class _FirstConv(torch.autograd.Function):
             # border sums of the mean's closed form are five more columns of the same product)
             gw, davg = first_wrw(x0, gz, w, gb, w)
         else:
-            _, gw = _conv3x3_backward(gz, x0, w, False)
+            _, gw = _conv3x3_backward(_bwd_route(x0, gz, w, False), gz, x0, w)
             davg = avg_rgb_grad(gz, w, gb)
         return None, davg, _grad_ret(gw, w), _grad_ret(gb, bias), None, None, None, None
 
