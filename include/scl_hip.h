@@ -339,6 +339,35 @@ int scl_topn_index_query_window(const float* ref, int R, int d, const void* inde
                                 int* count_out, unsigned char* uncertified, double* bound_sq,
                                 void* workspace, size_t workspace_bytes, int flags, void* stream);
 
+/* The prepared index and the stream route for descriptors WIDER than 256 columns: d a multiple of
+ * 256 with 512 <= d <= 32768 (the caller zero-pads rows and queries once; no distance changes),
+ * Q <= SCL_TOPN_STREAM_MAX_Q, n <= 25, n <= R.  The size queries return 0 for anything else.
+ *
+ * The wide index block (scl_topn_wide_index_bytes) holds the norm-bound word and refnorm[R]: the
+ * norms summed in float64 and rounded to float32 once, the bound word rounded up so that it is never
+ * below max |r|^2.  Written by scl_topn_wide_index_build, read-only afterwards.
+ *
+ * scl_topn_wide_query is the one call for both kinds of query.  With geo, center, radius and
+ * count_out all NULL it returns what scl_topn_index_query's stream route returns at d <= 256 — the
+ * exact top n by float64 sum (q - r)^2, ordered by (distance, index), with the certificate in
+ * uncertified / bound_sq (both or neither).  With all four given (the geo block of
+ * scl_topn_geo_build for the same R) it is scl_topn_index_query_window: the top min(n, |W_q|) of each
+ * query's window, (-1, +inf) behind them, count_out[q] = min(n, |W_q|).  Any other mixture of the
+ * four is SCL_E_NULL.  Scores are refnorm[j] - 2 q.r_j with float32 matrix-core chains inside
+ * chunks of 256 features and float64 across chunks, so the certificate's bound does not grow with d
+ * (csrc/topn.hip, topn_wide_eps).  A flagged query is resolved by the caller from exact float64
+ * distances to every reference (of its window). */
+size_t scl_topn_wide_index_bytes(int R, int d);
+int scl_topn_wide_index_build(const float* ref, int R, int d, void* index, size_t index_bytes,
+                              void* stream);
+size_t scl_topn_wide_query_workspace_bytes(int R, int Q, int d, int n);
+int scl_topn_wide_query(const float* ref, int R, int d, const void* index, size_t index_bytes,
+                        const void* geo, size_t geo_bytes, const float* query, int Q,
+                        const double* center, const double* radius, int n, int64_t idx_offset,
+                        int64_t* idx_out, double* dist_out, int* count_out,
+                        unsigned char* uncertified, double* bound_sq, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
 /* Exact resolution of uncertified queries: for each listed query, float64 sum (q - r)^2 against
  * EVERY reference row (d <= 256, d % 4 == 0); rows with squared distance <= bound_sq[query] are
  * appended (unordered) to that query's candidate list.  The true top-n are the n smallest

@@ -107,6 +107,11 @@ SIGNATURES = {
     "scl_topn_index_query_window_workspace_bytes": (_z, [_i, _i, _i, _i, _i]),
     "scl_topn_index_query_window": (_i, [_p, _i, _i, _p, _z, _p, _z, _p, _i, _p, _p, _i, _l, _p, _p, _p,
                                          _p, _p, _p, _z, _i, _p]),
+    "scl_topn_wide_index_bytes": (_z, [_i, _i]),
+    "scl_topn_wide_index_build": (_i, [_p, _i, _i, _p, _z, _p]),
+    "scl_topn_wide_query_workspace_bytes": (_z, [_i, _i, _i, _i]),
+    "scl_topn_wide_query": (_i, [_p, _i, _i, _p, _z, _p, _z, _p, _i, _p, _p, _i, _l, _p, _p, _p, _p, _p,
+                                 _p, _z, _p]),
     "scl_topn_exact_filter": (_i, [_p, _i, _p, _i, _p, _i, _p, _i, _p, _p, _p, _p]),
     "scl_topn_dots": (_i, [_p, _i, _p, _i, _i, _i, _p, _p]),
     "scl_vgg_workspace_bytes": (_z, [_i]),

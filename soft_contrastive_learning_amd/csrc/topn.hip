@@ -1447,6 +1447,216 @@ __global__ __launch_bounds__(256) void topn_rerank_window_kernel(
   }
 }
 
+// ---- the wide stream route (scl_topn_wide_query): descriptors of 512 .. 32768 columns ----
+// The stream route's three stages with a score kernel of its own; selection and re-rank take the
+// width at run time or not at all and are the kernels above.
+constexpr int kWideChunk = 256;        // features per float32 chain (one rounding bound whatever d is)
+constexpr int kWideLdsChunks = 4;      // chunks of the query block a workgroup holds in LDS, 32 KB each
+
+// refnorm_kernel in float64: out[row] = float32(sum_e r_e^2), the squares exact and their sum in
+// float64, rounded to nearest ONCE.  rmax_bits (zeroed by the caller) is raised to a float32 that is
+// never below the true max_j |r_j|^2: the float64 sum is within (d - 1) 2^-53 of it relatively, so
+// sum * (1 + (d + 2) 2^-52) is above it, and that is rounded UP to float32.
+__global__ __launch_bounds__(256) void topn_wide_norm_kernel(const float* __restrict__ ref, int R, int d,
+                                                             float* __restrict__ out,
+                                                             unsigned* __restrict__ rmax_bits) {
+  __shared__ float wmax[4];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const double up = 1.0 + (double)(d + 2) * 0x1p-52;
+  float mx = 0.f;
+  for (int t = 0; t < 16; ++t) {
+    const int row = blockIdx.x * 64 + wid * 16 + t;
+    if (row >= R) break;                         // wave-uniform
+    const float* p = ref + (int64_t)row * d;
+    double s = 0.0;
+    for (int e = lane * 4; e < d; e += 256) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(p + e);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) s = fma((double)v[c], (double)v[c], s);
+    }
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) s += __shfl_xor(s, m, 64);
+    if (lane == 0) out[row] = (float)s;
+    const double su = s * up;
+    float b = (float)su;
+    if (b < INFINITY && (double)b < su) b = __uint_as_float(__float_as_uint(b) + 1u);   // (b >= 0)
+    mx = fmaxf(mx, b);
+  }
+  if (lane == 0) wmax[wid] = mx;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    atomicMax(rmax_bits, __float_as_uint(fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]))));
+}
+
+// topn_wide_score_kernel: scores[q][j] = float32(refnorm[j] - 2 q.r_j) for every reference, d a
+// multiple of 256.  As in topn_stream_score_kernel a WAVE owns 32-reference tiles and lane (r, h)
+// loads row r's elements 8 u + 4 h .. + 3 straight into the B operands of v_mfma_f32_32x32x2_f32,
+// 256 features (one chunk: two halves of 16 KB per wave, each refilled for the next chunk as soon as
+// its products are issued) at a time.  The query fragment of a chunk is 128 registers and there are
+// d / 256 of them, so it lives in LDS: the workgroup stages the query block [32][256] per chunk (rows
+// past Q zero), 16-byte slot s of row r at slot s ^ (r & 15) so that the 16 lanes of a ds_read_b128
+// group fall on 16 different slots, and every wave reads its A operands from there.  Up to
+// kWideLdsChunks chunks (d <= 1024: the whole query) are staged once and the waves then run on their
+// own; beyond that the workgroup walks its tiles in rounds (wave w of workgroup b takes tile
+// (k G + b) 4 + w in round k) and re-stages the groups of chunks in every round, from L2.
+// Arithmetic: inside a chunk the instruction's k-ordered float32 chain of 256 products; the chunk
+// sums are added in float64; refnorm[j] - 2 sum is formed in float64 and rounded to float32 once
+// (topn_wide_eps has the bound).
+// WIN: the windows of topn_stream_score_window_kernel with its predicates: a tile that no circle
+// reaches is neither loaded nor multiplied and gets the empty marker, and in the other tiles a pair
+// outside the window gets the marker.  Dynamic LDS: the staged chunks | WIN: win [32][4] doubles.
+// The last tile may be ragged: rows past R re-read row R - 1 and are not written.  No scratch.
+template <bool WIN>
+__global__ __launch_bounds__(256) void topn_wide_score_kernel(
+    const float* __restrict__ ref, const float* __restrict__ refnorm, int R, int d,
+    const float* __restrict__ query, int Q, float* __restrict__ scores, const double* __restrict__ xy,
+    const double* __restrict__ box, const double* __restrict__ center,
+    const double* __restrict__ radius) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int r = lane & 31, h = lane >> 5;
+  const int ntiles = (R + 31) / 32;
+  const int nchunks = d / kWideChunk;
+  const int nl = nchunks < kWideLdsChunks ? nchunks : kWideLdsChunks;
+  const int ngroups = (nchunks + nl - 1) / nl;
+  const int nw = gridDim.x * 4;
+  const int rounds = (ntiles - 4 * (int)blockIdx.x + nw - 1) / nw;   // (grid <= ceil(ntiles / 4): >= 1)
+  double* win = reinterpret_cast<double*>(lds + nl * 32 * kWideChunk);
+  double wcx = 0.0, wcy = 0.0, wr2 = -1.0;                   // lane r: query r's circle (none past Q)
+  if constexpr (WIN) {
+    if (r < Q) {
+#pragma clang fp contract(off)
+      const double rad = radius[r];
+      wcx = center[2 * r];
+      wcy = center[2 * r + 1];
+      wr2 = rad < 0.0 ? -1.0 : rad * rad;
+    }
+    if (threadIdx.x < 32) {
+      win[4 * r] = wcx;
+      win[4 * r + 1] = wcy;
+      win[4 * r + 2] = wr2;
+    }
+  }
+  // group g of the query block into LDS: 64 consecutive lanes move one row of a chunk
+  auto stage = [&](int g) {
+    const int c0 = g * nl;
+    const int nc = nchunks - c0 < nl ? nchunks - c0 : nl;
+    for (int i = threadIdx.x; i < nc * 2048; i += 256) {
+      const int cc = i >> 11, row = (i >> 6) & 31, slot = i & 63;
+      f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
+      if (row < Q) v = *reinterpret_cast<const f32x4*>(query + (int64_t)row * d + (c0 + cc) * kWideChunk + slot * 4);
+      *reinterpret_cast<f32x4*>(lds + (cc * 32 + row) * kWideChunk + 4 * (slot ^ (row & 15))) = v;
+    }
+  };
+  // a tile the wave works on: inside the reference set and (WIN) reached by some query's circle
+  auto live = [&](int tile) {                                // (wave-uniform)
+    if (tile >= ntiles) return false;
+    if constexpr (WIN) return __ballot(window_reaches(box + 4 * (int64_t)tile, wcx, wcy, wr2)) != 0ull;
+    return true;
+  };
+  auto row_of = [&](int tile, int c) {
+    const int row = tile * 32 + r;
+    return ref + (int64_t)(row < R ? row : R - 1) * d + c * kWideChunk + 4 * h;
+  };
+  f32x4 a[16], b[16];
+  auto load_a = [&](const float* p) {
+#pragma unroll
+    for (int u = 0; u < 16; ++u) a[u] = *reinterpret_cast<const f32x4*>(p + 8 * u);
+  };
+  auto load_b = [&](const float* p) {
+#pragma unroll
+    for (int u = 0; u < 16; ++u) b[u] = *reinterpret_cast<const f32x4*>(p + 8 * (16 + u));
+  };
+  double acc64[16];
+  const int cm = h ^ (r & 15);                               // the lane's slot 2 u + h lies at (2 u) ^ cm
+  // one chunk: staged chunk cc against the rows in a / b; `pn` (more): the rows that follow
+  auto chunk = [&](int cc, bool more, const float* pn) {
+    const float* qb = lds + (cc * 32 + r) * kWideChunk;
+    f32x16 acc = zero16();
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+      const f32x4 qv = *reinterpret_cast<const f32x4*>(qb + 4 * ((2 * u) ^ cm));
+#pragma unroll
+      for (int c = 0; c < 4; ++c) acc = mfma32(qv[c], a[u][c], acc);
+    }
+    if (more) load_a(pn);
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+      const f32x4 qv = *reinterpret_cast<const f32x4*>(qb + 4 * ((2 * (16 + u)) ^ cm));
+#pragma unroll
+      for (int c = 0; c < 4; ++c) acc = mfma32(qv[c], b[u][c], acc);
+    }
+    if (more) load_b(pn);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) acc64[k] += (double)acc[k];
+  };
+
+  int t = blockIdx.x * 4 + wid;
+  bool act = live(t);
+  stage(0);
+  if (act) {
+    const float* p = row_of(t, 0);
+    load_a(p);
+    load_b(p);
+  }
+  __syncthreads();
+  for (int k = 0; k < rounds; ++k) {
+    const int tn = t + nw;
+    const bool nact = k + 1 < rounds && live(tn);            // wave-uniform
+    const int ridx = t * 32 + r;
+    const int rclamp = ridx < R ? ridx : R - 1;              // (t >= ntiles: not used)
+    double rn = 0.0, px = 0.0, py = 0.0;
+    if (act) {
+      rn = (double)refnorm[rclamp];
+      if constexpr (WIN) {
+        px = xy[2 * (int64_t)rclamp];
+        py = xy[2 * (int64_t)rclamp + 1];
+      }
+#pragma unroll
+      for (int q = 0; q < 16; ++q) acc64[q] = 0.0;
+    } else if (WIN && ridx < R) {                            // passed over: the marker
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        const int row = acc_row(q, h);
+        if (row < Q) scores[(int64_t)row * R + ridx] = __uint_as_float(kEmptyScoreBits);
+      }
+    }
+    for (int g = 0; g < ngroups; ++g) {
+      if (ngroups > 1 && (k | g)) {                          // workgroup-uniform
+        __syncthreads();                                     // every wave is done with the staged group
+        stage(g);
+        __syncthreads();
+      }
+      if (!act) continue;
+      const int c0 = g * nl;
+      const int nc = nchunks - c0 < nl ? nchunks - c0 : nl;
+      for (int cc = 0; cc < nc; ++cc) {
+        const bool last = c0 + cc + 1 == nchunks;
+        chunk(cc, !last || nact, last ? row_of(tn, 0) : row_of(t, c0 + cc + 1));
+      }
+    }
+    if (act && ridx < R) {
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        const int row = acc_row(q, h);
+        float s = (float)(rn - 2.0 * acc64[q]);
+        if constexpr (WIN) {
+          const double* w = win + 4 * row;
+          if (!window_holds(px, py, w[0], w[1], w[2])) s = __uint_as_float(kEmptyScoreBits);
+        }
+        if (row < Q) scores[(int64_t)row * R + ridx] = s;
+      }
+    }
+    if (!act && nact) {                                      // nothing was fetched ahead
+      const float* p = row_of(tn, 0);
+      load_a(p);
+      load_b(p);
+    }
+    t = tn;
+    act = nact;
+  }
+}
+
 struct TopnPlan {
   int qtiles, splits, refs_per_split;
 };
@@ -1604,6 +1814,37 @@ inline TopnEps topn_eps(int d, int bf) {
   const double eps_q = 2.0 * (2.0 * (d + 16) * u +
                               (bf ? 6.0 / 262144.0 + 6.0 * d * u : 2.0 * d * u));
   return TopnEps{(float)eps_q, (float)eps_r};
+}
+
+// topn_eps for topn_wide_score_kernel: |approximate - exact score| <= eps_q |q| Rmax + eps_r Rmax^2
+// with u = 2^-24, v = 2^-53, g = gamma_256 = 256 u / (1 - 256 u), C = d / 256 chunks, term by term:
+//   refnorm[j]: squares exact in float64, their sum within (d - 1) v relatively,
+//               rounded to float32 once                                          (u + d v) Rmax^2
+//   -2 q.r, chunk c: a float32 chain of 256 fused multiply-adds, in any order
+//               <= g |q_c||r_c|; over the chunks, by Cauchy-Schwarz               2 g |q| Rmax
+//   -2 q.r, the C <= 128 chunk sums added in float64: (C - 1) v sum_c |chunk_c|
+//               <= (C - 1) v (1 + g) |q||r|                                       2 C v |q| Rmax
+//   refnorm - 2 sum in float64, rounded to float32 once: (u + v) |score|,
+//               |score| <= Rmax^2 + 2 |q| Rmax (1 + ..)                           (u + v)(Rmax^2 + 2 |q| Rmax)
+// Sum: (2 g + 2 u + 2 (C + 1) v) |q| Rmax + (2 u + (d + 1) v) Rmax^2 to first order.  With the
+// products of these terms covered by 4 u / 3 u in place of 2 u / 2 u, the float64 terms written as
+// 2 (d + 8) v / (d + 8) v, and the usual factor 2 of safety:
+//   eps_q = 2 (2 g + 4 u + 2 (d + 8) v),  eps_r = 2 (3 u + (d + 8) v)
+// = 6.2e-5 and 3.6e-7 at every d (the float64 terms reach 7e-12 at d = 32768): the bound does not
+// grow with d.  The re-rank's own float64 sums (|q|^2 and the n-th distance, (d + 2) v relative
+// each) are not part of the score error; as at d <= 256 the safety factor carries them, here as
+// long as |q| < 4e6 Rmax.
+inline TopnEps topn_wide_eps(int d) {
+  const double u = 0x1p-24, v = 0x1p-53;
+  const double g = 256.0 * u / (1.0 - 256.0 * u);
+  const double eps_q = 2.0 * (2.0 * g + 4.0 * u + 2.0 * (d + 8) * v);
+  const double eps_r = 2.0 * (3.0 * u + (d + 8) * v);
+  // rounded up: a float32 never below the double
+  auto up = [](double x) {
+    float f = (float)x;
+    return (double)f < x ? nextafterf(f, INFINITY) : f;
+  };
+  return TopnEps{up(eps_q), up(eps_r)};
 }
 
 inline size_t rerank_lds_bytes(int M) { return (size_t)4 * (2 * M + 3 * KEEP + 4 + 66) * sizeof(float); }
@@ -1819,6 +2060,74 @@ int topn_scan_rerank(const float* ref, int R, const float* query, int Q, int d, 
 
 inline bool topn_flags_ok(int flags) { return !(flags & ~SCL_TOPN_SCORE_BF16X3); }
 
+// ---- the wide stream route: shapes, index block, certificate bound, launches ----
+inline bool topn_wide_shape_ok(int R, int Q, int d, int n) {
+  const bool d_ok = d >= 2 * kWideChunk && d <= 32768 && d % kWideChunk == 0;
+  return R >= 1 && Q >= 1 && Q <= SCL_TOPN_STREAM_MAX_Q && d_ok && n >= 1 && n <= kMaxN && n <= R;
+}
+
+// The wide index block: the norm-bound word and the float64-summed norms, filled by topn_wide_prepare
+// (scl_topn_wide_index_build), read-only afterwards.
+struct TopnWideIndex {
+  unsigned* rmax_bits;   // float bits of a number >= max |r|^2, a 256-byte piece of its own
+  float* refnorm;        // [R]: float32(|r|^2 summed in float64)
+  size_t bytes;
+};
+inline TopnWideIndex topn_wide_index_at(const void* block, int R) {   // nullptr: for .bytes
+  Carver c(const_cast<void*>(block));
+  TopnWideIndex x{};
+  x.rmax_bits = c.take<unsigned>(64);
+  x.refnorm = c.take(R);
+  x.bytes = c.off;
+  return x;
+}
+hipError_t topn_wide_prepare(const TopnWideIndex& x, const float* ref, int R, int d, hipStream_t st) {
+  const hipError_t e = hipMemsetAsync(x.rmax_bits, 0, 16, st);
+  if (e != hipSuccess) return e;
+  SCL_LAUNCH("topn_wide_norm_kernel", topn_wide_norm_kernel, dim3((R + 63) / 64), dim3(256), 0, st, ref,
+             R, d, x.refnorm, x.rmax_bits);
+  return hipSuccess;
+}
+
+inline size_t wide_score_lds_bytes(int d, bool win) {
+  const int nl = d / kWideChunk < kWideLdsChunks ? d / kWideChunk : kWideLdsChunks;
+  return (size_t)nl * 32 * kWideChunk * sizeof(float) + (win ? 32 * 4 * sizeof(double) : 0);
+}
+// Workgroups of the wide score kernel: one wave per tile until the chip is full, which is one
+// workgroup per CU: a wave holds a chunk of its tile, the float32 and the float64 accumulators (272
+// registers, 296 with windows: one wave per SIMD) and the workgroup 128 KB of LDS from d = 1024 on.
+inline int wide_score_wgs(int R) {
+  const int ntiles = (R + 31) / 32;
+  return (ntiles + 3) / 4 < 256 ? (ntiles + 3) / 4 : 256;
+}
+template <bool WIN>
+void launch_wide_score(const float* ref, const float* refnorm, int R, int d, const float* query, int Q,
+                       float* scores, const TopnGeo& g, const double* center, const double* radius,
+                       hipStream_t st) {
+  scl_lds_limit<&topn_wide_score_kernel<WIN>>((int)wide_score_lds_bytes(kWideLdsChunks * kWideChunk, WIN));
+  SCL_LAUNCH(WIN ? "topn_wide_score_kernel<window>" : "topn_wide_score_kernel", topn_wide_score_kernel<WIN>,
+             dim3(wide_score_wgs(R)), dim3(256), wide_score_lds_bytes(d, WIN), st, ref, refnorm, R, d,
+             query, Q, scores, (const double*)g.xy, (const double*)g.box, center, radius);
+}
+// topn_rerank_window_kernel over the stream route's lists (splits <= 32)
+void launch_rerank_window(const float* ref, const float* query, int Q, int d, int splits, int n,
+                          int64_t idx_offset, const float* cs, const int* ci, int64_t* idx_out,
+                          double* dist_out, int* count_out, const unsigned* rmax_bits, TopnEps eps,
+                          unsigned char* uncertified, double* bound_sq, hipStream_t st) {
+  const int M = splits * KEEP;
+#define SCL_RERANK(NE)                                                                              \
+  SCL_LAUNCH("topn_rerank_window_kernel", topn_rerank_window_kernel<NE>, dim3((Q + 3) / 4), dim3(256), \
+             rerank_lds_bytes(M), st, ref, query, Q, d, splits, n, idx_offset, cs, ci, idx_out,     \
+             dist_out, count_out, rmax_bits, eps.q, eps.r, uncertified, bound_sq)
+  if (M <= 256)
+    SCL_RERANK(4);
+  else if (M <= 512)
+    SCL_RERANK(8);
+  else
+    SCL_RERANK(16);
+#undef SCL_RERANK
+}
+
 }  // namespace
 
 // workspace of the one-shot calls: index block | candidate lists
@@ -1998,6 +2307,69 @@ extern "C" int scl_topn_index_query_window(const float* ref, int R, int d, const
   else
     SCL_RERANK(16);
 #undef SCL_RERANK
+  return scl_launch_status();
+}
+
+// ---- the wide stream route: a prepared index over rows of 512 .. 32768 columns (a multiple of 256) ----
+// (the block: topn_wide_index_at)
+extern "C" size_t scl_topn_wide_index_bytes(int R, int d) {
+  return topn_wide_shape_ok(R, 1, d, 1) ? topn_wide_index_at(nullptr, R).bytes : 0;
+}
+
+extern "C" int scl_topn_wide_index_build(const float* ref, int R, int d, void* index, size_t index_bytes,
+                                         void* stream) {
+  if (!ref || !index) return SCL_E_NULL;
+  if (!topn_wide_shape_ok(R, 1, d, 1) || ((uintptr_t)ref % 16)) return SCL_E_SHAPE;
+  const TopnWideIndex x = topn_wide_index_at(index, R);
+  if (!scl_aligned256(index) || index_bytes < x.bytes) return SCL_E_WORKSPACE;
+  const hipError_t e = topn_wide_prepare(x, ref, R, d, (hipStream_t)stream);
+  return e != hipSuccess ? (int)e : scl_launch_status();
+}
+
+// the stream route's score matrix and lists (topn_lists_at)
+extern "C" size_t scl_topn_wide_query_workspace_bytes(int R, int Q, int d, int n) {
+  return topn_wide_shape_ok(R, Q, d, n) ? topn_lists_at(nullptr, R, Q, 0, kStream).bytes : 0;
+}
+
+extern "C" int scl_topn_wide_query(const float* ref, int R, int d, const void* index, size_t index_bytes,
+                                   const void* geo, size_t geo_bytes, const float* query, int Q,
+                                   const double* center, const double* radius, int n,
+                                   int64_t idx_offset, int64_t* idx_out, double* dist_out,
+                                   int* count_out, unsigned char* uncertified, double* bound_sq,
+                                   void* workspace, size_t workspace_bytes, void* stream) {
+  if (!ref || !index || !query || !idx_out || !dist_out || !workspace) return SCL_E_NULL;
+  const bool win = geo != nullptr;                           // the window's four: all or none
+  if ((center != nullptr) != win || (radius != nullptr) != win || (count_out != nullptr) != win)
+    return SCL_E_NULL;
+  if ((uncertified == nullptr) != (bound_sq == nullptr)) return SCL_E_NULL;
+  if (!topn_wide_shape_ok(R, Q, d, n)) return SCL_E_SHAPE;
+  if (((uintptr_t)ref % 16) || ((uintptr_t)query % 16) || ((uintptr_t)center % 8) ||
+      ((uintptr_t)radius % 8))
+    return SCL_E_SHAPE;
+  const TopnWideIndex x = topn_wide_index_at(index, R);      // read-only here, like the geo block
+  const TopnGeo g = win ? topn_geo_at(geo, R) : TopnGeo{};
+  if (!scl_aligned256(index) || index_bytes < x.bytes) return SCL_E_WORKSPACE;
+  if (win && (!scl_aligned256(geo) || geo_bytes < g.bytes)) return SCL_E_WORKSPACE;
+  if (!scl_aligned256(workspace) || workspace_bytes < topn_lists_at(nullptr, R, Q, 0, kStream).bytes)
+    return SCL_E_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const StreamPlan sp = stream_plan(R);
+  const TopnLists w = topn_lists_at(workspace, R, Q, 0, kStream);
+  const TopnEps eps = topn_wide_eps(d);
+  if (win) {
+    launch_wide_score<true>(ref, x.refnorm, R, d, query, Q, w.scores, g, center, radius, st);
+    SCL_LAUNCH("topn_stream_select_window_kernel", topn_stream_select_window_kernel,
+               dim3((sp.splits + 3) / 4, Q), dim3(256), 0, st, (const float*)w.scores, R, sp.splits, sp.per,
+               w.cs, w.ci);
+    launch_rerank_window(ref, query, Q, d, sp.splits, n, idx_offset, w.cs, w.ci, idx_out, dist_out,
+                         count_out, x.rmax_bits, eps, uncertified, bound_sq, st);
+  } else {
+    launch_wide_score<false>(ref, x.refnorm, R, d, query, Q, w.scores, g, nullptr, nullptr, st);
+    SCL_LAUNCH("topn_stream_select_kernel", topn_stream_select_kernel, dim3((sp.splits + 3) / 4, Q),
+               dim3(256), 0, st, (const float*)w.scores, R, sp.splits, sp.per, w.cs, w.ci);
+    launch_rerank(ref, query, Q, d, sp.splits, n, idx_offset, w.cs, w.ci, idx_out, dist_out, x.rmax_bits,
+                  eps, uncertified, bound_sq, st);
+  }
   return scl_launch_status();
 }
 

@@ -33,10 +33,14 @@ class Localizer:
 
     ``query_fn(ref_f, query_f, n) -> (dist [Q,n], idx [Q,n])`` on NumPy arrays replaces the index
     in the CPU tests of the bookkeeping around it (a window is applied there by subsetting the
-    rows on the host); the product path has no such argument and no CPU fallback."""
+    rows on the host); the product path has no such argument and no CPU fallback.
+
+    ``wide`` is ``RetrievalIndex``'s: with more than 256 (whitened) columns, 'resident' (it needs
+    ``score='f32'``) keeps the frame-at-a-time route and the window; 'delegate', the default, answers
+    every call with ``topn_l2`` and takes no window."""
 
     def __init__(self, ref_desc, ref_xy, pca=None, model=None, n=5, l=0.0, score='f32', device='cuda',
-                 query_fn=None):
+                 query_fn=None, wide='delegate'):
         self.ref_xy = np.asarray(ref_xy, dtype=np.float64)
         self.ref_idx = thin_reference(self.ref_xy, l)
         self.n = int(n)
@@ -57,7 +61,7 @@ class Localizer:
             return
         self.device = torch.device(device)
         self._index = retrieval.RetrievalIndex(self._whiten(rows), 0, score,
-                                               positions=self.ref_xy[self._orig])
+                                               positions=self.ref_xy[self._orig], wide=wide)
 
     def _whiten(self, rows):
         """[m, E] NumPy or tensor -> what the index holds: device float32 rows (NumPy with query_fn)."""
@@ -231,6 +235,9 @@ def main_parser():
     p.add_argument('--batch', default=1, type=int, help='frames per call')
     p.add_argument('--prior_radius', default=0.0, type=float,
                    help='metres around the previous call\'s last position estimate to search in (0: everywhere)')
+    p.add_argument('--wide_index', default=0, type=int, choices=[0, 1],
+                   help='1: descriptors wider than 256 columns get the resident wide index (needs --score f32); '
+                        '0: every call on them is a one-shot top-n and --prior_radius is refused')
     p.add_argument('--geo', default='table', choices=list(GEO_ROUTES),
                    help='geographic distances: read out of the [Q, M] table of the reference, or computed from '
                         'the index\'s positions on the device (no table is built)')
@@ -242,6 +249,8 @@ def main(argv=None, query_fn=None):
     query descriptors go through a ``Localizer`` in list order, --batch at a time; the payload of
     ``top_n.main`` goes to ``top_n.out_pickle_path``.  --prior_radius M (0: off) searches every call but
     the first within M metres of the call before's last position estimate (``localize_set``).
+    --wide_index 1 keeps descriptors wider than 256 columns in the resident wide index
+    (``RetrievalIndex(wide='resident')``; 0, the default: as before).
     --geo device takes the payload's geographic part from the index's positions (``Localizer.payload``
     with ``query_xy``) and builds no [Q, M] table; it needs the resident index, so together with
     ``query_fn`` it raises.  Prints queries per second, how many queries needed the exact fallback
@@ -278,7 +287,7 @@ def main(argv=None, query_fn=None):
     if len(thin_reference(full_ref_xy, flags.L)) < flags.N:       # (evaluation/top-n.py:96-97)
         return None
     loc = Localizer(full_ref_f, full_ref_xy, pca=pca, n=flags.N, l=flags.L, score=flags.score,
-                    query_fn=query_fn)
+                    query_fn=query_fn, wide='resident' if flags.wide_index else 'delegate')
     if query_fn is None:
         torch.cuda.synchronize()
     t0 = time.perf_counter()

@@ -17,6 +17,7 @@ SCORE_MODES = {'f32': L.TOPN_SCORE_F32, 'bf16x3': L.TOPN_SCORE_BF16X3}
 
 
 _WIDTHS = (32, 64, 128, 256)      # descriptor widths the kernels of csrc/topn.hip take
+WIDE_MAX = 32768                  # columns of the widest row scl_topn_wide_query takes (a multiple of 256 from 512 on)
 
 
 def _pad_width(t, width=None):
@@ -133,11 +134,22 @@ class RetrievalIndex:
     +inf.  ``stats`` then receives ``route='window'``, ``count`` (int32 tensor [Q]: min(n, |W_q|))
     and ``uncertified``.  The call (``scl_topn_index_query_window``, 32 queries at a time) skips
     every 32-reference tile that no query's circle reaches, so on a traverse it costs what the
-    windows cover."""
+    windows cover.
 
-    def __init__(self, ref, idx_offset=0, score='f32', positions=None):
+    ``wide`` says what happens to descriptors wider than 256 columns.  'delegate' (default): nothing
+    is prepared, every query is ``topn_l2`` on the stored rows and a window raises.  'resident'
+    (``score='f32'``, at most ``WIDE_MAX`` columns): the rows are zero-padded to a multiple of 256
+    once and the wide index block is built (``scl_topn_wide_index_build``: float64-summed norms and
+    their bound); a query of at most ``_lib.TOPN_STREAM_MAX_Q`` rows and n <= 25 is then one
+    ``scl_topn_wide_query`` (``route`` 'wide'), and windowed queries run the same call in groups
+    (``route`` 'window').  The queries it cannot certify are resolved by ``_brute_force_f64``.  More
+    rows or a larger n delegate as before.  At 256 columns or fewer ``wide`` changes nothing."""
+
+    def __init__(self, ref, idx_offset=0, score='f32', positions=None, wide='delegate'):
         if score not in SCORE_MODES:
             raise ValueError("score must be one of %s, got %r" % (sorted(SCORE_MODES), score))
+        if wide not in ('delegate', 'resident'):
+            raise ValueError("wide must be 'delegate' or 'resident', got %r" % (wide,))
         L.require_device(ref)
         ref = ref.float().contiguous()
         if ref.dim() != 2 or ref.shape[0] < 1:
@@ -149,17 +161,31 @@ class RetrievalIndex:
         self._ws = None
         self._index = None
         self._geo = None
+        self._wide = False                             # the index block is the wide one
         self.positions = None
         if positions is not None:
             xy = torch.as_tensor(positions).to(ref.device, torch.float64).contiguous()
             if xy.dim() != 2 or tuple(xy.shape) != (ref.shape[0], 2):
                 raise ValueError("positions %s must be [%d,2]" % (tuple(xy.shape), ref.shape[0]))
             self.positions = xy
-        if self.width > 256:
+        if self.width > 256 and wide == 'delegate':
             self.ref = ref                             # (topn_l2's wide path; nothing to prepare)
             return
-        self.ref = ref = _pad_width(ref)
         lib = L.load()
+        if self.width > 256:
+            if score != 'f32':
+                raise ValueError("wide='resident' scores in float32: score must be 'f32', got %r" % (score,))
+            if self.width > WIDE_MAX:
+                raise ValueError("wide='resident' takes at most %d columns, got %d" % (WIDE_MAX, self.width))
+            self.ref = ref = _pad_width(ref, -(-self.width // 256) * 256)
+            self._wide = True
+            r, d = ref.shape
+            self._index = L.workspace(_sized(lib.scl_topn_wide_index_bytes(r, d), r, 1, d, 1), ref.device)
+            L.check(lib.scl_topn_wide_index_build(L.ptr(ref), r, d, L.ptr(self._index), self._index.numel(),
+                                                  L.stream_of(ref)))
+            self._build_geo(lib)
+            return
+        self.ref = ref = _pad_width(ref)
         r, d = ref.shape
         nbytes = lib.scl_topn_index_bytes(r, d, self._flags)
         if nbytes == 0:
@@ -167,10 +193,14 @@ class RetrievalIndex:
         self._index = L.workspace(nbytes, ref.device)
         L.check(lib.scl_topn_index_build(L.ptr(ref), r, d, L.ptr(self._index), self._index.numel(),
                                          self._flags, L.stream_of(ref)))
+        self._build_geo(lib)
+
+    def _build_geo(self, lib):
         if self.positions is not None:
-            self._geo = L.workspace(lib.scl_topn_geo_bytes(r), ref.device)
+            r = self.ref.shape[0]
+            self._geo = L.workspace(lib.scl_topn_geo_bytes(r), self.ref.device)
             L.check(lib.scl_topn_geo_build(L.ptr(self.positions), r, L.ptr(self._geo), self._geo.numel(),
-                                           L.stream_of(ref)))
+                                           L.stream_of(self.ref)))
 
     def query(self, query, n, certify=True, stats=None, near=None, radius=None):
         """query [Q, width] float32 on the index's device -> (dist [Q,n] float64, idx [Q,n] int64).
@@ -178,12 +208,26 @@ class RetrievalIndex:
         ref, query = _checked(self.ref, query, n, self.width)
         if near is not None or radius is not None:
             return self._query_window(query, n, certify, stats, near, radius)
-        if self._index is None or n > MAX_N:
+        if self._index is None or n > MAX_N or (self._wide and query.shape[0] > L.TOPN_STREAM_MAX_Q):
             if stats is not None:
                 stats['route'] = 'delegate'
             return topn_l2(ref[:, :self.width], query, n, self.idx_offset, self.score, certify, stats)
         lib = L.load()
         r, d = ref.shape
+
+        def call_wide(query, idx, dist, flag, bound):
+            q = query.shape[0]
+            nbytes = _sized(lib.scl_topn_wide_query_workspace_bytes(r, q, d, n), r, q, d, n)
+            if self._ws is None or self._ws.numel() < nbytes:
+                self._ws = L.workspace(nbytes, ref.device)
+            if stats is not None:
+                stats['route'] = 'wide'
+            L.check(lib.scl_topn_wide_query(L.ptr(ref), r, d, L.ptr(self._index), self._index.numel(), None, 0,
+                                            L.ptr(query), q, None, None, n, self.idx_offset, L.ptr(idx),
+                                            L.ptr(dist), None, L.ptr(flag), L.ptr(bound), L.ptr(self._ws),
+                                            self._ws.numel(), L.stream_of(ref)))
+        if self._wide:
+            return _run(ref, query, n, self.idx_offset, certify, stats, call_wide)
 
         def call(query, idx, dist, flag, bound):
             q = query.shape[0]
@@ -233,8 +277,8 @@ class RetrievalIndex:
         if self.positions is None:
             raise ValueError("near/radius need an index built with positions")
         if self._geo is None or n > MAX_N:
-            raise ValueError("a windowed query takes descriptors of at most 256 columns and n <= %d, "
-                             "got width %d, n=%d" % (MAX_N, self.width, n))
+            raise ValueError("a windowed query takes descriptors of at most 256 columns (wider ones with "
+                             "wide='resident') and n <= %d, got width %d, n=%d" % (MAX_N, self.width, n))
         near = torch.as_tensor(near).to(dev, torch.float64).contiguous()
         if tuple(near.shape) != (q, 2):
             raise ValueError("near %s must be [%d,2]" % (tuple(near.shape), q))
@@ -255,16 +299,20 @@ class RetrievalIndex:
         step = L.TOPN_STREAM_MAX_Q
         for s in range(0, q, step):
             g = min(step, q - s)
-            nbytes = _sized(lib.scl_topn_index_query_window_workspace_bytes(r, g, d, n, self._flags), r, g, d, n)
+            nbytes = _sized(lib.scl_topn_wide_query_workspace_bytes(r, g, d, n) if self._wide else
+                            lib.scl_topn_index_query_window_workspace_bytes(r, g, d, n, self._flags), r, g, d, n)
             if self._ws is None or self._ws.numel() < nbytes:
                 self._ws = L.workspace(nbytes, dev)
             part = slice(s, s + g)
-            L.check(lib.scl_topn_index_query_window(
-                L.ptr(ref), r, d, L.ptr(self._index), self._index.numel(), L.ptr(self._geo),
-                self._geo.numel(), L.ptr(query[part]), g, L.ptr(near[part]), L.ptr(radius[part]), n,
-                self.idx_offset, L.ptr(idx[part]), L.ptr(dist[part]), L.ptr(count[part]),
-                None if flag is None else L.ptr(flag[part]), None if bound is None else L.ptr(bound[part]),
-                L.ptr(self._ws), self._ws.numel(), self._flags, L.stream_of(ref)))
+            head = (L.ptr(ref), r, d, L.ptr(self._index), self._index.numel(), L.ptr(self._geo),
+                    self._geo.numel(), L.ptr(query[part]), g, L.ptr(near[part]), L.ptr(radius[part]), n,
+                    self.idx_offset, L.ptr(idx[part]), L.ptr(dist[part]), L.ptr(count[part]),
+                    None if flag is None else L.ptr(flag[part]), None if bound is None else L.ptr(bound[part]),
+                    L.ptr(self._ws), self._ws.numel())
+            if self._wide:
+                L.check(lib.scl_topn_wide_query(*head, L.stream_of(ref)))
+            else:
+                L.check(lib.scl_topn_index_query_window(*head, self._flags, L.stream_of(ref)))
         if stats is not None:
             stats['route'] = 'window'
             stats['count'] = count
@@ -291,9 +339,21 @@ def _resolve_exactly(ref, query, n, idx_offset, bad, bound, dist, idx, window=No
     """Rows ``bad`` of (dist, idx) recomputed from the exact float64 distances to every
     reference that lies within the query's bound.  ``window`` = (positions, near, radius): among
     the references inside each query's window only (a flagged query's window holds at least n
-    within its bound: the bound is the n-th distance of nominated MEMBERS)."""
-    lib = L.load()
+    within its bound: the bound is the n-th distance of nominated MEMBERS).  Rows wider than the
+    filter kernel takes (256 columns) go through ``_brute_force_f64`` one query at a time."""
     r, d = ref.shape
+    if d > 256:
+        for qi in bad.tolist():
+            rows = None
+            if window is not None:
+                xy, near, radius = window
+                rows = torch.nonzero(_in_window(xy, near[qi, 0], near[qi, 1], radius[qi])).reshape(-1)
+            best_d, best_i = _brute_force_f64(ref if rows is None else ref[rows], query[qi], n)
+            k = best_i.numel()                               # (a flagged query's window holds >= n)
+            dist[qi, :k] = best_d.sqrt()
+            idx[qi, :k] = (best_i if rows is None else rows[best_i]) + idx_offset
+        return
+    lib = L.load()
     dev = ref.device
     for s in range(0, bad.numel(), 4096):
         ql = bad[s:s + 4096].to(torch.int32).contiguous()
