@@ -5,8 +5,13 @@ size) and the disassembly of every device symbol, the `__hip_cuid_*` hash apart.
 
     python scripts/kernel_code_diff.py parent/gram_loss.o soft_contrastive_learning_amd/csrc/gram_loss.o
 
+--map FILE: kernels that were renamed between the builds.  Lines `old name<TAB>new name`, the names
+as kernel_resources.py prints them (demangled, no parameter list); the first object's symbols take
+the second's names before they are matched.  A symbol that differs in at most 8 lines has them shown.
+
 Exit status 0: identical.  1: the differing kernels are listed with their resource rows.
 """
+import difflib
 import os
 import re
 import subprocess
@@ -42,16 +47,38 @@ def device_code(path):
     return rows, syms, order
 
 
+def renamed(a, b, path):
+    """`a` with the symbols that the map file names under their new names, which are symbols of `b`"""
+    pairs = dict(line.rstrip('\n').split('\t') for line in open(path) if line.strip())
+    short = lambda syms: [K.short_name(n) for n in K.demangle(syms)]
+    new_sym = dict(zip(short(b[2]), b[2]))
+    old = short(a[2])
+    lost = [n for n in pairs if n not in old or pairs[n] not in new_sym]
+    assert not lost, 'map lines that name no symbol: %s' % lost
+    to = {s: new_sym[pairs[n]] for s, n in zip(a[2], old) if n in pairs}
+    return ({to.get(s, s): v for s, v in a[0].items()}, {to.get(s, s): v for s, v in a[1].items()},
+            [to.get(s, s) for s in a[2]])
+
+
 def main():
-    a, b = device_code(sys.argv[1]), device_code(sys.argv[2])
+    argv = sys.argv[1:]
+    mapfile = argv.pop(argv.index('--map') + 1) if '--map' in argv else None
+    argv = [x for x in argv if x != '--map']
+    a, b = device_code(argv[0]), device_code(argv[1])
+    if mapfile:
+        a = renamed(a, b, mapfile)
     bad = sorted(set(a[1]) ^ set(b[1]))
     bad += [s for s in a[2] if s in b[1] and (a[1][s] != b[1][s] or a[0].get(s) != b[0].get(s))]
     print('%d device symbols / %d kernels in %s, %d / %d in %s; symbol order %s'
-          % (len(a[2]), len(a[0]), sys.argv[1], len(b[2]), len(b[0]), sys.argv[2],
+          % (len(a[2]), len(a[0]), argv[0], len(b[2]), len(b[0]), argv[1],
              'equal' if a[2] == b[2] else 'DIFFERS'))
     for s in bad:
         print('DIFFERS  %s\n   resources (vgpr, agpr, sgpr, scratch, lds, code bytes): %s -> %s'
               % (K.demangle([s])[0], a[0].get(s), b[0].get(s)))
+        lines = [d for d in difflib.unified_diff(a[1].get(s, []), b[1].get(s, []), lineterm='', n=0)
+                 if d[0] in '+-' and d[:3] not in ('+++', '---')]
+        if s in a[1] and s in b[1] and len(lines) <= 8:
+            print('\n'.join('   ' + d for d in lines))
     if not bad and a[2] == b[2]:
         print('identical: resource rows and disassembly of every symbol')
     elif not bad:

@@ -77,6 +77,17 @@ def demangle(names):
     return r.stdout.splitlines()
 
 
+def short_name(n):
+    """a demangled kernel name without `void`, the anonymous namespace and the parameter list"""
+    n = n.replace('void ', '').replace('(anonymous namespace)::', '')
+    depth = 0
+    for i, ch in enumerate(n):            # cut the parameter list: the first '(' outside <...>
+        depth += (ch == '<') - (ch == '>')
+        if ch == '(' and depth == 0:
+            return n[:i]
+    return n
+
+
 def main():
     path = sys.argv[1]
     flt = sys.argv[2] if len(sys.argv) > 2 else ''
@@ -87,13 +98,7 @@ def main():
     names = demangle([r[0] for r in rows])
     print('%6s %5s %5s %8s %7s %9s  %s' % ('vgpr', 'agpr', 'sgpr', 'scratch', 'lds', 'code B', 'kernel'))
     for r, n in sorted(zip(rows, names), key=lambda t: t[1]):
-        n = n.replace('void ', '').replace('(anonymous namespace)::', '')
-        depth = 0
-        for i, ch in enumerate(n):            # cut the parameter list: the first '(' outside <...>
-            depth += (ch == '<') - (ch == '>')
-            if ch == '(' and depth == 0:
-                n = n[:i]
-                break
+        n = short_name(n)
         if flt and flt not in n:
             continue
         print('%6d %5d %5d %8d %7d %9d  %s' % (r[1], r[2], r[3], r[4], r[5], r[6], n))

@@ -18,9 +18,9 @@
 // order and distances are float64-exact.
 // A prepared index (scl_topn_index_build / scl_topn_index_query) keeps the norms, their bound and
 // the bf16 planes between calls; at most 32 queries then take
-//   topn_stream_score_kernel   one pass of every CU over the float32 rows -> scores [Q][R]
-//   topn_stream_select_kernel  the 32 smallest (score, index) pairs per (query, split)
-// in front of the same re-rank.
+//   topn_stream_score_kernel<D8, WIN>  one pass of every CU over the float32 rows -> scores [Q][R]
+//   topn_stream_select_kernel<WIN>     the 32 smallest (score, index) pairs per (query, split)
+// in front of the same re-rank (WIN: with a window per query; the host side is stream_query).
 #include <limits.h>
 #include <math.h>
 
@@ -843,85 +843,8 @@ __global__ __launch_bounds__(256) void topn_exact_filter_kernel(
 // ---------------------------------------------------------------------------------------
 // The STREAM route of scl_topn_index_query: at most 32 queries against a prepared index.
 //
-// topn_stream_score_kernel: scores[q][j] = refnorm[j] - 2 q.r_j for every reference, one pass over
-// the float32 rows.  The product is skinny ([Q <= 32, d] x ref^T), so nothing is shared between
-// waves and nothing goes through LDS: a WAVE owns 32-reference tiles (tile w, w + W, w + 2 W, .. of
-// the W waves of the grid), lane (r, h) loads row r's elements 8 t + 4 h .. + 3 straight into the B
-// operands of v_mfma_f32_32x32x2_f32 and keeps the query fragment of topn_scan_kernel (BF = 0)
-// resident.  A tile's registers come in two halves; each half is refilled for the wave's next tile
-// as soon as its products are issued, so half a tile (16 KB per wave) is always in flight.
-// Arithmetic: the same instruction on the same operands as the float32 scan — a float32 chain of
-// d products per score and one subtraction from the float32 norm — so the certificate's eps_q /
-// eps_r ("f32 MFMA chain of d terms") cover it unchanged.
-// The last tile may be ragged: rows past R re-read row R - 1 and are not written.  Query rows
-// past Q are zero and not written.  No scratch, no LDS.
-template <int D8>
-__global__ __launch_bounds__(256) void topn_stream_score_kernel(const float* __restrict__ ref,
-                                                                const float* __restrict__ refnorm,
-                                                                int R, const float* __restrict__ query,
-                                                                int Q, float* __restrict__ scores) {
-  constexpr int d = D8 * 8, H = D8 / 2;
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int r = lane & 31, h = lane >> 5;
-  const int ntiles = (R + 31) / 32;
-  const int nw = gridDim.x * 4;
-  int t = blockIdx.x * 4 + wid;
-  if (t >= ntiles) return;                                   // wave-uniform
-  f32x4 qf[D8];
-  {
-    const float* qp = query + (int64_t)(r < Q ? r : 0) * d + 4 * h;
-#pragma unroll
-    for (int u = 0; u < D8; ++u) {
-      qf[u] = *reinterpret_cast<const f32x4*>(qp + 8 * u);
-      if (r >= Q) qf[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-  }
-  auto row_of = [&](int tile) {
-    const int row = tile * 32 + r;
-    return ref + (int64_t)(row < R ? row : R - 1) * d + 4 * h;
-  };
-  f32x4 a[H], b[H];
-  {
-    const float* p = row_of(t);
-#pragma unroll
-    for (int u = 0; u < H; ++u) a[u] = *reinterpret_cast<const f32x4*>(p + 8 * u);
-#pragma unroll
-    for (int u = 0; u < H; ++u) b[u] = *reinterpret_cast<const f32x4*>(p + 8 * (H + u));
-  }
-  for (; t < ntiles; t += nw) {
-    const bool more = t + nw < ntiles;                       // wave-uniform
-    const float* pn = row_of(more ? t + nw : t);
-    const int ridx = t * 32 + r;
-    const float rn = refnorm[ridx < R ? ridx : R - 1];
-    f32x16 acc = zero16();
-#pragma unroll
-    for (int u = 0; u < H; ++u)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) acc = mfma32(qf[u][c], a[u][c], acc);
-    if (more) {
-#pragma unroll
-      for (int u = 0; u < H; ++u) a[u] = *reinterpret_cast<const f32x4*>(pn + 8 * u);
-    }
-#pragma unroll
-    for (int u = 0; u < H; ++u)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) acc = mfma32(qf[H + u][c], b[u][c], acc);
-    if (more) {
-#pragma unroll
-      for (int u = 0; u < H; ++u) b[u] = *reinterpret_cast<const f32x4*>(pn + 8 * (H + u));
-    }
-    if (ridx < R) {
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        const int row = acc_row(q, h);
-        if (row < Q) scores[(int64_t)row * R + ridx] = rn - 2.0f * acc[q];
-      }
-    }
-  }
-}
-
-// ---- the windowed stream route (scl_topn_index_query_window) ----
-// Every query has a window: the references whose position lies within `radius` of `center`.
+// With windows (scl_topn_index_query_window) every query has one: the references whose position
+// lies within `radius` of `center`.
 // One query's window against one point, in float64 with every operation rounded on its own (no
 // fused multiply-add): what NumPy's `dx*dx + dy*dy <= r2` decides, bit for bit.  r2 = rad * rad,
 // -1 for a negative radius, NaN for a NaN one: both compare false with everything.
@@ -940,28 +863,10 @@ __device__ __forceinline__ bool window_reaches(const double* __restrict__ box, d
   const double dy = fmax(fmax(box[1] - cy, cy - box[3]), 0.0);
   return dx * dx + dy * dy <= r2;
 }
-// the float32 whose score_key is all ones, the selection's "empty" key: a score the window masks
-constexpr unsigned kEmptyScoreBits = 0x7fffffffu;
-
-// topn_stream_score_kernel with windows.  xy [R][2] are the references' positions and box [tiles][4]
-// bounds those of each 32-reference tile (the geo block, topn_geo_at).  A wave passes over a tile that
-// no query's circle reaches: no row loads, no products, its [Q][32] scores are the empty marker.  In
-// the other tiles a (query, reference) pair outside the window gets the marker instead of its score,
-// decided per accumulator register from the lane's reference position and the row's circle in LDS
-// (win [32][4] doubles: cx, cy, r2).  Tiles, fragments, prefetch and arithmetic are that kernel's.
-template <int D8>
-__global__ __launch_bounds__(256) void topn_stream_score_window_kernel(
-    const float* __restrict__ ref, const float* __restrict__ refnorm, int R,
-    const float* __restrict__ query, int Q, float* __restrict__ scores, const double* __restrict__ xy,
-    const double* __restrict__ box, const double* __restrict__ center,
-    const double* __restrict__ radius) {
-  constexpr int d = D8 * 8, H = D8 / 2;
-  __shared__ double win[32 * 4];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int r = lane & 31, h = lane >> 5;
-  const int ntiles = (R + 31) / 32;
-  const int nw = gridDim.x * 4;
-  double wcx = 0.0, wcy = 0.0, wr2 = -1.0;                   // lane r: query r's circle (none past Q)
+// lane r: query r's circle (none past Q); the first 32 threads leave them in win [32][4]
+__device__ __forceinline__ void window_circles(const double* __restrict__ center,
+                                               const double* __restrict__ radius, int r, int Q,
+                                               double* win, double& wcx, double& wcy, double& wr2) {
   if (r < Q) {
 #pragma clang fp contract(off)
     const double rad = radius[r];
@@ -974,7 +879,47 @@ __global__ __launch_bounds__(256) void topn_stream_score_window_kernel(
     win[4 * r + 1] = wcy;
     win[4 * r + 2] = wr2;
   }
-  __syncthreads();
+}
+// the float32 whose score_key is all ones, the selection's "empty" key: a score the window masks
+constexpr unsigned kEmptyScoreBits = 0x7fffffffu;
+
+// topn_stream_score_kernel<D8, WIN>: scores[q][j] = refnorm[j] - 2 q.r_j for every reference, one
+// pass over the float32 rows.  The product is skinny ([Q <= 32, d] x ref^T), so nothing is shared
+// between waves and no operand goes through LDS: a WAVE owns 32-reference tiles (tile w, w + W,
+// w + 2 W, .. of the W waves of the grid), lane (r, h) loads row r's elements 8 t + 4 h .. + 3
+// straight into the B operands of v_mfma_f32_32x32x2_f32 and keeps the query fragment of
+// topn_scan_kernel (BF = 0) resident.  A tile's registers come in two halves; each half is refilled
+// for the wave's next tile as soon as its products are issued, so half a tile (16 KB per wave) is
+// always in flight.
+// Arithmetic: the same instruction on the same operands as the float32 scan — a float32 chain of
+// d products per score and one subtraction from the float32 norm — so the certificate's eps_q /
+// eps_r ("f32 MFMA chain of d terms") cover it unchanged.
+// The last tile may be ragged: rows past R re-read row R - 1 and are not written.  Query rows
+// past Q are zero and not written.  No scratch; no LDS without windows (xy, box, center and radius
+// are null then and never read).
+// WIN: xy [R][2] are the references' positions and box [tiles][4] bounds those of each 32-reference
+// tile (the geo block, topn_geo_at).  A wave passes over a tile that no query's circle reaches: no
+// row loads, no products, its [Q][32] scores are the empty marker.  In the other tiles a (query,
+// reference) pair outside the window gets the marker instead of its score, decided per accumulator
+// register from the lane's reference position and the row's circle in LDS (win [32][4] doubles: cx,
+// cy, r2).  Tiles, fragments, prefetch and arithmetic do not depend on WIN.
+template <int D8, bool WIN>
+__global__ __launch_bounds__(256) void topn_stream_score_kernel(
+    const float* __restrict__ ref, const float* __restrict__ refnorm, int R,
+    const float* __restrict__ query, int Q, float* __restrict__ scores, const double* __restrict__ xy,
+    const double* __restrict__ box, const double* __restrict__ center,
+    const double* __restrict__ radius) {
+  constexpr int d = D8 * 8, H = D8 / 2;
+  __shared__ double win[WIN ? 32 * 4 : 1];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int r = lane & 31, h = lane >> 5;
+  const int ntiles = (R + 31) / 32;
+  const int nw = gridDim.x * 4;
+  double wcx = 0.0, wcy = 0.0, wr2 = -1.0;                   // lane r: query r's circle (none past Q)
+  if constexpr (WIN) {
+    window_circles(center, radius, r, Q, win, wcx, wcy, wr2);
+    __syncthreads();
+  }
   // the wave's first tile from `tile` on that some query reaches; the ones passed over get the marker
   auto reached = [&](int tile) {
     for (; tile < ntiles; tile += nw) {
@@ -990,7 +935,8 @@ __global__ __launch_bounds__(256) void topn_stream_score_window_kernel(
     }
     return tile;
   };
-  int t = reached(blockIdx.x * 4 + wid);
+  int t = blockIdx.x * 4 + wid;
+  if constexpr (WIN) t = reached(t);
   if (t >= ntiles) return;                                   // wave-uniform; no block barriers below
   f32x4 qf[D8];
   {
@@ -1014,13 +960,18 @@ __global__ __launch_bounds__(256) void topn_stream_score_window_kernel(
     for (int u = 0; u < H; ++u) b[u] = *reinterpret_cast<const f32x4*>(p + 8 * (H + u));
   }
   while (t < ntiles) {
-    const int tn = reached(t + nw);
+    int tn = t + nw;
+    if constexpr (WIN) tn = reached(tn);
     const bool more = tn < ntiles;                           // wave-uniform
     const float* pn = row_of(more ? tn : t);
     const int ridx = t * 32 + r;
     const int rclamp = ridx < R ? ridx : R - 1;
     const float rn = refnorm[rclamp];
-    const double px = xy[2 * (int64_t)rclamp], py = xy[2 * (int64_t)rclamp + 1];
+    double px = 0.0, py = 0.0;
+    if constexpr (WIN) {
+      px = xy[2 * (int64_t)rclamp];
+      py = xy[2 * (int64_t)rclamp + 1];
+    }
     f32x16 acc = zero16();
 #pragma unroll
     for (int u = 0; u < H; ++u)
@@ -1042,9 +993,13 @@ __global__ __launch_bounds__(256) void topn_stream_score_window_kernel(
 #pragma unroll
       for (int q = 0; q < 16; ++q) {
         const int row = acc_row(q, h);
-        const double* w = win + 4 * row;
-        const bool in = window_holds(px, py, w[0], w[1], w[2]);
-        if (row < Q) scores[(int64_t)row * R + ridx] = in ? rn - 2.0f * acc[q] : __uint_as_float(kEmptyScoreBits);
+        if constexpr (WIN) {
+          const double* w = win + 4 * row;
+          const bool in = window_holds(px, py, w[0], w[1], w[2]);
+          if (row < Q) scores[(int64_t)row * R + ridx] = in ? rn - 2.0f * acc[q] : __uint_as_float(kEmptyScoreBits);
+        } else {
+          if (row < Q) scores[(int64_t)row * R + ridx] = rn - 2.0f * acc[q];
+        }
       }
     }
     t = tn;
@@ -1229,6 +1184,8 @@ __device__ __forceinline__ void stream_select_step(const float* __restrict__ sc,
   select_finish<NE + 1>(key, idx, lane, lk, li, ck, ci);
 }
 
+// WIN: over a score matrix with masked entries (stream_select_step<NE, true>)
+template <bool WIN>
 __global__ __launch_bounds__(256) void topn_stream_select_kernel(const float* __restrict__ scores,
                                                                  int R, int S, int per,
                                                                  float* __restrict__ cand_sc,
@@ -1245,43 +1202,7 @@ __global__ __launch_bounds__(256) void topn_stream_select_kernel(const float* __
   int ci = -1;
   for (int base = begin; base < end; base += 64 * kSelNE) {
     const int rem = end - base;                              // wave-uniform
-#define SCL_SEL_STEP(NE) stream_select_step<NE>(sc, base, end, lane, lkey[wid], lidx[wid], ck, ci)
-    if (rem > 512)
-      SCL_SEL_STEP(16);
-    else if (rem > 256)
-      SCL_SEL_STEP(8);
-    else if (rem > 128)
-      SCL_SEL_STEP(4);
-    else if (rem > 64)
-      SCL_SEL_STEP(2);
-    else
-      SCL_SEL_STEP(1);
-#undef SCL_SEL_STEP
-  }
-  if (lane < KEEP) {
-    const int64_t o = ((int64_t)qi * S + s) * KEEP + lane;
-    cand_sc[o] = ci >= 0 ? key_score(ck) : INFINITY;
-    cand_ix[o] = ci;
-  }
-}
-
-// topn_stream_select_kernel over a score matrix with masked entries (stream_select_step<NE, true>)
-__global__ __launch_bounds__(256) void topn_stream_select_window_kernel(
-    const float* __restrict__ scores, int R, int S, int per, float* __restrict__ cand_sc,
-    int* __restrict__ cand_ix) {
-  __shared__ unsigned lkey[4][kSelBuf];
-  __shared__ int lidx[4][kSelBuf];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int s = blockIdx.x * 4 + wid, qi = blockIdx.y;
-  if (s >= S) return;                                        // wave-uniform; no block barriers below
-  const float* sc = scores + (int64_t)qi * R;
-  const int begin = s * per;
-  const int end = begin + per < R ? begin + per : R;
-  unsigned ck = 0xffffffffu;
-  int ci = -1;
-  for (int base = begin; base < end; base += 64 * kSelNE) {
-    const int rem = end - base;                              // wave-uniform
-#define SCL_SEL_STEP(NE) stream_select_step<NE, true>(sc, base, end, lane, lkey[wid], lidx[wid], ck, ci)
+#define SCL_SEL_STEP(NE) stream_select_step<NE, WIN>(sc, base, end, lane, lkey[wid], lidx[wid], ck, ci)
     if (rem > 512)
       SCL_SEL_STEP(16);
     else if (rem > 256)
@@ -1502,7 +1423,7 @@ __global__ __launch_bounds__(256) void topn_wide_norm_kernel(const float* __rest
 // Arithmetic: inside a chunk the instruction's k-ordered float32 chain of 256 products; the chunk
 // sums are added in float64; refnorm[j] - 2 sum is formed in float64 and rounded to float32 once
 // (topn_wide_eps has the bound).
-// WIN: the windows of topn_stream_score_window_kernel with its predicates: a tile that no circle
+// WIN: the windows of topn_stream_score_kernel<D8, true> with its predicates: a tile that no circle
 // reaches is neither loaded nor multiplied and gets the empty marker, and in the other tiles a pair
 // outside the window gets the marker.  Dynamic LDS: the staged chunks | WIN: win [32][4] doubles.
 // The last tile may be ragged: rows past R re-read row R - 1 and are not written.  No scratch.
@@ -1524,18 +1445,7 @@ __global__ __launch_bounds__(256) void topn_wide_score_kernel(
   double* win = reinterpret_cast<double*>(lds + nl * 32 * kWideChunk);
   double wcx = 0.0, wcy = 0.0, wr2 = -1.0;                   // lane r: query r's circle (none past Q)
   if constexpr (WIN) {
-    if (r < Q) {
-#pragma clang fp contract(off)
-      const double rad = radius[r];
-      wcx = center[2 * r];
-      wcy = center[2 * r + 1];
-      wr2 = rad < 0.0 ? -1.0 : rad * rad;
-    }
-    if (threadIdx.x < 32) {
-      win[4 * r] = wcx;
-      win[4 * r + 1] = wcy;
-      win[4 * r + 2] = wr2;
-    }
+    window_circles(center, radius, r, Q, win, wcx, wcy, wr2);
   }
   // group g of the query block into LDS: 64 consecutive lanes move one row of a chunk
   auto stage = [&](int g) {
@@ -1849,24 +1759,31 @@ inline TopnEps topn_wide_eps(int d) {
 
 inline size_t rerank_lds_bytes(int M) { return (size_t)4 * (2 * M + 3 * KEEP + 4 + 66) * sizeof(float); }
 
-// the re-rank over sorted-or-not lists [Q][splits][KEEP] (-1 = empty slot), splits <= 32
+// the re-rank over sorted-or-not lists [Q][splits][KEEP] (-1 = empty slot), splits <= 32; with
+// count_out the lists hold the members of each query's window only (topn_rerank_window_kernel)
 void launch_rerank(const float* ref, const float* query, int Q, int d, int splits, int n,
                    int64_t idx_offset, const float* cs, const int* ci, int64_t* idx_out, double* dist_out,
                    const unsigned* rmax_bits, TopnEps eps, unsigned char* uncertified, double* bound_sq,
-                   hipStream_t st) {
+                   hipStream_t st, int* count_out = nullptr) {
   const int M = splits * KEEP;
   const size_t lds = rerank_lds_bytes(M);
   const dim3 rgrid((Q + 3) / 4);
-#define SCL_RERANK(NE)                                                                           \
-  SCL_LAUNCH("topn_rerank_kernel", topn_rerank_kernel<NE>, rgrid, dim3(256), lds, st, ref, query, \
-             Q, d, splits, n, idx_offset, cs, ci, idx_out, dist_out, rmax_bits, eps.q, eps.r,     \
-             uncertified, bound_sq)
-  if (M <= 256)
+#define SCL_RERANK(NE)                                                                              \
+  if (count_out)                                                                                    \
+    SCL_LAUNCH("topn_rerank_window_kernel", topn_rerank_window_kernel<NE>, rgrid, dim3(256), lds, st, \
+               ref, query, Q, d, splits, n, idx_offset, cs, ci, idx_out, dist_out, count_out,       \
+               rmax_bits, eps.q, eps.r, uncertified, bound_sq);                                     \
+  else                                                                                              \
+    SCL_LAUNCH("topn_rerank_kernel", topn_rerank_kernel<NE>, rgrid, dim3(256), lds, st, ref, query, \
+               Q, d, splits, n, idx_offset, cs, ci, idx_out, dist_out, rmax_bits, eps.q, eps.r,     \
+               uncertified, bound_sq)
+  if (M <= 256) {
     SCL_RERANK(4);
-  else if (M <= 512)
+  } else if (M <= 512) {
     SCL_RERANK(8);
-  else
+  } else {
     SCL_RERANK(16);
+  }
 #undef SCL_RERANK
 }
 
@@ -2109,24 +2026,50 @@ void launch_wide_score(const float* ref, const float* refnorm, int R, int d, con
              dim3(wide_score_wgs(R)), dim3(256), wide_score_lds_bytes(d, WIN), st, ref, refnorm, R, d,
              query, Q, scores, (const double*)g.xy, (const double*)g.box, center, radius);
 }
-// topn_rerank_window_kernel over the stream route's lists (splits <= 32)
-void launch_rerank_window(const float* ref, const float* query, int Q, int d, int splits, int n,
-                          int64_t idx_offset, const float* cs, const int* ci, int64_t* idx_out,
-                          double* dist_out, int* count_out, const unsigned* rmax_bits, TopnEps eps,
-                          unsigned char* uncertified, double* bound_sq, hipStream_t st) {
-  const int M = splits * KEEP;
-#define SCL_RERANK(NE)                                                                              \
-  SCL_LAUNCH("topn_rerank_window_kernel", topn_rerank_window_kernel<NE>, dim3((Q + 3) / 4), dim3(256), \
-             rerank_lds_bytes(M), st, ref, query, Q, d, splits, n, idx_offset, cs, ci, idx_out,     \
-             dist_out, count_out, rmax_bits, eps.q, eps.r, uncertified, bound_sq)
-  if (M <= 256)
-    SCL_RERANK(4);
-  else if (M <= 512)
-    SCL_RERANK(8);
+
+// One validated call of the stream route, narrow (scl_topn_index_query[_window]) or wide
+// (scl_topn_wide_query): score matrix -> lists of KEEP per split -> float64 re-rank.
+struct StreamCall {
+  const float* ref;
+  int R, d;
+  bool wide;                       // the score kernel: topn_wide_score_kernel, not topn_stream_score_kernel
+  const float* refnorm;            // of the index block, like
+  const unsigned* rmax_bits;       // its norm-bound word
+  TopnEps eps;
+  TopnGeo geo;                     // windows: the geo block, their circles and count_out; else all null
+  const double *center, *radius;
+  int* count_out;
+  const float* query;
+  int Q, n;
+  int64_t idx_offset, *idx_out;
+  double* dist_out;
+  unsigned char* uncertified;
+  double* bound_sq;
+  void* workspace;                 // topn_lists_at(.., kStream)
+  hipStream_t st;
+};
+template <bool WIN>
+int stream_query(const StreamCall& c) {
+  const StreamPlan sp = stream_plan(c.R);
+  const TopnLists w = topn_lists_at(c.workspace, c.R, c.Q, 0, kStream);
+  if (c.wide)
+    launch_wide_score<WIN>(c.ref, c.refnorm, c.R, c.d, c.query, c.Q, w.scores, c.geo, c.center, c.radius,
+                           c.st);
   else
-    SCL_RERANK(16);
-#undef SCL_RERANK
+    for_width(c.d, [&](auto d8) {
+      SCL_LAUNCH(WIN ? "topn_stream_score_kernel<window>" : "topn_stream_score_kernel",
+                 (topn_stream_score_kernel<decltype(d8)::value, WIN>), dim3(stream_score_wgs(c.R, c.d)),
+                 dim3(256), 0, c.st, c.ref, c.refnorm, c.R, c.query, c.Q, w.scores,
+                 (const double*)c.geo.xy, (const double*)c.geo.box, c.center, c.radius);
+    });
+  SCL_LAUNCH(WIN ? "topn_stream_select_kernel<window>" : "topn_stream_select_kernel",
+             topn_stream_select_kernel<WIN>, dim3((sp.splits + 3) / 4, c.Q), dim3(256), 0, c.st,
+             (const float*)w.scores, c.R, sp.splits, sp.per, w.cs, w.ci);
+  launch_rerank(c.ref, c.query, c.Q, c.d, sp.splits, c.n, c.idx_offset, w.cs, w.ci, c.idx_out, c.dist_out,
+                c.rmax_bits, c.eps, c.uncertified, c.bound_sq, c.st, c.count_out);
+  return scl_launch_status();
 }
+int stream_query(const StreamCall& c) { return c.count_out ? stream_query<true>(c) : stream_query<false>(c); }
 
 }  // namespace
 
@@ -2223,18 +2166,9 @@ extern "C" int scl_topn_index_query(const float* ref, int R, int d, const void* 
     return topn_scan_rerank(ref, R, query, Q, d, n, idx_offset, idx_out, dist_out, uncertified,
                             bound_sq, x, workspace, bf, st);
   // stream route: always scores from the float32 rows (the score flag only sizes the index)
-  const StreamPlan sp = stream_plan(R);
-  const TopnLists w = topn_lists_at(workspace, R, Q, 0, kStream);
-  const int wgs = stream_score_wgs(R, d);
-  for_width(d, [&](auto d8) {
-    SCL_LAUNCH("topn_stream_score_kernel", topn_stream_score_kernel<decltype(d8)::value>, dim3(wgs),
-               dim3(256), 0, st, ref, (const float*)x.refnorm, R, query, Q, w.scores);
-  });
-  SCL_LAUNCH("topn_stream_select_kernel", topn_stream_select_kernel, dim3((sp.splits + 3) / 4, Q),
-             dim3(256), 0, st, (const float*)w.scores, R, sp.splits, sp.per, w.cs, w.ci);
-  launch_rerank(ref, query, Q, d, sp.splits, n, idx_offset, w.cs, w.ci, idx_out, dist_out, x.rmax_bits,
-                topn_eps(d, 0), uncertified, bound_sq, st);
-  return scl_launch_status();
+  return stream_query({ref, R, d, false, x.refnorm, x.rmax_bits, topn_eps(d, 0), TopnGeo{}, nullptr,
+                       nullptr, nullptr, query, Q, n, idx_offset, idx_out, dist_out, uncertified,
+                       bound_sq, workspace, st});
 }
 
 // ---- the windowed query: the stream route over the references inside each query's circle ----
@@ -2281,33 +2215,9 @@ extern "C" int scl_topn_index_query_window(const float* ref, int R, int d, const
   if (!scl_aligned256(workspace) || workspace_bytes < topn_lists_at(nullptr, R, Q, 0, kStream).bytes)
     return SCL_E_WORKSPACE;
   if (!topn_flags_ok(flags)) return SCL_E_KIND;
-  hipStream_t st = (hipStream_t)stream;
-  const StreamPlan sp = stream_plan(R);
-  const TopnLists w = topn_lists_at(workspace, R, Q, 0, kStream);
-  const int wgs = stream_score_wgs(R, d);
-  for_width(d, [&](auto d8) {
-    SCL_LAUNCH("topn_stream_score_window_kernel", topn_stream_score_window_kernel<decltype(d8)::value>,
-               dim3(wgs), dim3(256), 0, st, ref, (const float*)x.refnorm, R, query, Q, w.scores,
-               (const double*)g.xy, (const double*)g.box, center, radius);
-  });
-  SCL_LAUNCH("topn_stream_select_window_kernel", topn_stream_select_window_kernel,
-             dim3((sp.splits + 3) / 4, Q), dim3(256), 0, st, (const float*)w.scores, R, sp.splits, sp.per,
-             w.cs, w.ci);
-  const int M = sp.splits * KEEP;
-  const TopnEps eps = topn_eps(d, 0);
-#define SCL_RERANK(NE)                                                                              \
-  SCL_LAUNCH("topn_rerank_window_kernel", topn_rerank_window_kernel<NE>, dim3((Q + 3) / 4), dim3(256), \
-             rerank_lds_bytes(M), st, ref, query, Q, d, sp.splits, n, idx_offset, (const float*)w.cs, \
-             (const int*)w.ci, idx_out, dist_out, count_out, (const unsigned*)x.rmax_bits, eps.q,   \
-             eps.r, uncertified, bound_sq)
-  if (M <= 256)
-    SCL_RERANK(4);
-  else if (M <= 512)
-    SCL_RERANK(8);
-  else
-    SCL_RERANK(16);
-#undef SCL_RERANK
-  return scl_launch_status();
+  return stream_query({ref, R, d, false, x.refnorm, x.rmax_bits, topn_eps(d, 0), g, center, radius,
+                       count_out, query, Q, n, idx_offset, idx_out, dist_out, uncertified, bound_sq,
+                       workspace, (hipStream_t)stream});
 }
 
 // ---- the wide stream route: a prepared index over rows of 512 .. 32768 columns (a multiple of 256) ----
@@ -2352,25 +2262,9 @@ extern "C" int scl_topn_wide_query(const float* ref, int R, int d, const void* i
   if (win && (!scl_aligned256(geo) || geo_bytes < g.bytes)) return SCL_E_WORKSPACE;
   if (!scl_aligned256(workspace) || workspace_bytes < topn_lists_at(nullptr, R, Q, 0, kStream).bytes)
     return SCL_E_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  const StreamPlan sp = stream_plan(R);
-  const TopnLists w = topn_lists_at(workspace, R, Q, 0, kStream);
-  const TopnEps eps = topn_wide_eps(d);
-  if (win) {
-    launch_wide_score<true>(ref, x.refnorm, R, d, query, Q, w.scores, g, center, radius, st);
-    SCL_LAUNCH("topn_stream_select_window_kernel", topn_stream_select_window_kernel,
-               dim3((sp.splits + 3) / 4, Q), dim3(256), 0, st, (const float*)w.scores, R, sp.splits, sp.per,
-               w.cs, w.ci);
-    launch_rerank_window(ref, query, Q, d, sp.splits, n, idx_offset, w.cs, w.ci, idx_out, dist_out,
-                         count_out, x.rmax_bits, eps, uncertified, bound_sq, st);
-  } else {
-    launch_wide_score<false>(ref, x.refnorm, R, d, query, Q, w.scores, g, nullptr, nullptr, st);
-    SCL_LAUNCH("topn_stream_select_kernel", topn_stream_select_kernel, dim3((sp.splits + 3) / 4, Q),
-               dim3(256), 0, st, (const float*)w.scores, R, sp.splits, sp.per, w.cs, w.ci);
-    launch_rerank(ref, query, Q, d, sp.splits, n, idx_offset, w.cs, w.ci, idx_out, dist_out, x.rmax_bits,
-                  eps, uncertified, bound_sq, st);
-  }
-  return scl_launch_status();
+  return stream_query({ref, R, d, true, x.refnorm, x.rmax_bits, topn_wide_eps(d), g, center, radius,
+                       count_out, query, Q, n, idx_offset, idx_out, dist_out, uncertified, bound_sq,
+                       workspace, (hipStream_t)stream});
 }
 
 extern "C" int scl_topn_exact_filter(const float* ref, int R, const float* query, int d,

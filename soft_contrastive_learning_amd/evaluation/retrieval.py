@@ -48,23 +48,28 @@ def _sized(nbytes, r, q, d, n, hint=''):
     return nbytes
 
 
-def _run(ref, query, n, idx_offset, certify, stats, call):
-    """One kernel pass over ``ref`` [R, d in _WIDTHS], n <= MAX_N: pads the query to d, allocates the
-    outputs, has ``call(query, idx, dist, flag, bound)`` make the C call (flag, bound: None without
-    ``certify``) and resolves exactly the queries that the call could not certify."""
+def _run(ref, query, n, idx_offset, certify, stats, call, window=None):
+    """One kernel pass over ``ref`` [R, d], n <= MAX_N: pads the query to d, allocates the outputs,
+    has ``call(query, idx, dist, flag, bound, count)`` make the C call(s) (flag, bound: None without
+    ``certify``) and resolves exactly the queries that the call could not certify.  ``window`` =
+    (positions, near, radius): the call is a windowed one and fills ``count`` (else None), which
+    ``stats`` receives."""
     query = _pad_width(query, ref.shape[1])
     q, dev = query.shape[0], ref.device
     idx = torch.empty((q, n), dtype=torch.int64, device=dev)
     dist = torch.empty((q, n), dtype=torch.float64, device=dev)
+    count = torch.empty(q, dtype=torch.int32, device=dev) if window is not None else None
     flag = torch.empty(q, dtype=torch.uint8, device=dev) if certify else None
     bound = torch.empty(q, dtype=torch.float64, device=dev) if certify else None
-    call(query, idx, dist, flag, bound)
+    call(query, idx, dist, flag, bound, count)
+    if stats is not None and window is not None:
+        stats['count'] = count
     if certify:
         bad = torch.nonzero(flag).reshape(-1)                      # (synchronises; usually empty)
         if stats is not None:
             stats['uncertified'] = int(bad.numel())
         if bad.numel():
-            _resolve_exactly(ref, query, n, int(idx_offset), bad, bound, dist, idx)
+            _resolve_exactly(ref, query, n, int(idx_offset), bad, bound, dist, idx, window=window)
     return dist, idx
 
 
@@ -98,7 +103,7 @@ def topn_l2(ref, query, n, idx_offset=0, score='f32', certify=True, stats=None):
     ref = _pad_width(ref)
     d, flags = ref.shape[1], SCORE_MODES[score]
 
-    def call(query, idx, dist, flag, bound):
+    def call(query, idx, dist, flag, bound, _):
         q = query.shape[0]
         nbytes = _sized(lib.scl_topn_l2_ex_workspace_bytes(r, q, d, n, flags), r, q, d, n,
                         " (d in {32,64,128,256}, n <= %d, n <= R)" % MAX_N)
@@ -215,32 +220,29 @@ class RetrievalIndex:
         lib = L.load()
         r, d = ref.shape
 
-        def call_wide(query, idx, dist, flag, bound):
+        def call(query, idx, dist, flag, bound, _):
             q = query.shape[0]
-            nbytes = _sized(lib.scl_topn_wide_query_workspace_bytes(r, q, d, n), r, q, d, n)
-            if self._ws is None or self._ws.numel() < nbytes:
-                self._ws = L.workspace(nbytes, ref.device)
+            self._workspace(lib.scl_topn_wide_query_workspace_bytes(r, q, d, n) if self._wide else
+                            lib.scl_topn_index_query_workspace_bytes(r, q, d, n, self._flags), q, n)
             if stats is not None:
-                stats['route'] = 'wide'
-            L.check(lib.scl_topn_wide_query(L.ptr(ref), r, d, L.ptr(self._index), self._index.numel(), None, 0,
-                                            L.ptr(query), q, None, None, n, self.idx_offset, L.ptr(idx),
-                                            L.ptr(dist), None, L.ptr(flag), L.ptr(bound), L.ptr(self._ws),
-                                            self._ws.numel(), L.stream_of(ref)))
-        if self._wide:
-            return _run(ref, query, n, self.idx_offset, certify, stats, call_wide)
-
-        def call(query, idx, dist, flag, bound):
-            q = query.shape[0]
-            nbytes = _sized(lib.scl_topn_index_query_workspace_bytes(r, q, d, n, self._flags), r, q, d, n)
-            if self._ws is None or self._ws.numel() < nbytes:
-                self._ws = L.workspace(nbytes, ref.device)
-            if stats is not None:
-                stats['route'] = 'stream' if q <= L.TOPN_STREAM_MAX_Q else 'scan'
-            L.check(lib.scl_topn_index_query(L.ptr(ref), r, d, L.ptr(self._index), self._index.numel(),
-                                             L.ptr(query), q, n, self.idx_offset, L.ptr(idx), L.ptr(dist),
-                                             L.ptr(flag), L.ptr(bound), L.ptr(self._ws), self._ws.numel(),
-                                             self._flags, L.stream_of(ref)))
+                stats['route'] = 'wide' if self._wide else 'stream' if q <= L.TOPN_STREAM_MAX_Q else 'scan'
+            head = (L.ptr(ref), r, d, L.ptr(self._index), self._index.numel())
+            out = (n, self.idx_offset, L.ptr(idx), L.ptr(dist))
+            tail = (L.ptr(flag), L.ptr(bound), L.ptr(self._ws), self._ws.numel())
+            if self._wide:
+                L.check(lib.scl_topn_wide_query(*head, None, 0, L.ptr(query), q, None, None, *out, None, *tail,
+                                                L.stream_of(ref)))
+            else:
+                L.check(lib.scl_topn_index_query(*head, L.ptr(query), q, *out, *tail, self._flags,
+                                                 L.stream_of(ref)))
         return _run(ref, query, n, self.idx_offset, certify, stats, call)
+
+    def _workspace(self, nbytes, q, n):
+        """the object's workspace, grown to ``nbytes`` (0: a shape the library does not take)"""
+        if nbytes == 0:
+            _sized(0, self.ref.shape[0], q, self.ref.shape[1], n)
+        if self._ws is None or self._ws.numel() < nbytes:
+            self._ws = L.workspace(nbytes, self.ref.device)
 
     def nearest_position(self, query_xy):
         """query_xy [Q, 2] (NumPy or a tensor on the index's device) -> (row int64 [Q], dist float64
@@ -290,40 +292,26 @@ class RetrievalIndex:
         radius = radius.contiguous()
         lib = L.load()
         r, d = ref.shape
-        query = _pad_width(query, d)
-        idx = torch.empty((q, n), dtype=torch.int64, device=dev)
-        dist = torch.empty((q, n), dtype=torch.float64, device=dev)
-        count = torch.empty(q, dtype=torch.int32, device=dev)
-        flag = torch.empty(q, dtype=torch.uint8, device=dev) if certify else None
-        bound = torch.empty(q, dtype=torch.float64, device=dev) if certify else None
         step = L.TOPN_STREAM_MAX_Q
-        for s in range(0, q, step):
-            g = min(step, q - s)
-            nbytes = _sized(lib.scl_topn_wide_query_workspace_bytes(r, g, d, n) if self._wide else
-                            lib.scl_topn_index_query_window_workspace_bytes(r, g, d, n, self._flags), r, g, d, n)
-            if self._ws is None or self._ws.numel() < nbytes:
-                self._ws = L.workspace(nbytes, dev)
-            part = slice(s, s + g)
-            head = (L.ptr(ref), r, d, L.ptr(self._index), self._index.numel(), L.ptr(self._geo),
-                    self._geo.numel(), L.ptr(query[part]), g, L.ptr(near[part]), L.ptr(radius[part]), n,
-                    self.idx_offset, L.ptr(idx[part]), L.ptr(dist[part]), L.ptr(count[part]),
-                    None if flag is None else L.ptr(flag[part]), None if bound is None else L.ptr(bound[part]),
-                    L.ptr(self._ws), self._ws.numel())
-            if self._wide:
-                L.check(lib.scl_topn_wide_query(*head, L.stream_of(ref)))
-            else:
-                L.check(lib.scl_topn_index_query_window(*head, self._flags, L.stream_of(ref)))
-        if stats is not None:
-            stats['route'] = 'window'
-            stats['count'] = count
-        if certify:
-            bad = torch.nonzero(flag).reshape(-1)                      # (synchronises; usually empty)
+
+        def call(query, idx, dist, flag, bound, count):
+            for s in range(0, q, step):
+                g = min(step, q - s)
+                self._workspace(lib.scl_topn_wide_query_workspace_bytes(r, g, d, n) if self._wide else
+                                lib.scl_topn_index_query_window_workspace_bytes(r, g, d, n, self._flags), g, n)
+                part = slice(s, s + g)
+                head = (L.ptr(ref), r, d, L.ptr(self._index), self._index.numel(), L.ptr(self._geo),
+                        self._geo.numel(), L.ptr(query[part]), g, L.ptr(near[part]), L.ptr(radius[part]), n,
+                        self.idx_offset, L.ptr(idx[part]), L.ptr(dist[part]), L.ptr(count[part]),
+                        None if flag is None else L.ptr(flag[part]),
+                        None if bound is None else L.ptr(bound[part]), L.ptr(self._ws), self._ws.numel())
+                if self._wide:
+                    L.check(lib.scl_topn_wide_query(*head, L.stream_of(ref)))
+                else:
+                    L.check(lib.scl_topn_index_query_window(*head, self._flags, L.stream_of(ref)))
             if stats is not None:
-                stats['uncertified'] = int(bad.numel())
-            if bad.numel():
-                _resolve_exactly(ref, query, n, self.idx_offset, bad, bound, dist, idx,
-                                 window=(self.positions, near, radius))
-        return dist, idx
+                stats['route'] = 'window'
+        return _run(ref, query, n, self.idx_offset, certify, stats, call, (self.positions, near, radius))
 
 
 _FILTER_CAP = 2048      # candidates within the bound kept per uncertified query

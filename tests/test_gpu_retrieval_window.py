@@ -80,7 +80,8 @@ def _traverse(r):
 
 
 # ---- 1. a window that holds everything is no window -------------------------------------------------------
-@pytest.mark.parametrize("r,q,d,n", [(33, 1, 32, 25), (4099, 32, 256, 25), (40000, 8, 128, 7)])
+@pytest.mark.parametrize("r,q,d,n", [(33, 1, 32, 25), (4099, 32, 256, 25), (40000, 8, 128, 7),
+                                     (65, 3, 64, 5)])
 def test_window_of_everything_equals_the_unwindowed_query(dev, r, q, d, n):
     ref, qry = U.retrieval_sets(r, q, d)
     xy = _traverse(r)
