@@ -648,8 +648,9 @@ __global__ __launch_bounds__((ConvCfg<CIN, KOUT, GEO>::NTHR), (GEO ? 2 : 1)) voi
 //   dW[k][c][kh][kw] = sum_{b,y,x} gz[b,y,x,k] * x[b, y+kh-1, x+kw-1, c].
 // The contraction runs over pixels — the SLOW index of both channels-last operands — so both
 // MFMA operands are read with ds_read_b64_tr_b16 out of row-major LDS tiles (the x halo
-// window of conv64_kernel and the gz tile); a tap row is an address offset, the three tap
-// columns of a row are one 12-pixel fragment shifted inside the lane (round 3, see the loop).
+// window of conv64_kernel and the gz tile); a tap row is a window-row offset and a tap column a
+// pixel offset of the x read: both shifts are LDS addresses, every MFMA operand is an aligned
+// register tuple as loaded and no vector instruction assembles one (see the loop).
 //   * v_mfma_f32_32x32x16_bf16 with M = 32 input channels, N = 32 output channels, 16 pixels
 //     per step; wave (mt, nt) keeps all nine taps of its 32 x 32 block: 144 accumulators;
 //   * persistent grid, one workgroup per CU accumulating over all its tiles, then ONE slab
@@ -658,7 +659,9 @@ __global__ __launch_bounds__((ConvCfg<CIN, KOUT, GEO>::NTHR), (GEO ? 2 : 1)) voi
 // LDS layout: each staged tile is TWO planes of 32 channels with 64-byte pixels and no padding.
 // A ds_read_b64_tr_b16 is served 32 lanes at a time (8-byte units, 32 of them per cycle); the
 // 32 lanes of a group address 4 pixels x (2 x 16 channels): unit = 8 * pixel + 4 * (channel
-// half) + piece, all distinct mod 32 — conflict-free.  (One 64-channel plane at 144 B per
+// half) + piece, all distinct mod 32 — conflict-free; the four pixels of a group are consecutive
+// in one window row, so a read that starts one or two pixels further right (kw = 1, 2) only
+// rotates the units.  (One 64-channel plane at 144 B per
 // pixel, fine for ds_read_b128, makes every transposed read 2-way conflicted: unit 18 * pixel.)
 // The planes are filled by LDS-DMA (global_load_lds_dwordx4: no staging registers, no
 // ds_write pass, 80 KB in flight per CU): one wave-instruction writes 1 KB = 16 pixels of a
@@ -877,10 +880,11 @@ __global__ __launch_bounds__(512, 1) void wrw64_kernel(const unsigned short* __r
   for (int t = 0; t < 9; ++t) acc[t] = zero16();
   // Bias gradient on the side: the B fragment of a step is 8 pixels of gz channel r of this
   // wave's n-tile — summed into one register per lane (v_dot2c_f32_bf16 against (1, 1): four
-  // instructions per nine MFMAs, in every wave so that the loop stays branch-free; only the
-  // waves mt == 0 of the workgroups cb == 0 write theirs out).
+  // instructions per nine MFMAs), behind a wave-uniform branch in the waves that write theirs
+  // out: mt == 0 of the workgroups cb == 0.
   float bsum = 0.f;
   typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+  const bool bias_wave = __builtin_amdgcn_readfirstlane((bslabs && wg_cb == 0 && mt == 0) ? 1 : 0) != 0;
 
   // The wave's 72 (step, tap) products of a tile run as ONE software pipeline: the window-row
   // fragment a product opens is requested six products earlier (an LDS transposed read returns
@@ -919,22 +923,16 @@ __global__ __launch_bounds__(512, 1) void wrw64_kernel(const unsigned short* __r
         lds + buf * WBUF + 2 * XPLANE + nt * GPLANE + (lrow * TWv + lcol) * WPL + ch0;
     // product i = 9 * s + t: step s of this wave's eight (first pixel (ry, cx)), tap t = 3 kh + kw.
     // A lane's A operand is 8 consecutive pixels of a window row for its channel; the three kw
-    // taps of a row are the same pixels shifted by 0 / 1 / 2 — so ONE fragment of 12 pixels (three
-    // transposed reads: pixels 0-3, 4-7, 8-11 of the lane's block) serves all three: kw = 1 is four
-    // v_alignbit, kw = 2 a renaming of registers.  And a window row serves the kh taps of three
-    // tile rows (wide tiles) / two steps (tall tiles): it is read once and stays in registers.
-    // LDS reads per wave and tile: 36 (52 tall) + 16 for B instead of 144 + 16 — the transposed
-    // reads of nine separate taps kept the LDS pipe busy for more cycles than the MFMAs take.
-    struct XFrag {
-      uint2 lo, hi, ex;
-    };
-    auto x_frag = [&](int wrow, int cx) {
-      const unsigned short* p = xl + (wrow * WCv + cx) * WPL;
-      XFrag f;
-      f.lo = __builtin_bit_cast(uint2, lds_tr16(p));
-      f.hi = __builtin_bit_cast(uint2, lds_tr16(p + 4 * WPL));
-      f.ex = __builtin_bit_cast(uint2, lds_tr16(p + 8 * WPL));
-      return f;
+    // taps of a row are the same pixels shifted by 0 / 1 / 2 — three fragments of 8 pixels (two
+    // transposed reads each), read at pixel offsets 0 / 1 / 2 of the window row: the shift is an
+    // address, and every product multiplies exactly the pixel pairs it always did (the results do
+    // not change by a bit against the fragment that was shifted inside the lane with four
+    // v_alignbit for kw = 1 and four register moves for kw = 2).  A window row serves the kh taps
+    // of three tile rows (wide tiles) / two steps (tall tiles): its fragments are read once and
+    // stay in registers.  LDS reads per wave and tile: 72 (102 tall) + 16 for B instead of 144 + 16
+    // for nine separate taps, which kept the LDS pipe busy for more cycles than the MFMAs take.
+    auto x_frag = [&](int wrow, int cx, int kw) {
+      return tr_pair(xl + (wrow * WCv + cx + kw) * WPL, 4 * WPL);
     };
     // window row (relative to the wave's first) and column slot of step s_, tap row kh
     // Wide tiles walk the left 16 columns of the wave's four rows, then the right ones (steps
@@ -945,10 +943,10 @@ __global__ __launch_bounds__(512, 1) void wrw64_kernel(const unsigned short* __r
     // is (s_, kh) the first product that touches its fragment?
     auto f_first = [](int s_, int kh) { return TWv == 32 ? ((s_ & 3) == 0 || kh == 2) : (s_ == 0 || kh >= 1); };
     const int row_w = TWv == 32 ? 4 * ph : 16 * ph;        // the wave's first window row
-    XFrag fr[NFR][NFC];
-    auto f_load = [&](int i) {                            // the fragment product i (kw = 0) opens
-      const int s_ = i / 9, kh = (i % 9) / 3;
-      fr[f_row(s_, kh)][f_col(s_)] = x_frag(row_w + f_row(s_, kh), 16 * f_col(s_));
+    u32x4 fr[NFR][NFC][3];
+    auto f_load = [&](int i) {                            // the fragment product i opens
+      const int s_ = i / 9, kh = (i % 9) / 3, kw = i % 3;
+      fr[f_row(s_, kh)][f_col(s_)][kw] = x_frag(row_w + f_row(s_, kh), 16 * f_col(s_), kw);
     };
     auto b_of = [&](int s_) {
       const int ry = TWv == 32 ? 4 * ph + (s_ & 3) : 16 * ph + 2 * s_;
@@ -959,26 +957,17 @@ __global__ __launch_bounds__(512, 1) void wrw64_kernel(const unsigned short* __r
     static_assert(STG * NI <= 9 * 8 - 12, "the last chunk needs time to land");
     u32x4 bf[2];
 #pragma unroll
-    for (int i = 0; i < LEAD; i += 3)
+    for (int i = 0; i < LEAD; ++i)
       if (f_first(i / 9, (i % 9) / 3)) f_load(i);
     bf[0] = b_of(0);
 #pragma unroll
     for (int i = 0; i < 9 * 8; ++i) {
       const int s_ = i / 9, kh = (i % 9) / 3, kw = i % 3;
-      if (i + LEAD < 9 * 8 && (i + LEAD) % 3 == 0 && f_first((i + LEAD) / 9, ((i + LEAD) % 9) / 3))
-        f_load(i + LEAD);
+      if (i + LEAD < 9 * 8 && f_first((i + LEAD) / 9, ((i + LEAD) % 9) / 3)) f_load(i + LEAD);
       if (i % 9 == 2 && s_ + 1 < 8) bf[(s_ + 1) & 1] = b_of(s_ + 1);
       if (!(DBG & 2) && i % STG == 0 && i / STG < NI) stage_chunk(stg, buf ^ 1, i / STG);
       __builtin_amdgcn_sched_barrier(0);
-      const XFrag& f = fr[f_row(s_, kh)][f_col(s_)];
-      u32x4 a;
-      if (kw == 0)
-        a = u32x4{f.lo.x, f.lo.y, f.hi.x, f.hi.y};
-      else if (kw == 1)
-        a = u32x4{__builtin_amdgcn_alignbit(f.lo.y, f.lo.x, 16), __builtin_amdgcn_alignbit(f.hi.x, f.lo.y, 16),
-                  __builtin_amdgcn_alignbit(f.hi.y, f.hi.x, 16), __builtin_amdgcn_alignbit(f.ex.x, f.hi.y, 16)};
-      else
-        a = u32x4{f.lo.y, f.hi.x, f.hi.y, f.ex.x};
+      const u32x4 a = fr[f_row(s_, kh)][f_col(s_)][kw];
       if constexpr ((DBG & 16) != 0) {
         // timing ablation (RESULTS MEANINGLESS): the same FLOPs, operand registers and accumulator
         // registers on v_mfma_f32_16x16x32_bf16 — what would the other MFMA shape be worth here?
@@ -996,7 +985,7 @@ __global__ __launch_bounds__(512, 1) void wrw64_kernel(const unsigned short* __r
       if (i == 8) WRW_STAMP(2);
       if (i == 35) WRW_STAMP(3);
       if (i == 71) WRW_STAMP(4);
-      if (i % 9 == 4) {
+      if (i % 9 == 4 && bias_wave) {
         const u32x4 bw = bf[s_ & 1];
         const bf16x2 one2 = __builtin_bit_cast(bf16x2, 0x3f803f80u);
         // (element by element: indexing the vector in a loop made hipcc feed word 0 four times)
