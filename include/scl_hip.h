@@ -992,6 +992,57 @@ int scl_geo_hit_dist(const double* ref_xy, int R, const double* query_xy, int Q,
                      int n, double* dist_out, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Match saliency (csrc/saliency.hip; evaluation/saliency.py): which positions of the conv5_3 map
+ * made a frame match, and that map drawn over the frame.  The counterpart of the reference's
+ * model/grad_nets.py, which returns the map (`grad_in`) so that a gradient can be taken there.
+ *
+ * scl_saliency_map
+ *   act, grad [B, h, w, 512] channels-last, float32 or bf16 (dtype: SCL_DT_*), 16-byte aligned: the
+ *             conv5_3 map before the channel L2 norm and the gradient of a score with respect to
+ *             it.  act is not read by SCL_SALIENCY_GRADNORM and may be NULL there.
+ *   map_out   float32 [B, h, w];  max_out float32 [B]
+ *   With P = h w:
+ *     SCL_SALIENCY_GRADCAM   w[b,c] = (sum_p grad[b,p,c]) (1/P),
+ *                            map[b,p] = max(0, sum_c w[b,c] act[b,p,c])
+ *     SCL_SALIENCY_GRADNORM  map[b,p] = sqrt(sum_c grad[b,p,c]^2)
+ *   Every sum is float32 in an order the code fixes, without atomics: the same input gives the same
+ *   bits.  max_out[b] is the largest value written to map_out[b], taken with fmaxf from +0: a NaN
+ *   stays in the map and is not the maximum.  One launch, one workgroup per image; any P >= 1.
+ *   (No "gradient x activation" mode: behind the channel L2 norm the score does not change when one
+ *   position's vector is scaled, so sum_c grad[p,c] act[p,c] is zero at every position up to
+ *   rounding.)
+ *
+ * scl_saliency_overlay
+ *   map [B, h, w] float32, scale [B] float32 (the value that maps to the top of the colour table:
+ *   max_out), frame and out uint8 [B, H, W, 3] (two buffers), lut uint8 [256][3], alpha in
+ *   0 .. 256.  y0, y1 int32 [H] and ty float32 [H]; x0, x1 int32 [W] and tx float32 [W]: for every
+ *   destination row / column the two source rows / columns and the weight of the second, made on
+ *   the host from the sizes alone (saliency.upsample_plan: half-pixel centres, clamped at the
+ *   border).  In float32, every operation rounded on its own (no fused multiply-add, IEEE division):
+ *     top = m[y0,x0] + (m[y0,x1] - m[y0,x0]) tx;   bot = m[y1,x0] + (m[y1,x1] - m[y1,x0]) tx
+ *     v = top + (bot - top) ty;   r = scale > 0 ? v / scale : 0
+ *     r = (r == r) ? min(max(r, 0), 1) : 0;   q = (int)(r 255 + 0.5)
+ *     out[c] = (alpha lut[q][c] + (256 - alpha) frame[c] + 128) >> 8
+ *   Any H, W >= 1, larger or smaller than h, w.  An index read from a table is clamped into the map.
+ *
+ * Both return SCL_E_NULL for a missing pointer; SCL_E_SHAPE for B outside 1..SCL_SALIENCY_MAX_B, a
+ * side outside 1..SCL_SALIENCY_MAX_SIDE, h w above SCL_SALIENCY_MAX_P, B H W above 2^32, alpha
+ * outside 0..256 or an operand that is not aligned (act, grad: 16 bytes; float32 and int32
+ * operands: 4); SCL_E_KIND for an unknown dtype or mode; nothing is launched then.
+ * ------------------------------------------------------------------------- */
+#define SCL_SALIENCY_GRADCAM 0
+#define SCL_SALIENCY_GRADNORM 1
+#define SCL_SALIENCY_MAX_B 65535
+#define SCL_SALIENCY_MAX_SIDE 16384
+#define SCL_SALIENCY_MAX_P (1 << 22)
+int scl_saliency_map(const void* act, const void* grad, int dtype, int B, int h, int w, int mode,
+                     float* map_out, float* max_out, void* stream);
+int scl_saliency_overlay(const float* map, const float* scale, int B, int h, int w, const void* frame,
+                         int H, int W, const int* y0, const int* y1, const float* ty, const int* x0,
+                         const int* x1, const float* tx, const void* lut, int alpha, void* out,
+                         void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Host utility for the checkpoint bundle reader / writer (tf_bundle.py; the reference
  * restores and saves through tf.train.Saver, train/train.py:882-905, 984, 1079, 1102):
  * CRC-32C (Castagnoli, reflected 0x82F63B78) of n bytes continued from `crc` (0 to start),

@@ -12,7 +12,7 @@ def install_as_learnlarge():
     """Make the reference's own import lines resolve to this backend: its scripts import
     ``learnlarge.model.nets``, ``learnlarge.model.losses``, ``learnlarge.util.cv`` / ``.io`` / ``.meta``
     (train/train.py:15-25, evaluation/inference.py:11-16, evaluation/top-n.py:8-10) and
-    ``pointnetvlad.pointnetvlad_cls``.  Registers
+    ``pointnetvlad.pointnetvlad_cls``; ``learnlarge.model.grad_nets`` for who imports it by hand.  Registers
     those names in ``sys.modules`` (a ``learnlarge`` package that is really installed is left
     alone and the call raises) and returns the alias package."""
     import importlib
@@ -21,7 +21,7 @@ def install_as_learnlarge():
     if 'learnlarge' in sys.modules and not getattr(sys.modules['learnlarge'], '_scl_alias', False):
         raise RuntimeError("a real 'learnlarge' package is already imported")
     names = {'model': 'model', 'model.nets': 'model.nets', 'model.losses': 'model.losses',
-             'util': 'util', 'util.cv': 'util.cv', 'util.io': 'util.io', 'util.meta': 'util.meta'}
+             'model.grad_nets': 'model.grad_nets', 'util': 'util', 'util.cv': 'util.cv', 'util.io': 'util.io', 'util.meta': 'util.meta'}
     pkg = types.ModuleType('learnlarge')
     pkg._scl_alias = True
     pkg.__path__ = []                                   # a package: `import learnlarge.model.nets`

@@ -45,6 +45,7 @@ GEO_SLAB = 256             # SCL_GEO_SLAB: references per LDS slab of scl_geo_ne
 GEO_BLOCK_QUERIES = 256    # SCL_GEO_BLOCK_QUERIES: queries per workgroup of its query-per-lane route
 GEO_SMALL_Q = 32           # SCL_GEO_SMALL_Q: at most this many queries put the lanes over the references
 GEO_TARGET_BLOCKS = 1024   # SCL_GEO_TARGET_BLOCKS: workgroups the split count aims at
+SALIENCY_GRADCAM, SALIENCY_GRADNORM = 0, 1   # mode of scl_saliency_map
 
 _p = ctypes.c_void_p
 _i = ctypes.c_int
@@ -179,6 +180,8 @@ SIGNATURES = {
     "scl_geo_nearest_workspace_bytes": (_z, [_i, _i]),
     "scl_geo_nearest": (_i, [_p, _i, _p, _i, _p, _p, _p, _z, _p]),
     "scl_geo_hit_dist": (_i, [_p, _i, _p, _i, _p, _i, _p, _p]),
+    "scl_saliency_map": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "scl_saliency_overlay": (_i, [_p, _p, _i, _i, _i, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p]),
 }
 
 _libs = {}

@@ -144,6 +144,36 @@ class Localizer:
         """``locate`` of ``prepare_raw(frames, rule, **kw)``."""
         return self.locate(self.prepare_raw(frames, rule, **kw), near, radius)
 
+    def explain(self, images, k=0, mode='gradcam', near=None, radius=None):
+        """``locate(images, near, radius)`` plus WHY: -> (idx, feature_dist, xy, map [B, h, w] float32,
+        scale [B] float32), the last two on the device (evaluation/saliency.py: ``MatchSaliency.explain``;
+        draw them with ``saliency.overlay``).  Each frame is explained against the index's own
+        whitened row of its k-th hit; a frame without a k-th hit (row -1 under a window) gets an
+        all-zero map and scale 0.  Needs the resident index: with ``query_fn`` it raises."""
+        if self._index is None:
+            raise ValueError('explain needs the resident index and the device model: a Localizer made '
+                             'with query_fn has neither')
+        from ..model import nets
+        from .saliency import MatchSaliency
+        k = int(k)
+        if not 0 <= k < self.n:
+            raise ValueError('k=%d: the localiser keeps n=%d hits per frame' % (k, self.n))
+        model = self.model or nets.default_model()
+        with torch.no_grad():
+            t = images if isinstance(images, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(images))
+            t = t.to(next(model.parameters()).device)
+            desc = nets.output(t, model=model).float()
+        dist, local = self.query_thinned(desc, near, radius)
+        found = local >= 0
+        idx = np.where(found, self._orig[np.where(found, local, 0)], -1)
+        xy = np.where(found[..., None], self.ref_xy[np.where(found, idx, 0)], np.nan)
+        rows = torch.from_numpy(np.where(found[:, k], local[:, k], 0)).to(self._index.ref.device)
+        target = self._index.ref[rows, :self._index.width]
+        m, scale = MatchSaliency(model, self.pca).explain(t, target, mode)
+        hit = torch.from_numpy(found[:, k]).to(m.device)
+        return (idx, dist, xy, torch.where(hit[:, None, None], m, torch.zeros_like(m)),
+                torch.where(hit, scale, torch.zeros_like(scale)))
+
     def payload(self, local_idx, feature_dist, full_xy_dists=None, query_xy=None):
         """``top_n.retrieve``'s output list [top_i, top_g_dists, top_f_dists, gt_i, gt_g_dist, ref_idx]
         (evaluation/top-n.py:110-119) from the hits of ``query_thinned`` for every query, in order, and

@@ -1371,17 +1371,33 @@ class VGG16NetVLAD(torch.nn.Module):
                 x = F.relu(x)
         return x
 
-    def forward(self, image_batch):
+    def forward_with_map(self, image_batch, vlad=True, cut=False):
+        """(what ``forward`` / ``forward_vgg16`` return, the conv5_3 map it was computed from): the
+        one code path of both and of model/grad_nets.py, whose ``grad_in`` the second value is —
+        ``features()``' own tensor, in the compute dtype, the node the first value hangs on.
+        ``cut``: the backbone runs under ``no_grad`` and the map is a leaf that requires a gradient,
+        so a gradient taken at the map costs a backward pass of the head alone
+        (evaluation/saliency.py)."""
         _FWD.planes = None
-        x = self.features(image_batch)
-        # the plane images features() had written by its own (forced) packing launch, or None
-        planes = fresh_vlad_planes(self.assignment_kernel)
-        return netvlad(x, self.assignment_kernel, self.cluster_centers, True, planes)
+        if cut:
+            with torch.no_grad():
+                grad_in = self.features(image_batch)
+            grad_in = grad_in.detach().requires_grad_()
+        else:
+            grad_in = self.features(image_batch)
+        if vlad:
+            # the plane images features() had written by its own (forced) packing launch, or None
+            planes = fresh_vlad_planes(self.assignment_kernel)
+            return netvlad(grad_in, self.assignment_kernel, self.cluster_centers, True, planes), grad_in
+        x = grad_in.float()
+        return x * torch.rsqrt(torch.clamp_min((x * x).sum(dim=-1, keepdim=True), 1e-12)), grad_in
+
+    def forward(self, image_batch):
+        return self.forward_with_map(image_batch)[0]
 
     def forward_vgg16(self, image_batch):
         """model/nets.py:72-131: backbone + channel L2 norm, no VLAD."""
-        x = self.features(image_batch).float()
-        return x * torch.rsqrt(torch.clamp_min((x * x).sum(dim=-1, keepdim=True), 1e-12))
+        return self.forward_with_map(image_batch, vlad=False)[0]
 
     # ---- checkpoint layout (TF variable names and shapes) ----------------------
     def state_dict_tf(self):
