@@ -1043,6 +1043,61 @@ int scl_saliency_overlay(const float* map, const float* scale, int B, int h, int
                          void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * k-means on the conv5_3 descriptors (csrc/kmeans.hip; model/vlad_init.py): the Lloyd step a
+ * NetVLAD head is seeded with.  D = SCL_VLAD_D = 512 and 1 <= K <= SCL_VLAD_K = 64 only, float32 only.
+ *
+ * scl_kmeans_assign
+ *   x [N, 512] and centres [K, 512] float32, 16-byte aligned; offsets [K] float32.  Per row n and
+ *   cluster k
+ *       score[n,k] = fl32(x_n . c_k) - offsets[k]           (a float32 subtraction)
+ *   where the dot product is ONE float32 fmaf chain over d = 0, 1, .., 511 from +0
+ *   (v_mfma_f32_32x32x2_f32).  A score takes part when it is neither a NaN nor -inf; +inf does.
+ *   With the scores that take part ordered by (score descending, k ascending):
+ *     label[n]  int32    k of the first entry, -1 when there is none
+ *     best[n]   float32  its score, -inf when there is none
+ *     second[n] float32  the score of the second entry, -inf when there is none (K = 1 always)
+ *   part_sum NULL: nothing else is written.  Otherwise part_cnt and part_inertia are required, and
+ *   workgroup g, which owns the rows [g SCL_KMEANS_ROWS, min(N, (g + 1) SCL_KMEANS_ROWS)), writes
+ *     part_sum[g, k, :]   float32  the sum of its rows with label k: one float32 fmaf chain per
+ *                                  coordinate over ALL its rows in ascending order, row n entering as
+ *                                  fmaf(label[n] == k ? 1 : 0, label[n] < 0 ? 0 : x[n, d], sum)
+ *                                  (onehot^T X on the same instruction).  A row with label -1 is
+ *                                  taken as zeros and changes nothing; a LABELLED row with a
+ *                                  non-finite coordinate makes that coordinate NaN in every cluster.
+ *     part_cnt[g, k]      int32    its rows with label k
+ *     part_inertia[g]     float64  sum over its labelled rows, ascending, of |x_n|^2 - 2 best[n];
+ *                                  |x_n|^2 = (sum of squares over even d) + (over odd d), each an
+ *                                  ascending float64 chain
+ *   G = ceil(N / SCL_KMEANS_ROWS): the partition depends on N alone, there are no atomics, and the
+ *   bits do not depend on the device.  The workspace (scl_kmeans_workspace_bytes(N, K), 256-byte
+ *   aligned) receives the operand image of the centres — even and odd d in two planes, rows K .. 63
+ *   zero, their offsets +inf so that a padded slot scores -inf and never takes part — which a
+ *   prologue kernel of the same call writes; two calls in flight at once need a workspace each.
+ *
+ * scl_kmeans_update
+ *   For every k: counts[k] = sum_g part_cnt[g, k]; new_centres[k, d] = fl32(S / counts[k]) with
+ *   S = sum_g part_sum[g, k, d] in float64, g ascending, and the division in float64 (one rounding
+ *   to float32); counts[k] == 0 copies old_centres[k, :].  inertia[0] = sum_g part_inertia[g],
+ *   float64, g ascending.  new_centres may not alias old_centres.
+ *
+ * scl_kmeans_workspace_bytes(N, K): pure host function, a multiple of 256; 0 for a shape without
+ * a kernel: N < 1, N > SCL_KMEANS_MAX_N, K outside 1..64.
+ *
+ * Both calls return SCL_E_NULL for a missing pointer (part_cnt, part_inertia: only with part_sum),
+ * then SCL_E_SHAPE (N, K, G out of range; x, centres, part_sum or the centre arrays not 16-byte
+ * aligned), then SCL_E_WORKSPACE (too small, not 256-byte aligned); nothing is launched then.
+ * ------------------------------------------------------------------------- */
+#define SCL_KMEANS_ROWS 128          /* rows per workgroup: G = ceil(N / SCL_KMEANS_ROWS) */
+#define SCL_KMEANS_MAX_N (1 << 22)
+size_t scl_kmeans_workspace_bytes(int N, int K);
+int scl_kmeans_assign(const float* x, int N, const float* centres, const float* offsets, int K,
+                      int* label, float* best, float* second, float* part_sum, int* part_cnt,
+                      double* part_inertia, void* work, size_t work_bytes, void* stream);
+int scl_kmeans_update(const float* part_sum, const int* part_cnt, const double* part_inertia, int G,
+                      int K, const float* old_centres, float* new_centres, int* counts,
+                      double* inertia, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Host utility for the checkpoint bundle reader / writer (tf_bundle.py; the reference
  * restores and saves through tf.train.Saver, train/train.py:882-905, 984, 1079, 1102):
  * CRC-32C (Castagnoli, reflected 0x82F63B78) of n bytes continued from `crc` (0 to start),

@@ -46,6 +46,8 @@ GEO_BLOCK_QUERIES = 256    # SCL_GEO_BLOCK_QUERIES: queries per workgroup of its
 GEO_SMALL_Q = 32           # SCL_GEO_SMALL_Q: at most this many queries put the lanes over the references
 GEO_TARGET_BLOCKS = 1024   # SCL_GEO_TARGET_BLOCKS: workgroups the split count aims at
 SALIENCY_GRADCAM, SALIENCY_GRADNORM = 0, 1   # mode of scl_saliency_map
+KMEANS_ROWS = 128          # SCL_KMEANS_ROWS: rows per workgroup of scl_kmeans_assign; G = ceil(N / it)
+KMEANS_MAX_N = 1 << 22     # SCL_KMEANS_MAX_N
 
 _p = ctypes.c_void_p
 _i = ctypes.c_int
@@ -182,6 +184,9 @@ SIGNATURES = {
     "scl_geo_hit_dist": (_i, [_p, _i, _p, _i, _p, _i, _p, _p]),
     "scl_saliency_map": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p]),
     "scl_saliency_overlay": (_i, [_p, _p, _i, _i, _i, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p]),
+    "scl_kmeans_workspace_bytes": (_z, [_i, _i]),
+    "scl_kmeans_assign": (_i, [_p, _i, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _z, _p]),
+    "scl_kmeans_update": (_i, [_p, _p, _p, _i, _i, _p, _p, _p, _p, _p]),
 }
 
 _libs = {}

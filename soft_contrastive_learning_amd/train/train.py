@@ -114,6 +114,16 @@ def make_parser():
     p.add_argument('--out_dim', default=512, type=int)
     p.add_argument('--reduction', default='none', help='none, 1fc, 2fc, 3fc')
     p.add_argument('--vlad_cores', default=64, type=int)
+    # the NetVLAD head from data (model/vlad_init.py; new work: the reference warm-starts from a
+    # released model that has one)
+    p.add_argument('--vlad_init', default='none', choices=['none', 'kmeans'],
+                   help='kmeans: before the first step, seed the NetVLAD head with k-means on conv5_3 '
+                        'descriptors of --vlad_init_images frames of the training set; --checkpoint may '
+                        'then lack the two head variables')
+    p.add_argument('--vlad_init_images', type=int, default=500)
+    p.add_argument('--vlad_init_per_image', type=int, default=100)
+    p.add_argument('--vlad_init_iters', type=int, default=100)
+    p.add_argument('--vlad_init_seed', type=int, default=0)
     # hard negative mining (:1288-1293)
     p.add_argument('--mining_step', type=int, default=250)
     p.add_argument('--mining_cache_size', type=int, default=1000)
@@ -665,6 +675,16 @@ def restore(flags, model, opt, verbose=True):
     returns the global step.  Returns the step to continue from."""
     if not flags.checkpoint:
         return 0
+    if getattr(flags, 'vlad_init', 'none') == 'kmeans':
+        # the head is about to be seeded from data: a checkpoint without the two head variables
+        # (and with nothing else missing) will do; flags.vlad_init_found says whether it had them
+        from ..model import vlad_init
+        _, missing = vlad_init.load_without_head(model, flags.checkpoint, head=False)
+        flags.vlad_init_found = not missing
+        if reduction.head_of(model) is not None and verbose:
+            for name, _ in reduction.head_of(model).tf_variables():
+                print('Newly initialized: {}'.format(name))
+        return 0
     got = checkpoint.load(model, flags.checkpoint, optimizer=opt if flags.resume else None,
                           head=flags.resume)
     head = reduction.head_of(model)
@@ -672,6 +692,40 @@ def restore(flags, model, opt, verbose=True):
         for name, _ in head.tf_variables():
             print('Newly initialized: {}'.format(name))
     return got if flags.resume else 0
+
+
+def check_vlad_init(flags):
+    """--vlad_init kmeans needs a head to seed, frames to seed it from, and a run that starts."""
+    if flags.vlad_init != 'kmeans':
+        return
+    if flags.vlad_cores != 64:
+        raise SystemExit('--vlad_init kmeans seeds the NetVLAD head: it needs --vlad_cores 64')
+    if not (flags.synthetic_dataset > 0 or flags.shuffled_root):
+        raise SystemExit('--vlad_init kmeans takes its frames from the training set: it needs '
+                         '--synthetic_dataset M or --shuffled_root DIR')
+    if flags.resume:
+        raise SystemExit('--vlad_init kmeans would replace the head --resume restores (and keep its '
+                         'optimizer slots): seed the head in a run that starts, or drop one of the two')
+    if flags.vlad_init_images < 1 or flags.vlad_init_per_image < 1 or flags.vlad_init_iters < 1:
+        raise SystemExit('--vlad_init_images, --vlad_init_per_image and --vlad_init_iters must be positive')
+
+
+def seed_vlad_head(flags, model, tuple_shape):
+    """--vlad_init kmeans, after the restore and before the first step: ``vlad_init.init_head`` on the
+    first --vlad_init_images entries of a seeded permutation of epoch 0's local reference set.
+    Every rank runs it alike: the frames, the seeds and the restored weights are the same on all of
+    them and the kernels fix every summation order, so the ranks hold the same head bit for bit
+    without a collective.  Returns the log record."""
+    from ..model import vlad_init
+    local_ref = open_sets(flags, 0)[0]
+    indices = np.random.RandomState(flags.vlad_init_seed).permutation(len(local_ref))[:flags.vlad_init_images]
+    rec = vlad_init.init_head(model, local_ref, indices, flags.tuples_per_batch * sum(tuple_shape),
+                              per_image=flags.vlad_init_per_image, iters=flags.vlad_init_iters,
+                              seed=flags.vlad_init_seed)
+    out = {'event': 'vlad_init', 'images': int(len(indices))}
+    out.update(rec)
+    out['replaced_checkpoint_head'] = bool(getattr(flags, 'vlad_init_found', False))
+    return out
 
 
 def main(argv=None):
@@ -682,6 +736,7 @@ def main(argv=None):
     if flags.vlad_cores not in (0, 64) or flags.reduction not in ('none',) + reduction.KINDS:
         raise SystemExit('only --vlad_cores 64 | 0 with --reduction none|1fc|2fc|3fc is on the hot path')
     check_tuple_sizes(flags)
+    check_vlad_init(flags)
     if flags.skip_nonfinite and flags.optimizer_impl != 'hip':
         raise SystemExit('--skip_nonfinite 1 needs --optimizer_impl hip: the skip is decided on the device, '
                          'inside the update kernel')
@@ -771,6 +826,8 @@ def main(argv=None):
                 log.flush()
             to_boards(rec)
         try:
+            if flags.vlad_init == 'kmeans':
+                write(seed_vlad_head(flags, model, tuple_shape))
             for epoch in range(flags.max_epoch):
                 train_dataset_epoch(flags, epoch, state, write)
         finally:
