@@ -680,6 +680,10 @@ int scl_build_is_diag(void);
  *                 (CORRECT results: A/B partner)
  *   2300          weight-gradient kernel: every 32x32x16 product issued as two 16x16x32 MFMAs on the
  *                 same registers (timing only: would the other MFMA shape pay here?  It does not)
+ *   2400 / 2404   weight-gradient kernel on [64 c] x [128 k] blocks: the whole-tile schedule / the
+ *                 half-tile schedule (four LDS slots, waves 4-7 half a tile behind waves 0-3).  CORRECT,
+ *                 bit-identical results: A/B partners (2404 measured equal or slower: not in the product)
+ *   2008          the clock stamps of 2004 on the half-tile schedule, waves 0 and 4 (timing only)
  *   100000 * s    Gram loss, B <= 256: force s K-splits
  *   100 + s       top-n: force s reference splits (1..32) instead of the planner's choice
  *   1000 * b (+ 100 + s)   top-n scan: b bit 0 no selection, bit 1 no tile staging,

@@ -4,10 +4,12 @@ step (24 x 640x480: conv1_2 .. conv5_3 at their resolutions, post-ReLU-like oper
 of x exactly zero, the incoming gradient masked the same way), alternating between the product
 kernels (variant 0) and diagnostic variants, e.g. 2200 = round 4's staging without the buffer path.
 
-    python scripts/wrw_ab.py [--variants 0,2200] [--rounds 3] [--layers 4_2,5_1]
+    python scripts/wrw_ab.py [--variants 0,2200] [--rounds 3] [--layers 4_2,5_1] [--reps 5]
 
-Prints microseconds per launch (kernel + reduce, HIP events around `iters` back-to-back calls) and
-checks that every variant's gradient is bit-identical to variant 0's.
+Prints microseconds per launch (kernel + reduce, HIP events around `iters` back-to-back calls; the
+best of the rounds, and with --reps N every round's median of N such figures) and checks that every
+variant's gradient is bit-identical to variant 0's.  2400 / 2404 = [64 c] x [128 k] blocks on the
+whole-tile / half-tile schedule.
 """
 import argparse
 import json
@@ -47,6 +49,7 @@ def main():
     ap.add_argument('--variants', default='0,2200')
     ap.add_argument('--rounds', type=int, default=3)
     ap.add_argument('--iters', type=int, default=10)
+    ap.add_argument('--reps', type=int, default=1, help='figures per round and variant; the round counts their median')
     ap.add_argument('--batch', type=int, default=24)
     ap.add_argument('--height', type=int, default=480)
     ap.add_argument('--width', type=int, default=640)
@@ -76,12 +79,16 @@ def main():
         gb = torch.empty(cout, device=dev)
         gf = 2.0 * args.batch * h * w * cin * cout * 9 / 1e9
         best = {v: float('inf') for v in variants}
+        per_round = {v: [] for v in variants}
         outs = {}
         for _ in range(args.rounds):
             for v in variants:
                 lib.scl_debug_set_variant(v)
                 try:
-                    best[v] = min(best[v], timed(lambda: nets.wrw64(x, gy, wt, bias_grad=gb, pool_idx=pidx), args.iters))
+                    us = sorted(timed(lambda: nets.wrw64(x, gy, wt, bias_grad=gb, pool_idx=pidx), args.iters)
+                                for _ in range(args.reps))[args.reps // 2]
+                    best[v] = min(best[v], us)
+                    per_round[v].append(us)
                     outs[v] = (nets.wrw64(x, gy, wt, bias_grad=gb, pool_idx=pidx).clone(), gb.clone())
                 finally:
                     lib.scl_debug_set_variant(0)
@@ -90,7 +97,10 @@ def main():
         print('%-5s %5d %5d %9.1f | %s  %s' % (name, cin, cout, gf, '  '.join(
             '%8.1f (%5.0f)' % (best[v], gf / best[v] * 1e3) for v in variants),
             'bit-identical' if same else 'RESULTS DIFFER'))
-        rows.append(dict(layer=name, cin=cin, cout=cout, h=h, w=w, gflop=gf, us=best, identical=same))
+        if args.reps > 1:
+            print('      per round: %s' % '  |  '.join(
+                'v%d %s' % (v, ' / '.join('%.0f' % u for u in per_round[v])) for v in variants))
+        rows.append(dict(layer=name, cin=cin, cout=cout, h=h, w=w, gflop=gf, us=best, per_round=per_round, identical=same))
         del x, gy
     tot = {v: sum(r['us'][v] for r in rows) for v in variants}
     print('sum of the %d launches: %s' % (len(rows), '  '.join('v%d %.1f us' % (v, tot[v]) for v in variants)))

@@ -15,8 +15,10 @@
 //                              its input while staging: conv_launch
 // Weight gradient — scl_wrw3x3_bias / _pooled (scl_wrw3x3_ex, scl_wrw3x3, scl_wrw64): each fills a
 // WrwCall; wrw3x3_run checks it and cuts the work with ONE WrwPlan (wrw_plan; the workspace: wrw_space).
-//   wrw64_kernel<TWv, NKB, PL> [64 c] x [64 NKB k] blocks over pixel splits -> slabs (+ bias partials);
-//                              tile width, blocks and pooled form chosen once: for_wrw_shape, wrw_launch
+//   wrw64_kernel<TWv, NKB, PL, SCHED> [64 c] x [64 NKB k] blocks over pixel splits -> slabs (+ bias
+//                              partials); tile width, blocks, pooled form and schedule (whole tiles; half
+//                              tiles with waves 4-7 half a tile behind: diagnostic library only, wrw_sched)
+//                              chosen once: for_wrw_shape, wrw_launch
 //   wrw64_reduce_kernel<RG>    slabs -> gw at its strides (+ grad_bias): wrw_reduce
 // First layer — scl_conv_first: conv_first_kernel (mean subtraction, cast, conv1_1, bias, ReLU).
 // scl_conv_first_pool_idx: conv3x3_pack_kernel, conv12_kernel (conv1_1 and conv1_2 with the pooling
@@ -684,16 +686,25 @@ constexpr int GPLANE = TH * TW * WPL;                // one 32-channel plane of 
 // 2: [64 c] x [128 k], waves = 2 x 4 blocks over a whole 128-pixel tile — the x window is
 // fetched once for twice the output channels: 24 % fewer bytes per FLOP, which is what the
 // kernel is bound by once the staging is DMA: 76 KB per 72 MFMAs of every wave).
-template <int TWv, int NKB>
+// SCHED (the schedule, see wrw64_kernel): 0 = whole tiles in two buffers, the eight waves in step;
+// 1 (NKB = 2) = HALF tiles — the left / right 16 columns of a wide tile, the upper / lower 8 rows
+// of a tall one: steps 0-3 and 4-7 of a wave — in a ring of four slots, waves 4-7 one half behind
+// waves 0-3.  The staged unit (SW x SH pixels, its halo window WCv x WRv) is the tile or the half.
+template <int TWv, int NKB, int SCHED = 0>
 struct WrwCfg {
+  static_assert(SCHED == 0 || NKB == 2, "the half-tile schedule is built for [64 c] x [128 k] blocks");
   static constexpr int PIXELS = 256 / NKB;
-  static constexpr int THv = PIXELS / TWv, WCv = TWv + 2, WRv = THv + 2;
+  static constexpr int THv = PIXELS / TWv;             // the tile's height
+  static constexpr int SW = SCHED && TWv == 32 ? TWv / 2 : TWv, SH = SCHED && TWv != 32 ? THv / 2 : THv;
+  static constexpr int NSTEP = SCHED ? 4 : 8;          // steps of 16 pixels per wave and unit
+  static constexpr int WCv = SW + 2, WRv = SH + 2;
   static constexpr int XCHv = (WRv * WCv + 15) / 16;   // 1-KB chunks per x plane
-  static constexpr int GCHv = PIXELS / 16;             // per gz plane
+  static constexpr int GCHv = SW * SH / 16;            // per gz plane
   static constexpr int XPL = XCHv * 16 * WPL, GPL = GCHv * 16 * WPL;
   static constexpr int BUF = 2 * XPL + 2 * NKB * GPL;  // one staged (x window, gz tile) pair
   static constexpr int CHUNKS = 2 * XCHv + 2 * NKB * GCHv;
-  static constexpr size_t LDS = 2 * (size_t)BUF * sizeof(unsigned short);
+  static constexpr int NBUF = SCHED ? 4 : 2;
+  static constexpr size_t LDS = NBUF * (size_t)BUF * sizeof(unsigned short);
 };
 
 // TWv: tile width, 32 (8 x 32 tiles, a step = 16 pixels of a row) or 8 (32 x 8 tiles for
@@ -709,7 +720,7 @@ struct WrwCfg {
 // pieces exactly), and writes the four 16-byte pixels of the window at the tile's end.  The gz
 // part of the stream shrinks from 2 to 0.75 bytes per element; H and W are even (host check),
 // so a window is inside or outside the image as a whole.
-template <int DBG, int TWv, int NKB, int PL = 0>
+template <int DBG, int TWv, int NKB, int PL = 0, int SCHED = 0>
 __global__ __launch_bounds__(512, 1) void wrw64_kernel(const unsigned short* __restrict__ x,
                                                        const unsigned short* __restrict__ gz,
                                                        int B, int H, int W, int C, int K,
@@ -719,7 +730,8 @@ __global__ __launch_bounds__(512, 1) void wrw64_kernel(const unsigned short* __r
   extern __shared__ __attribute__((aligned(16))) unsigned short lds[];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int r = lane & 31, h = lane >> 5;
-  using Cfg = WrwCfg<TWv, NKB>;
+  using Cfg = WrwCfg<TWv, NKB, SCHED>;
+  static_assert(SCHED == 0 || (DBG & ~4) == 0, "the half-tile schedule carries the stamps only");
   // Workgroup -> (pixel split p, input block cb, output block kz).  The 1-D grid is dealt to the
   // eight XCDs round robin (workgroup L runs on XCD L % 8) and every workgroup is resident at
   // once.  The n_cb * n_kz workgroups of one p walk the same tiles at the same time — each x
@@ -748,7 +760,8 @@ __global__ __launch_bounds__(512, 1) void wrw64_kernel(const unsigned short* __r
   // transposed-read role of this lane: 16-lane group gq = lane >> 4 covers channels
   // 16 (gq & 1) .. + 15 and pixels 8 (gq >> 1) + q (+ 4); lane 4q + p addresses row q,
   // columns 4p .. 4p + 3
-  constexpr int THv = Cfg::THv, WCv = Cfg::WCv, WRv = Cfg::WRv;
+  // SW x SH: the staged unit — the tile, or (SCHED 1) a half of it — and its window WCv x WRv
+  constexpr int THv = Cfg::THv, SW = Cfg::SW, SH = Cfg::SH, WCv = Cfg::WCv, WRv = Cfg::WRv;
   const int q = (lane >> 2) & 3, pp = lane & 3, gq = lane >> 4;
   const int ch0 = 16 * (gq & 1) + 4 * pp;
   // the lane's pixel inside a step: (row, column) relative to the step's first pixel
@@ -765,7 +778,10 @@ __global__ __launch_bounds__(512, 1) void wrw64_kernel(const unsigned short* __r
   // bytes to the same place as the wave that owns it): stage_chunk has no branches, it sits
   // between the products of the unrolled tile loop.
   constexpr int NCH = PL ? 2 * XCH : WCHUNKS;
-  constexpr int NI = (NCH + 7) / 8;
+  // (SCHED 1: a wave stages in steps 0-3 of its own tile only — the four waves 0-3 a whole even
+  // half, waves 4-7 a whole odd one — so of a SIMD's two waves one is issuing DMA and one is not)
+  constexpr int NSW = SCHED ? 4 : 8;
+  constexpr int NI = (NCH + NSW - 1) / NSW;
   const int wid_s = __builtin_amdgcn_readfirstlane(wid);
   const int pl = lane >> 2, piece = lane & 3;
   int rel[NI], roff[NI];      // roff: element offset from the tile's first (halo) pixel
@@ -773,7 +789,7 @@ __global__ __launch_bounds__(512, 1) void wrw64_kernel(const unsigned short* __r
   bool is_x[NI];              // (wave-uniform) x window or gz tile
 #pragma unroll
   for (int i = 0; i < NI; ++i) {
-    const int j = wid_s + 8 * i < NCH ? wid_s + 8 * i : NCH - 1;
+    const int j = wid_s % NSW + NSW * i < NCH ? wid_s % NSW + NSW * i : NCH - 1;
     is_x[i] = j < 2 * XCH;
     if (j < 2 * XCH) {
       const int plane = j >= XCH ? 1 : 0;
@@ -787,8 +803,8 @@ __global__ __launch_bounds__(512, 1) void wrw64_kernel(const unsigned short* __r
       const int jj = j - 2 * XCH;
       const int plane = jj / GCH;
       const int pix = 16 * (jj - GCH * plane) + pl;
-      rel[i] = ((pix / TWv) << 8) | (pix % TWv);
-      roff[i] = ((pix / TWv) * W + pix % TWv) * K + NKB * C64 * wg_kz + 8 * piece + 32 * plane;
+      rel[i] = ((pix / SW) << 8) | (pix % SW);
+      roff[i] = ((pix / SW) * W + pix % SW) * K + NKB * C64 * wg_kz + 8 * piece + 32 * plane;
       ldst[i] = (2 * XPLANE + plane * GPLANE + (jj - GCH * plane) * 512) * 2;
     }
   }
@@ -804,19 +820,20 @@ __global__ __launch_bounds__(512, 1) void wrw64_kernel(const unsigned short* __r
                              // (rows may not): the buffer path; 2: per-lane border tests
     int b, xi, gi;           // image; the same offsets relative to the image's first element
   };
-  auto tile_pos = [&](int tile) {
+  // (hf: SCHED 1, the half of the tile)
+  auto tile_pos = [&](int tile, int hf = 0) {
     const int b = tile / per_img, t2 = tile % per_img;
     TilePos t;
-    t.ty = (t2 / tiles_x) * THv;
-    t.tx = (t2 % tiles_x) * TWv;
+    t.ty = (t2 / tiles_x) * THv + (TWv == 32 ? 0 : SH * hf);
+    t.tx = (t2 % tiles_x) * TWv + (TWv == 32 ? SW * hf : 0);
     // (< 2^31: host check; the window's may be negative at the image border — those lanes are
     // masked by `ok`)
     t.xo = ((b * H + t.ty - 1) * W + t.tx - 1) * C;
     t.go = ((b * H + t.ty) * W + t.tx) * K;
-    const bool colin = t.tx >= 1 && t.tx + TWv < W;
+    const bool colin = t.tx >= 1 && t.tx + SW < W;
     // (one scalar: as two bools hipcc rebuilt them as lane masks at every chunk)
     t.mode = __builtin_amdgcn_readfirstlane(
-        colin && t.ty >= 1 && t.ty + THv < H ? 0 : (colin && kWrwBufPath && !(DBG & 8) ? 1 : 2));
+        colin && t.ty >= 1 && t.ty + SH < H ? 0 : (colin && kWrwBufPath && !(DBG & 8) ? 1 : 2));
     t.b = b;
     t.xi = ((t.ty - 1) * W + t.tx - 1) * C;      // (negative in the first tile row)
     t.gi = (t.ty * W + t.tx) * K;
@@ -842,21 +859,24 @@ __global__ __launch_bounds__(512, 1) void wrw64_kernel(const unsigned short* __r
       glds16(ok ? src : zeros, dst);
     }
   };
-  auto stage_issue = [&](int tile, int buf) __attribute__((always_inline)) {
-    const TilePos tp = tile_pos(tile);
+  auto stage_issue = [&](int tile, int buf, int hf = 0) __attribute__((always_inline)) {
+    const TilePos tp = tile_pos(tile, hf);
 #pragma unroll
     for (int i = 0; i < NI; ++i) stage_chunk(tp, buf, i);
   };
-  // PL: this thread's window of the tile = pooled pixel (pr, pc), 8 channels (plane, piece)
-  constexpr int NPC = TWv / 2, NPR = THv / 2;
-  const int p_piece = threadIdx.x & 3, p_pc = (threadIdx.x >> 2) % NPC;
-  const int p_pr = ((threadIdx.x >> 2) / NPC) % NPR, p_plane = (threadIdx.x >> 2) / (NPC * NPR);
+  // PL: this thread's window of the unit = pooled pixel (pr, pc), 8 channels (plane, piece).  SCHED 1:
+  // a half has 256 of them — waves 0-3 build the even halves, waves 4-7 the odd ones.
+  constexpr int NPC = SW / 2, NPR = SH / 2;
+  const int p_tid = (SCHED ? threadIdx.x & 255 : threadIdx.x) >> 2;
+  const int p_piece = threadIdx.x & 3, p_pc = p_tid % NPC;
+  const int p_pr = (p_tid / NPC) % NPR, p_plane = p_tid / (NPC * NPR);
   const int Ho = H >> 1, Wo = W >> 1;
   u32x4 pg = {0u, 0u, 0u, 0u};
   uint2 pi = {0u, 0u};
-  auto pool_issue = [&](int tile) {
+  auto pool_issue = [&](int tile, int hf = 0) {
     const int b = tile / per_img, t2 = tile % per_img;
-    const int py = (t2 / tiles_x) * NPR + p_pr, px = (t2 % tiles_x) * NPC + p_pc;
+    const int py = (t2 / tiles_x) * (THv / 2) + (TWv == 32 ? 0 : NPR * hf) + p_pr;
+    const int px = (t2 % tiles_x) * (TWv / 2) + (TWv == 32 ? NPC * hf : 0) + p_pc;
     const int off = ((b * Ho + py) * Wo + px) * K + NKB * C64 * wg_kz + 32 * p_plane + 8 * p_piece;
     if (py < Ho && px < Wo) {
       pg = *reinterpret_cast<const u32x4*>(gz + off);
@@ -868,11 +888,11 @@ __global__ __launch_bounds__(512, 1) void wrw64_kernel(const unsigned short* __r
   };
   auto pool_write = [&](int buf) {
     unsigned short* dst = lds + buf * WBUF + 2 * XPLANE + p_plane * GPLANE +
-                          (2 * p_pr * TWv + 2 * p_pc) * WPL + 8 * p_piece;
+                          (2 * p_pr * SW + 2 * p_pc) * WPL + 8 * p_piece;
     const UnpoolFlags fl = unpool_flags(pi.x, pi.y);
 #pragma unroll
     for (int pos = 0; pos < 4; ++pos)
-      *reinterpret_cast<u32x4*>(dst + ((pos >> 1) * TWv + (pos & 1)) * WPL) = unpool8(pg, fl, pos);
+      *reinterpret_cast<u32x4*>(dst + ((pos >> 1) * SW + (pos & 1)) * WPL) = unpool8(pg, fl, pos);
   };
 
   f32x16 acc[9];
@@ -895,32 +915,48 @@ __global__ __launch_bounds__(512, 1) void wrw64_kernel(const unsigned short* __r
   // stamps of its first four tiles to bslabs (no bias partials then): [workgroup][tile][8] —
   // 0 tile start, 1 staging issued, 2 first step done, 3 fourth step done, 4 last product
   // issued, 5 own DMA landed, 6 barrier passed.
-  uint64_t stamp[7];
-#define WRW_STAMP(k)                                                   \
-  if (DBG & 4) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(stamp[k])::"memory")
-  int tile = wg_p;
-  if (tile < ntiles) {
-    stage_issue(tile, 0);
-    if (PL) {
-      pool_issue(tile);
-      pool_write(0);
-    }
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  int buf = 0, tcount = 0;
-  for (; tile < ntiles; tile += n_p) {
-    WRW_STAMP(0);
-    const int next = (DBG & 2) ? ntiles : tile + n_p;
-    // (after the last tile the current one is staged again, into the buffer nobody reads: the
-    // product loop stays free of branches)
-    const TilePos stg = tile_pos(next < ntiles ? next : tile);
-    if (PL && next < ntiles) pool_issue(next);
-    WRW_STAMP(1);
+  //
+  // SCHED 1 — the two waves of a SIMD half a tile apart.  With SCHED 0 every barrier puts the eight
+  // waves back in phase: both waves of a SIMD run their DMA-laden steps 0-3 together and their clean
+  // steps 4-7 together, matrix beside matrix, and the older one then idles at the barrier while the
+  // younger one finishes alone.  Here the staged unit is a HALF tile (steps 0-3 or 4-7: disjoint
+  // pixels, the shared halo staged twice) in a ring of four slots, and interval n — the time between
+  // two barriers — runs
+  //   waves 0-3: the 36 products of half n           (slot n & 3)
+  //   waves 4-7: the 36 products of half n - 1       (slot (n - 1) & 3)
+  //   staging:   all chunks of half n + 2            (slot (n + 2) & 3: half n - 2 lived there, and
+  //              its last reader, a wave 4-7 in interval n - 1, left it before the barrier)
+  // so every wave issues exactly the products of SCHED 0, in the same order, into the same
+  // accumulators — the results are the same bit for bit — only the barrier a product runs against
+  // moves.  Half n + 2 is staged by the four waves that are in steps 0-3 of their own tile (waves
+  // 0-3 the even halves, waves 4-7 the odd ones; the pooled form builds its gz half there too): of a
+  // SIMD's two waves one issues DMA and the other does not.  A wave waits for its chunks at the end
+  // of its steps 4-7, one barrier before the first reader.  (All eight waves staging in every
+  // interval, four chunks each, was measured too: 3-14 % slower than SCHED 0 on every layer.)
+  // Waves 4-7 sit out interval 0, waves 0-3 the last one: every wave of a workgroup passes
+  // 2 * tiles + 2 barriers, however many tiles it walks.
+  //
+  // DBG & 4 (scl_debug_set_variant(2004 / 2008), diagnostics): wave 0 of every workgroup writes
+  // s_memtime stamps of its first four tiles to bslabs (no bias partials then): [workgroup][tile][8] —
+  //   SCHED 0: 0 tile start, 1 staging issued, 2 first step done, 3 fourth step done, 4 last product
+  //            issued, 5 own DMA landed, 6 barrier passed;
+  //   SCHED 1: 0 tile start, 1 first step done, 2 fourth step done, 3 own DMA landed, 4 mid-tile
+  //            barrier passed, 5 last product issued, 6 own DMA landed, 7 barrier passed — and wave 4
+  //            writes the same record of ITS tiles behind the slabs in use (the workspace holds two
+  //            slabs per workgroup, [64 c] x [128 k] blocks write one).
+  uint64_t stamp[8];
+#define WRW_STAMP(k)                                                     \
+  do {                                                                   \
+    if (DBG & 4) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(stamp[k])::"memory"); \
+  } while (0)
+  // The NSTEP * 9 products of one staged unit out of buffer `buf`, the wave's chunks of unit `stg`
+  // on their way into buffer `sbuf` in between.
+  auto products = [&](auto stage_, int buf, const TilePos& stg, int sbuf, auto&& stamp_at) __attribute__((always_inline)) {
+    constexpr bool STAGE = decltype(stage_)::value;
     const unsigned short* xl =
         lds + buf * WBUF + mt * XPLANE + (lrow * WCv + lcol) * WPL + ch0;
     const unsigned short* gl =
-        lds + buf * WBUF + 2 * XPLANE + nt * GPLANE + (lrow * TWv + lcol) * WPL + ch0;
+        lds + buf * WBUF + 2 * XPLANE + nt * GPLANE + (lrow * SW + lcol) * WPL + ch0;
     // product i = 9 * s + t: step s of this wave's eight (first pixel (ry, cx)), tap t = 3 kh + kw.
     // A lane's A operand is 8 consecutive pixels of a window row for its channel; the three kw
     // taps of a row are the same pixels shifted by 0 / 1 / 2 — three fragments of 8 pixels (two
@@ -936,10 +972,12 @@ __global__ __launch_bounds__(512, 1) void wrw64_kernel(const unsigned short* __r
     };
     // window row (relative to the wave's first) and column slot of step s_, tap row kh
     // Wide tiles walk the left 16 columns of the wave's four rows, then the right ones (steps
-    // 0-3, 4-7): three window rows of ONE column half are live at a time.
-    constexpr int NFR = TWv == 32 ? 6 : 18, NFC = TWv == 32 ? 2 : 1;
+    // 0-3, 4-7): three window rows of ONE column half are live at a time.  (SCHED 1: the unit IS one
+    // half — four steps, one column slot.)
+    constexpr int NS = Cfg::NSTEP;
+    constexpr int NFR = TWv == 32 ? 6 : 2 * NS + 2, NFC = TWv == 32 && !SCHED ? 2 : 1;
     auto f_row = [](int s_, int kh) { return TWv == 32 ? (s_ & 3) + kh : 2 * s_ + kh; };
-    auto f_col = [](int s_) { return TWv == 32 ? (s_ >> 2) : 0; };
+    auto f_col = [](int s_) { return TWv == 32 && !SCHED ? (s_ >> 2) : 0; };
     // is (s_, kh) the first product that touches its fragment?
     auto f_first = [](int s_, int kh) { return TWv == 32 ? ((s_ & 3) == 0 || kh == 2) : (s_ == 0 || kh >= 1); };
     const int row_w = TWv == 32 ? 4 * ph : 16 * ph;        // the wave's first window row
@@ -950,22 +988,23 @@ __global__ __launch_bounds__(512, 1) void wrw64_kernel(const unsigned short* __r
     };
     auto b_of = [&](int s_) {
       const int ry = TWv == 32 ? 4 * ph + (s_ & 3) : 16 * ph + 2 * s_;
-      return tr_pair(gl + (ry * TWv + 16 * f_col(s_)) * WPL, 4 * WPL);
+      return tr_pair(gl + (ry * SW + 16 * f_col(s_)) * WPL, 4 * WPL);
     };
     constexpr int LEAD = 6;                                // products between a read and its first use
-    constexpr int STG = 5;                                 // products between two staging chunks
-    static_assert(STG * NI <= 9 * 8 - 12, "the last chunk needs time to land");
+    constexpr int STG = SCHED ? 4 : 5;                     // products between two staging chunks
+    // (SCHED 1 waits for its chunks one interval later)
+    static_assert(STG * NI <= 9 * NS - (SCHED ? 0 : 12), "the last chunk needs time to land");
     u32x4 bf[2];
 #pragma unroll
     for (int i = 0; i < LEAD; ++i)
       if (f_first(i / 9, (i % 9) / 3)) f_load(i);
     bf[0] = b_of(0);
 #pragma unroll
-    for (int i = 0; i < 9 * 8; ++i) {
+    for (int i = 0; i < 9 * NS; ++i) {
       const int s_ = i / 9, kh = (i % 9) / 3, kw = i % 3;
-      if (i + LEAD < 9 * 8 && f_first((i + LEAD) / 9, ((i + LEAD) % 9) / 3)) f_load(i + LEAD);
-      if (i % 9 == 2 && s_ + 1 < 8) bf[(s_ + 1) & 1] = b_of(s_ + 1);
-      if (!(DBG & 2) && i % STG == 0 && i / STG < NI) stage_chunk(stg, buf ^ 1, i / STG);
+      if (i + LEAD < 9 * NS && f_first((i + LEAD) / 9, ((i + LEAD) % 9) / 3)) f_load(i + LEAD);
+      if (i % 9 == 2 && s_ + 1 < NS) bf[(s_ + 1) & 1] = b_of(s_ + 1);
+      if (STAGE && !(DBG & 2) && i % STG == 0 && i / STG < NI) stage_chunk(stg, sbuf, i / STG);
       __builtin_amdgcn_sched_barrier(0);
       const u32x4 a = fr[f_row(s_, kh)][f_col(s_)][kw];
       if constexpr ((DBG & 16) != 0) {
@@ -982,9 +1021,7 @@ __global__ __launch_bounds__(512, 1) void wrw64_kernel(const unsigned short* __r
       } else {
         acc[i % 9] = mfma32b(a, bf[s_ & 1], acc[i % 9]);
       }
-      if (i == 8) WRW_STAMP(2);
-      if (i == 35) WRW_STAMP(3);
-      if (i == 71) WRW_STAMP(4);
+      stamp_at(i);
       if (i % 9 == 4 && bias_wave) {
         const u32x4 bw = bf[s_ & 1];
         const bf16x2 one2 = __builtin_bit_cast(bf16x2, 0x3f803f80u);
@@ -996,21 +1033,97 @@ __global__ __launch_bounds__(512, 1) void wrw64_kernel(const unsigned short* __r
         bsum = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, w3), one2, bsum, false);
       }
     }
-    if (PL && next < ntiles) pool_write(buf ^ 1);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this wave's DMA chunks have landed
-    WRW_STAMP(5);
-    __syncthreads();
-    WRW_STAMP(6);
-    if (DBG & 4) {
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      if (threadIdx.x == 0 && tcount < 4) {
-        uint64_t* o = reinterpret_cast<uint64_t*>(bslabs) + ((int64_t)((int)blockIdx.x) * 4 + tcount) * 8;
+  };
+  // the stamps of wave `wv`'s tile number tcount (of its first four) go to `o`
+  auto stamps_out = [&](uint64_t* o, int wv, int tcount) {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    if (threadIdx.x == 64 * wv && tcount < 4) {
+      o += ((int64_t)((int)blockIdx.x) * 4 + tcount) * 8;
 #pragma unroll
-        for (int k = 0; k < 7; ++k) o[k] = stamp[k];
-      }
-      ++tcount;
+      for (int k = 0; k < (SCHED ? 8 : 7); ++k) o[k] = stamp[k];
     }
-    buf ^= 1;
+  };
+
+  if constexpr (SCHED == 0) {
+    int tile = wg_p;
+    if (tile < ntiles) {
+      stage_issue(tile, 0);
+      if (PL) {
+        pool_issue(tile);
+        pool_write(0);
+      }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    int buf = 0, tcount = 0;
+    for (; tile < ntiles; tile += n_p) {
+      WRW_STAMP(0);
+      const int next = (DBG & 2) ? ntiles : tile + n_p;
+      // (after the last tile the current one is staged again, into the buffer nobody reads: the
+      // product loop stays free of branches)
+      const TilePos stg = tile_pos(next < ntiles ? next : tile);
+      if (PL && next < ntiles) pool_issue(next);
+      WRW_STAMP(1);
+      products(std::true_type{}, buf, stg, buf ^ 1, [&](int i) {
+        if (i == 8) WRW_STAMP(2);
+        if (i == 35) WRW_STAMP(3);
+        if (i == 71) WRW_STAMP(4);
+      });
+      if (PL && next < ntiles) pool_write(buf ^ 1);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this wave's DMA chunks have landed
+      WRW_STAMP(5);
+      __syncthreads();
+      WRW_STAMP(6);
+      if (DBG & 4) stamps_out(reinterpret_cast<uint64_t*>(bslabs), 0, tcount++);
+      buf ^= 1;
+    }
+  } else {
+    // (wave-uniform, scalar: the barriers below sit behind branches on it)
+    const int lag = wid_s >> 2;
+    const int nh = wg_p < ntiles ? 2 * ((ntiles - wg_p + n_p - 1) / n_p) : 0;   // this workgroup's halves
+    auto tile_of = [&](int g) { return wg_p + (g >> 1) * n_p; };
+    if (nh > 0) {
+      stage_issue(tile_of(0), 0, 0);
+      stage_issue(tile_of(1), 1, 1);
+      if (PL) {
+        pool_issue(tile_of(lag), lag);
+        pool_write(lag);
+      }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (lag) __syncthreads();                               // interval 0 of waves 4-7
+    for (int g = 0; g < nh; g += 2) {                       // the wave's halves g, g + 1 in intervals g + lag ..
+      WRW_STAMP(0);
+      const int hs = g + 2 + lag;
+      // (past the last half the current one is staged again, into the slot nobody reads: the product
+      // loop stays free of branches)
+      const TilePos stg = hs < nh ? tile_pos(tile_of(hs), hs & 1) : tile_pos(tile_of(g), 0);
+      const bool pool_now = PL && hs < nh;
+      if (pool_now) pool_issue(tile_of(hs), hs & 1);
+      products(std::true_type{}, g & 3, stg, hs & 3, [&](int i) {
+        if (i == 8) WRW_STAMP(1);
+        if (i == 35) WRW_STAMP(2);
+      });
+      if (pool_now) pool_write(hs & 3);
+      WRW_STAMP(3);
+      __syncthreads();
+      WRW_STAMP(4);
+      products(std::false_type{}, (g + 1) & 3, stg, 0, [&](int i) {
+        if (i == 35) WRW_STAMP(5);
+      });
+      // the chunks of half hs have landed: its first reader passes the barrier after this one
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      WRW_STAMP(6);
+      __syncthreads();
+      WRW_STAMP(7);
+      if (DBG & 4) {
+        // (wave 4: behind the gridDim.x slabs of [2][9][64][64] floats that this launch writes)
+        uint64_t* lag_o = reinterpret_cast<uint64_t*>(slabs + (int64_t)gridDim.x * 2 * 9 * C64 * C64);
+        stamps_out(lag ? lag_o : reinterpret_cast<uint64_t*>(bslabs), 4 * lag, g >> 1);
+      }
+    }
+    if (!lag) __syncthreads();                              // the last interval of waves 0-3
   }
 #undef WRW_STAMP
 
@@ -2018,21 +2131,30 @@ static WrwPlan wrw_plan(const WrwCall& c, int nkb, bool may_be_tall = true) {
   return p;
 }
 
-template <int DBG, int TWv, int NKB, int PL>
+template <int DBG, int TWv, int NKB, int PL, int SCHED = 0>
 void wrw_launch(const WrwPlan& p, const WrwCall& c) {
-  scl_lds_limit<&wrw64_kernel<DBG, TWv, NKB, PL>>((int)WrwCfg<TWv, NKB>::LDS);
-  SCL_LAUNCH(PL ? "wrw64_kernel<pooled>" : "wrw64_kernel", (wrw64_kernel<DBG, TWv, NKB, PL>),
-             dim3(p.splits * (c.cin / 64) * (c.kout / (64 * NKB))), dim3(512), (WrwCfg<TWv, NKB>::LDS), c.stream,
+  using Cfg = WrwCfg<TWv, NKB, SCHED>;
+  scl_lds_limit<&wrw64_kernel<DBG, TWv, NKB, PL, SCHED>>((int)Cfg::LDS);
+  SCL_LAUNCH(PL ? "wrw64_kernel<pooled>" : "wrw64_kernel", (wrw64_kernel<DBG, TWv, NKB, PL, SCHED>),
+             dim3(p.splits * (c.cin / 64) * (c.kout / (64 * NKB))), dim3(512), (Cfg::LDS), c.stream,
              (const unsigned short*)c.x, (const unsigned short*)c.gz, c.B, c.H, c.W, c.cin, c.kout, p.slabs,
              p.bslabs, c.pidx);
 }
-// f(TWv, NKB, PL), each a std::integral_constant<int, .>: wrw64_kernel takes the tile width (32 wide,
-// 8 tall), the k blocks and the pooled form as template arguments
+// The schedule of an instantiation (WrwCfg).  Whole tiles everywhere: in the same-box A/B of
+// profiles/wrw_stagger the half-tile schedule gained on no instantiation (wide tiles equal within the
+// spread, tall ones 2-8 % slower), so the product library does not contain it; the diagnostic library
+// reaches it through scl_debug_set_variant(2404), and tests/test_gpu_wrw_stagger.py keeps it bit-equal.
+constexpr int wrw_sched(int twv, int nkb, int pl) { return 0; }
+// f(TWv, NKB, PL, SCHED), each a std::integral_constant<int, .>: wrw64_kernel takes the tile width (32
+// wide, 8 tall), the k blocks, the pooled form and the schedule as template arguments
 template <class F>
 void for_wrw_shape(const WrwPlan& p, bool pooled, F&& f) {
   using std::integral_constant;
+  auto sched = [&](auto t, auto n, auto pl) {
+    f(t, n, pl, integral_constant<int, wrw_sched(decltype(t)::value, decltype(n)::value, decltype(pl)::value)>{});
+  };
   auto tile = [&](auto n, auto pl) {
-    if (!p.tall) f(integral_constant<int, 32>{}, n, pl); else f(integral_constant<int, 8>{}, n, pl);
+    if (!p.tall) sched(integral_constant<int, 32>{}, n, pl); else sched(integral_constant<int, 8>{}, n, pl);
   };
   auto blocks = [&](auto pl) {
     if (p.nkb == 1) tile(integral_constant<int, 1>{}, pl); else tile(integral_constant<int, 2>{}, pl);
@@ -2041,8 +2163,8 @@ void for_wrw_shape(const WrwPlan& p, bool pooled, F&& f) {
 }
 // the product's kernel for the plan
 static void wrw_launch_planned(const WrwPlan& p, const WrwCall& c) {
-  for_wrw_shape(p, c.pidx != nullptr, [&](auto t, auto n, auto pl) {
-    wrw_launch<0, decltype(t)::value, decltype(n)::value, decltype(pl)::value>(p, c);
+  for_wrw_shape(p, c.pidx != nullptr, [&](auto t, auto n, auto pl, auto sc) {
+    wrw_launch<0, decltype(t)::value, decltype(n)::value, decltype(pl)::value, decltype(sc)::value>(p, c);
   });
 }
 
