@@ -1,5 +1,5 @@
 # Same-box A/B of the train step between the product library and a PREVIOUS build of it: put the other build at
-# soft_contrastive_learning_amd/libscl_hip_prev.so (e.g. `git show HEAD~1:...conv64.hip`, compiled with the
+# soft_contrastive_learning_amd/libscl_hip_prev.so (e.g. `git show HEAD~1:...conv_wrw.hip`, compiled with the
 # Makefile's flags and linked with the current objects), then `gpurun -- 'bash scripts/lib_ab.sh'`.
 cd $GRAFT_REPO_ROOT
 P=soft_contrastive_learning_amd

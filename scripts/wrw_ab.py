@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Same-box, same-process A/B of wrw64_kernel variants on the weight-gradient launches of the bench
+"""Same-box, same-process A/B of wrw64_kernel variants (csrc/conv_wrw.hip, conv_wrw_diag.hip) on the weight-gradient launches of the bench
 step (24 x 640x480: conv1_2 .. conv5_3 at their resolutions, post-ReLU-like operands — about half
 of x exactly zero, the incoming gradient masked the same way), alternating between the product
 kernels (variant 0) and diagnostic variants, e.g. 2200 = round 4's staging without the buffer path.

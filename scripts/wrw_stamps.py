@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Where the cycles of a wrw64_kernel tile go: scl_debug_set_variant(2004) makes wave 0 of every
+"""Where the cycles of a wrw64_kernel tile (csrc/conv_wrw.hip) go: scl_debug_set_variant(2004) makes wave 0 of every
 workgroup write s_memtime stamps (100 MHz-independent shader clock counts) of its first four tiles.
 --halves takes the half-tile schedule (variant 2008): two barriers per tile, and wave 4 — the wave
 that shares wave 0's SIMD and runs half a tile behind it — writes the stamps of its tiles as well.

@@ -261,8 +261,8 @@ extern SclProfSink* volatile scl_prof_sink;
 // and every `dbg` test inside a kernel folds away, and scl_debug_set_variant rejects anything
 // but 0 — the shipped library has no process-wide switch that changes a result.  Kernels and
 // launch structures that only a variant reaches live in netvlad_diag.hip, gram_loss_diag.hip,
-// conv64_diag.hip and convh_diag.hip, which the diagnostic build compiles in place of their
-// product sources; what stays here are hooks that fold to 0 and one-line knobs between kernels
+// conv64_diag.hip, conv_wrw_diag.hip and convh_diag.hip, which the diagnostic build compiles in place
+// of their product sources; what stays here are hooks that fold to 0 and one-line knobs between kernels
 // the product launches.
 #ifdef SCL_DIAG
 extern volatile int scl_debug_variant;
@@ -307,8 +307,8 @@ static inline int scl_device_cus() {
 }
 
 // CUs the persistent convolution grids may fill: the device's, minus the reserve AS IT IS NOW (it may
-// change between calls: bench.py tries 0 and 8 at N > 1), at most the kSclMaxConvCus the wrw workspaces
-// are sized for.
+// change between calls: bench.py tries 0 and 8 at N > 1), at most the kSclMaxConvCus the weight-gradient
+// workspaces are sized for (conv_wrw.hip: wrw_space; the first layer's in conv64.hip: kFw*).
 constexpr int kSclMaxConvCus = 1024;
 static inline int scl_conv_cus() {
   const int u = scl_usable_cus(scl_device_cus());

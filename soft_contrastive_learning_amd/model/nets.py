@@ -3,7 +3,7 @@
 ``vgg16Netvlad(image_batch)`` and ``vgg16(image_batch)`` keep the reference names and
 the NHWC / raw-0..255-RGB input convention (model/nets.py:7-69, :72-131).  In bf16 mode every
 VGG16 convolution pass (forward, backward-data, weight gradient, every layer) runs on the
-hand-written implicit-GEMM kernels of csrc/conv64.hip and csrc/conv_lds.hip (convh.hip, convg.hip; bias /
+hand-written implicit-GEMM kernels of csrc/conv64.hip, csrc/conv_wrw.hip and csrc/conv_lds.hip (convh.hip, convg.hip; bias /
 ReLU / max-pool / ReLU' fused into their epilogues, float32 master weights read directly,
 weight gradients written straight into the flat gradient buffer); only the float32 mode and
 maps below 30x40 use the library (MIOpen / CK) with the fused glue passes of
@@ -838,7 +838,7 @@ def _bwd_route(x, g, w, need_x, link=None, pooled=False):
     channels and dtype are what is looked at); ``link``: x is a post-ReLU map whose producer holds
     the other end; ``pooled``: the gradient at the pooled map, already masked, and the window
     positions are at hand.  Which consumers of a pooled gradient can un-pool while they stage —
-    weight gradient: every own shape (csrc/conv64.hip, wrw64_kernel<.., 1>); backward-data: the
+    weight gradient: every own shape (csrc/conv_wrw.hip, wrw64_kernel<.., 1>); backward-data: the
     register kernels with cin == kout — conv1_2 and conv2_2 — in their masked form; conv3_3 /
     conv4_3 fill their windows by LDS-DMA, which copies bytes as they lie."""
     kind = _own_conv_kind(g, w, True)

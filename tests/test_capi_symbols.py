@@ -211,8 +211,8 @@ def test_lds_convolution_entry_points_validate_on_the_host(lib):
 
 def test_register_convolution_entry_points_validate_on_the_host(lib):
     """The register-weights family of csrc/conv64.hip — scl_conv3x3_fused / _pool_idx / _masked /
-    _masked_pooled (and the legacy scl_conv3x3, scl_conv64), the weight gradient scl_wrw3x3_bias /
-    _pooled (and scl_wrw3x3_ex, scl_wrw3x3, scl_wrw64), and the first-layer entry points: every
+    _masked_pooled (and the legacy scl_conv3x3, scl_conv64) — the weight gradient of csrc/conv_wrw.hip —
+    scl_wrw3x3_bias / _pooled (and scl_wrw3x3_ex, scl_wrw3x3, scl_wrw64) — and the first-layer entry points: every
     refusal comes back before any launch, each asserted with a condition that a LATER check refuses
     also present, so the order of precedence is pinned.  (Three of the convolution's checks — an
     index map with a mask, a mask with a bias, an un-pooling index without a mask — guard combinations

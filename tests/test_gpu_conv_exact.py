@@ -1,5 +1,5 @@
-"""Bit-exact checks of the own backbone kernels (csrc/conv64.hip, conv_lds.hip with convh.hip and
-convg.hip, conv_pack.hip, vgg_glue.hip) on integer-valued data.
+"""Bit-exact checks of the own backbone kernels (csrc/conv64.hip, conv_wrw.hip, conv_lds.hip with
+convh.hip and convg.hip, conv_pack.hip, vgg_glue.hip) on integer-valued data.
 
 With small-integer bf16 operands every product is exact and, while every partial sum is an integer
 below 2^24 (``exact_conv.premise``, asserted first in every test), the float32 accumulation is

@@ -1,4 +1,4 @@
-"""The workspaces of the register-weights convolution family (csrc/conv64.hip), between guard bands.
+"""The workspaces of the register-weights convolution family (csrc/conv64.hip, conv_wrw.hip), between guard bands.
 
 Every workspace-taking entry point gets EXACTLY the bytes its size query returns, inside a larger
 buffer whose 4096 bytes on either side must come back untouched (tests/util_guard.py), and every

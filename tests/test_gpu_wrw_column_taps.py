@@ -1,4 +1,4 @@
-"""Weight-gradient kernel (csrc/conv64.hip, wrw64_kernel): the column taps as shifted LDS reads.
+"""Weight-gradient kernel (csrc/conv_wrw.hip, wrw64_kernel): the column taps as shifted LDS reads.
 
 The kernel reads the x fragment of a window row three times, at pixel offsets 0 / 1 / 2 of the halo
 window, one read per column tap, against the unshifted gradient fragment of the step.  What can go
@@ -39,7 +39,7 @@ def dev():
 
 
 def _tall(shape, kout):
-    """The tile shape csrc/conv64.hip's wrw_plan takes."""
+    """The tile shape csrc/conv_wrw.hip's wrw_plan takes."""
     b, h, w = shape
     th_w, th_t = (4, 16) if kout % 128 == 0 else (8, 32)
     return b * -(-h // th_t) * -(-w // 8) < b * -(-h // th_w) * -(-w // 32)

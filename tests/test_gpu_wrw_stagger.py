@@ -1,4 +1,4 @@
-"""Weight-gradient kernel (csrc/conv64.hip, wrw64_kernel): the half-tile schedule (SCHED 1).
+"""Weight-gradient kernel (csrc/conv_wrw.hip, wrw64_kernel): the half-tile schedule (SCHED 1).
 
 On [64 c] x [128 k] blocks the kernel can stage HALF tiles into a ring of four LDS slots, with waves
 4-7 running one half behind waves 0-3.  Every wave issues the products of the whole-tile schedule in
@@ -13,7 +13,7 @@ last reader left, read before it landed, a half staged from the wrong place (the
 tile are column halves, of a tall one row halves; either may lie outside the image), a barrier
 missed by a wave that walks fewer tiles, the pooled gradient built by the wrong wave half.
 
-Shapes, with the plan csrc/conv64.hip's wrw_plan makes of them on 256 compute units (``_plan``
+Shapes, with the plan csrc/conv_wrw.hip's wrw_plan makes of them on 256 compute units (``_plan``
 restates it, and the test of the list checks it where the suite runs): every one of the four
 instantiations walks at least three tiles per workgroup — each of the four slots is reused — with
 workgroups of one launch walking unequal numbers of tiles.

@@ -182,3 +182,44 @@ def test_profiling_sink_names_are_the_kernel_names():
     assert len(head) >= 20, head
     missing = [n for n in head if n not in models]
     assert not missing, missing
+
+
+def test_kernel_code_diff_masks_only_the_pc_relative_literal():
+    """scripts/kernel_code_diff.py --pcrel: the literal that `s_add_u32 sA, sA, <literal>` adds to the
+    program counter `s_getpc_b64 s[A:A+1]` has just read (and the carry operand of the s_addc_u32 behind
+    it) compares as equal, because moving a kernel in its module changes it and no instruction.  A
+    literal on any other s_add_u32, and a REGISTER on the masked line, differ with the option as without."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location('kernel_code_diff',
+                                                  os.path.join(ROOT, 'scripts', 'kernel_code_diff.py'))
+    D = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(D)
+
+    def code(getpc='s[6:7]', add='s6, s6, 0x78ef0', carry='s7, s7, 0', other='s2, s2, 0x1200'):
+        txt = ('\nDisassembly of section .text:\n\n<_Z1kv>:\n'
+               '\ts_load_dwordx2 s[0:1], s[4:5], 0x0\n'
+               '\ts_getpc_b64 %s\n\ts_add_u32 %s\n\ts_addc_u32 %s\n'
+               '\tv_mov_b64_e32 v[2:3], s[6:7]\n\ts_add_u32 %s\n\ts_endpgm\n' % (getpc, add, carry, other))
+        syms, order = D.symbols(txt)
+        assert order == ['_Z1kv'] and len(syms['_Z1kv']) == 7
+        return ({'_Z1kv': (32, 0, 16, 0, 0, 28)}, syms, order)
+
+    def differs(a, b, pcrel):
+        return D.compare(a, b, pcrel=pcrel)[0] == ['_Z1kv']
+
+    base = code()
+    assert not differs(base, code(), False) and not differs(base, code(), True)
+    moved = code(add='s6, s6, 0x1c4', carry='s7, s7, -1')        # the same kernel elsewhere in the module
+    assert differs(base, moved, False) and not differs(base, moved, True)
+    assert D.compare(base, moved, pcrel=True)[2] == {'_Z1kv': 2}  # two lines masked, and counted
+    elsewhere = code(other='s2, s2, 0x1204')                     # a literal that is no PC offset
+    assert differs(base, elsewhere, False) and differs(base, elsewhere, True)
+    register = code(add='s8, s8, 0x78ef0')                       # another register on the masked line
+    assert differs(base, register, False) and differs(base, register, True)
+    pair = code(getpc='s[8:9]', add='s8, s8, 0x1c4', carry='s9, s9, 0')   # ... consistently: still a difference
+    assert differs(base, pair, True)
+    # a second object with a subset of the first one's symbols: the rest is listed, not compared
+    two = ({**base[0], '_Z1mv': base[0]['_Z1kv']}, {**base[1], '_Z1mv': base[1]['_Z1kv']}, ['_Z1kv', '_Z1mv'])
+    assert D.compare(two, base)[0] == ['_Z1mv']
+    assert D.compare(two, base, subset=True)[:2] == ([], ['_Z1mv'])
+    assert D.compare(base, two, subset=True)[0] == ['_Z1mv']     # a symbol only the second has is new
