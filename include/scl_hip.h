@@ -872,6 +872,52 @@ int scl_frames_resize(const void* src, int n, int sh, int sw, int c, const int* 
                       const int* ytab, int oh, int out_kind, void* out, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Raw Bayer frames (csrc/frames.hip; util/robotcar.py load_image_np, util/device_cv.py
+ * DeviceResizer.debayer): the RobotCar SDK's load_image — bilinear demosaic, look-up-table
+ * undistortion, astype(uint8) — as util/robotcar.py states it (pinned against the scipy functions
+ * the SDK calls; the SDK itself was not available), optionally fused with scl_frames_resize.
+ *
+ *   raw     uint8 [n, sh, sw], dense, any byte address: one-channel Bayer mosaics
+ *   pattern SCL_BAYER_*: the colours of the sites (0,0), (0,1), (1,0), (1,1) of every 2 x 2 cell
+ *   border  what a tap outside the frame reads: SCL_BAYER_REFLECT index -1 -> 0, n -> n-1 (scipy's
+ *           default mode='reflect'), SCL_BAYER_MIRROR -1 -> 1, n -> n-2
+ *   lut     float64 [2][sh*sw] ON THE DEVICE, as <camera>_distortion_lut.bin holds it: the column
+ *           coordinate of every pixel, then the row coordinate; NULL: demosaic only
+ *   xtab, ytab  the tables of scl_frames_resize for a source of sh x sw, or both NULL: full size
+ *           (ow and oh are then not read)
+ *   out     [n, sh, sw, 3], or [n, oh, ow, 3] with tables; uint8 or the float32 of that byte
+ * Per pixel and channel c (R, G, B):
+ *   q   = sum over the 3 x 3 taps of K_c * (raw where the site READ has colour c, else 0), integers,
+ *         K_G = [[0,1,0],[1,4,1],[0,1,0]], K_R = K_B = [[1,2,1],[2,4,2],[1,2,1]];  v = q / 4 (float64)
+ *   with (lx, ly) from lut: outside 0 <= ly <= sh-1, 0 <= lx <= sw-1 (NaN is outside) the value is 0;
+ *   inside y0 = floor(ly), ty = ly - y0, wy0 = 1 - ty, y1 = min(y0+1, sh-1), the same for x, and
+ *   acc = 0; acc += (v[y0,x0] wy0) wx0; acc += (v[y0,x1] wy0) tx; acc += (v[y1,x0] ty) wx0;
+ *   acc += (v[y1,x1] ty) tx — float64, every operation rounded on its own, in this order;
+ *   byte = acc truncated toward zero, low 8 bits.  Under SCL_BAYER_REFLECT the doubled border taps
+ *   make values up to 573.75 on an all-255 frame, which wrap (573 -> 61); SCL_BAYER_MIRROR stays
+ *   within 0..255.
+ * With tables the result is scl_frames_resize's int32 formula (same clamping of the table indices)
+ * applied to those bytes; each output value evaluates the four undistorted pixels it reads and
+ * nothing else, and no full-size frame is written.
+ * The launcher cannot see lut or the tables: every index derived from them is clamped to the
+ * frame, so wrong contents give wrong pixels but never a read outside raw.  Frame offsets are
+ * 64-bit.  A thread walks the frames of a batch with one read of the table.
+ * Returns SCL_E_NULL for raw or out NULL, or exactly one of xtab, ytab NULL; SCL_E_SHAPE for n
+ * outside 1..65535, sh or sw outside 2..16384, (with tables) oh or ow outside 1..16384, an unknown
+ * pattern, border or out_kind, a float32 out that is not 4-byte aligned or a lut that is not 8-byte
+ * aligned; nothing is launched then.
+ * ------------------------------------------------------------------------- */
+#define SCL_BAYER_RGGB 0
+#define SCL_BAYER_BGGR 1
+#define SCL_BAYER_GRBG 2
+#define SCL_BAYER_GBRG 3
+#define SCL_BAYER_REFLECT 0
+#define SCL_BAYER_MIRROR 1
+int scl_frames_debayer(const void* raw, int n, int sh, int sw, int pattern, int border,
+                       const double* lut, const int* xtab, int ow, const int* ytab, int oh,
+                       int out_kind, void* out, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * The parameter update (csrc/optim.hip; train/optim.py HipAdam / HipMomentum): TensorFlow's
  * ApplyAdam and ApplyMomentum (non-Nesterov) for a whole LIST of float32 parameters in one launch,
  * every operation a float32 operation rounded on its own (no contraction into fused multiply-adds,

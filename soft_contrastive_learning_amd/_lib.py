@@ -39,7 +39,9 @@ EIGEN_NTUPLET_EVMM, EIGEN_NTUPLET_TRACE, EIGEN_NEG_EIGENVALUE = 3, 4, 5
 CONV_TRANSPOSED, W_F32, W_PACKED = 1, 2, 4   # flag word of the convolution entry points
 PACK_VLAD_W = 16           # SclPackJob.flags: the job writes the NetVLAD plane images of assign_w
 OPTIM_CHUNK_GROUPS = 1024  # SCL_OPTIM_CHUNK_GROUPS: 16-byte groups per workgroup of scl_apply_*
-FRAMES_U8, FRAMES_F32 = 0, 1   # out_kind of scl_frames_resize
+FRAMES_U8, FRAMES_F32 = 0, 1   # out_kind of scl_frames_resize / scl_frames_debayer
+BAYER_PATTERNS = ('rggb', 'bggr', 'grbg', 'gbrg')   # SCL_BAYER_RGGB .. SCL_BAYER_GBRG, by index
+BAYER_BORDERS = ('reflect', 'mirror')               # SCL_BAYER_REFLECT, SCL_BAYER_MIRROR
 OPTIM_SEG_WORDS = 6       # SclOptimSeg as int64 words: var, grad, slot0, slot1, n, first_chunk
 GEO_SLAB = 256             # SCL_GEO_SLAB: references per LDS slab of scl_geo_nearest; the granule of a split
 GEO_BLOCK_QUERIES = 256    # SCL_GEO_BLOCK_QUERIES: queries per workgroup of its query-per-lane route
@@ -175,6 +177,7 @@ SIGNATURES = {
     "scl_eigen_loss_fwd": (_i, [_i, _p, _p, _p, _i, _i, _i, _i, _f, _i, _p, _p, _p, _p, _z, _p]),
     "scl_frames_gather": (_i, [_p, _l, _p, _l, _p, _i, _l, _p, _p]),
     "scl_frames_resize": (_i, [_p, _i, _i, _i, _i, _p, _i, _p, _i, _i, _p, _p]),
+    "scl_frames_debayer": (_i, [_p, _i, _i, _i, _i, _i, _p, _p, _i, _p, _i, _i, _p, _p]),
     "scl_apply_adam": (_i, [_p, _i, _l, _p, _p, _f, _f, _f, _p, _p]),
     "scl_apply_momentum": (_i, [_p, _i, _l, _p, _f, _p, _p]),
     "scl_grad_stats_workspace_bytes": (_z, [_l]),

@@ -13,7 +13,10 @@ util/io.py restated in ``soft_contrastive_learning_amd/util``): 'oxs' sets read 
 longer side becomes ``large_side`` unless ``--rescale`` is off, without it the frame is brought to
 ``small_side x large_side``.  Six loader threads feed the device (:155-160).  ``--set synthetic``:
 random images, no files.  ``--device_resize 1`` leaves the sizing of the decoded frames to the device
-(util/device_cv.py, csrc/frames.hip: the same pixels, the same pickle).
+(util/device_cv.py, csrc/frames.hip: the same pixels, the same pickle).  ``--bayer PATTERN
+--distortion_lut FILE [--bayer_border reflect|mirror]`` (they need ``--device_resize 1``): the files are
+raw one-channel Bayer frames as the RobotCar cameras deliver them; the device demosaics, undistorts and
+sizes them in one launch (util/robotcar.py states what is computed; the SDK it restates was not available).
 """
 import argparse
 import os
@@ -42,7 +45,7 @@ def size_on_host(img, rule, kw):
 
 
 def extract_features(model, loader, num, images_per_pass=4, device=None, loader_threads=6,
-                     device_resize=False):
+                     device_resize=False, debayer=None):
     """Returns ``list`` of ``num`` float32 vectors (length 32768 with the NetVLAD head, H' W' 512
     without: ``ops['full_out']``, evaluation/inference.py:89-92; ``out_dim`` with a dense reduction
     head: ``ops['output']``, :97-109), in index order.  ``loader`` is
@@ -52,7 +55,11 @@ def extract_features(model, loader, num, images_per_pass=4, device=None, loader_
     (``csv_loader(device_resize=True)``) and every batch is sized on the device
     (util/device_cv.py: the host's pixels bit for bit).  A batch whose frames do not share one
     source shape is sized on the host, frame by frame, as without the flag; such batches are
-    counted and the count is printed at the end."""
+    counted and the count is printed at the end.
+
+    ``debayer`` = (pattern, lut, border) with ``device_resize``: the decoded frames are raw Bayer
+    mosaics [SH,SW] (``csv_loader(bayer=...)``) and go through ``DeviceResizer.debayer``; on the host
+    route of a mixed batch through ``robotcar.load_image_np`` (a frame the table does not fit raises)."""
     from concurrent.futures import ThreadPoolExecutor
     device = device or next(model.parameters()).device
     order = pad_indices(num, images_per_pass)
@@ -66,6 +73,9 @@ def extract_features(model, loader, num, images_per_pass=4, device=None, loader_
         raw = [loader(int(i)) for i in idx]
         if len({(img.shape, rule, tuple(sorted(kw.items()))) for img, rule, kw in raw}) == 1:
             return np.stack([img for img, _, _ in raw]), raw[0][1], raw[0][2]
+        if debayer is not None:
+            from ..util import robotcar
+            raw = [(robotcar.load_image_np(img, *debayer), rule, kw) for img, rule, kw in raw]
         return np.stack([np.asarray(size_on_host(*r), dtype=np.float32) for r in raw])
     on_host = 0                       # batches of mixed source shapes (device_resize only)
     if device_resize:
@@ -80,7 +90,10 @@ def extract_features(model, loader, num, images_per_pass=4, device=None, loader_
                 pending.append(pool.submit(load_batch, starts[k + ahead]))
             if isinstance(batch, tuple):
                 frames, rule, kw = batch
-                batch = resizer.apply(frames, rule, torch.float32, **kw)
+                if debayer is not None:
+                    batch = resizer.debayer(frames, debayer[0], debayer[1], debayer[2], rule, torch.float32, **kw)
+                else:
+                    batch = resizer.apply(frames, rule, torch.float32, **kw)
             else:
                 on_host += int(device_resize)
                 batch = torch.from_numpy(batch).to(device)
@@ -95,12 +108,16 @@ def extract_features(model, loader, num, images_per_pass=4, device=None, loader_
 
 
 def csv_loader(set_name, csv_root, img_root, vlad_cores=64, rescale=True, small_side=180, large_side=240,
-               device_resize=False):
+               device_resize=False, bayer=''):
     """(loader, num) over ``<csv_root>/<set>.csv`` (column ``path``): evaluation/inference.py:52-72,
     168-170.  ``device_resize``: the loader returns ``(decoded uint8 frame, rule, parameters)`` —
     the frame as decoded and the sizing it would have applied (``size_on_host``,
-    ``DeviceResizer.apply``) — for ``extract_features(device_resize=True)``."""
+    ``DeviceResizer.apply``) — for ``extract_features(device_resize=True)``.  ``bayer`` (a pattern;
+    needs ``device_resize``): the files are raw Bayer frames and are returned as decoded, uint8 [SH,SW];
+    a file with more than one channel raises."""
     from ..util import io
+    if bayer and not device_resize:
+        raise ValueError('raw Bayer frames (bayer=%r) are prepared on the device: device_resize=True' % (bayer,))
     meta = io.load_csv(os.path.join(csv_root, '{}.csv'.format(set_name)))
     if not isinstance(meta, dict) or 'path' not in meta:
         raise ValueError('%s.csv needs a "path" column and at least one row' % set_name)
@@ -110,7 +127,11 @@ def csv_loader(set_name, csv_root, img_root, vlad_cores=64, rescale=True, small_
         rel = paths[i]
         if 'oxs' in set_name:
             rel = rel.replace('.png', '.jpg')
-        img = io.load_img(os.path.join(img_root, rel))
+        if bayer:
+            from ..util import robotcar
+            img = robotcar.load_raw_png(os.path.join(img_root, rel))
+        else:
+            img = io.load_img(os.path.join(img_root, rel))
         return (img, rule, kw) if device_resize else size_on_host(img, rule, kw)
     if 'achen' in set_name:
         rule, kw = 'standard_size', dict(h=large_side, w=small_side)        # portrait images
@@ -154,7 +175,34 @@ def build_parser():
     p.add_argument('--device_resize', type=int, default=0,
                    help='1: size the decoded frames of a CSV set on the device (csrc/frames.hip; '
                         'the pickle is the same)')
+    p.add_argument('--bayer', default='',
+                   help='the files are raw one-channel Bayer frames of this pattern (gbrg: RobotCar stereo, rggb: '
+                        'mono); needs --device_resize 1 and --distortion_lut')
+    p.add_argument('--distortion_lut', default='', help='<camera>_distortion_lut.bin of the RobotCar SDK')
+    p.add_argument('--bayer_border', default='reflect', choices=['reflect', 'mirror'],
+                   help="what the demosaic reads outside the frame (util/robotcar.py; 'reflect' is scipy's default)")
     return p
+
+
+def raw_route(flags):
+    """--bayer / --distortion_lut / --bayer_border checked against the other flags, before any device
+    work: (pattern, table file, border), or None without --bayer."""
+    from ..util import robotcar
+    if not flags.bayer and not flags.distortion_lut:
+        return None
+    if not flags.bayer:
+        raise SystemExit('--distortion_lut belongs to --bayer PATTERN (one of %s)' % ', '.join(robotcar.PATTERNS))
+    if flags.bayer not in robotcar.PATTERNS:
+        raise SystemExit('--bayer is one of %s, not %r' % (', '.join(robotcar.PATTERNS), flags.bayer))
+    if not flags.device_resize:
+        raise SystemExit('--bayer prepares the raw frames on the device: it needs --device_resize 1')
+    if flags.set == 'synthetic' and not flags.csv_root:
+        raise SystemExit('--bayer reads the files of a CSV set (--set, --csv_root, --img_root)')
+    if not flags.distortion_lut:
+        raise SystemExit('--bayer needs --distortion_lut FILE (the camera model\'s look-up table)')
+    if not os.path.isfile(flags.distortion_lut):
+        raise SystemExit('--distortion_lut %s does not exist' % flags.distortion_lut)
+    return flags.bayer, flags.distortion_lut, flags.bayer_border
 
 
 def main(argv=None):
@@ -164,6 +212,7 @@ def main(argv=None):
     # is unreachable).  The whitening runs in evaluation/top_n.py.
     if flags.vlad_cores not in (0, 64) or flags.reduction not in ('none', 'pca') + reduction.KINDS:
         raise SystemExit('only --vlad_cores 64 | 0 with --reduction none|pca|1fc|2fc|3fc is on the hot path')
+    raw = raw_route(flags)
     np.random.seed(42)                                       # inference.py:270-271
     model = nets.VGG16NetVLAD(vlad_cores=flags.vlad_cores).cuda()
     if flags.reduction in reduction.KINDS:
@@ -180,8 +229,14 @@ def main(argv=None):
         device_resize = bool(flags.device_resize)
         loader, num = csv_loader(flags.set, flags.csv_root, flags.img_root, flags.vlad_cores,
                                  flags.rescale, flags.small_side, flags.large_side,
-                                 device_resize=device_resize)
-    feats = extract_features(model, loader, num, flags.images_per_pass, device_resize=device_resize)
+                                 device_resize=device_resize, bayer=raw[0] if raw else '')
+    debayer = None
+    if raw:
+        from ..util import robotcar
+        first = loader(0)[0]                              # the table is for the camera's frame size
+        debayer = (raw[0], robotcar.load_distortion_lut(raw[1], *first.shape), raw[2])
+    feats = extract_features(model, loader, num, flags.images_per_pass, device_resize=device_resize,
+                             debayer=debayer)
     os.makedirs(flags.out_root, exist_ok=True)
     out = os.path.join(flags.out_root, '{}_{}.pickle'.format(flags.set, flags.out_name))
     save_pickle(feats, out)

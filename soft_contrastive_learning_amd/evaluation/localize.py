@@ -127,22 +127,31 @@ class Localizer:
             desc = nets.output(t.to(next(model.parameters()).device), model=model).float()
         return self.locate_descriptors(desc, near, radius)
 
-    def prepare_raw(self, frames, rule='resize_img', **kw):
+    def prepare_raw(self, frames, rule='resize_img', bayer=None, lut=None, border='reflect', **kw):
         """Frames as the camera or the decoder delivers them (uint8 [SH,SW,C] or [n,SH,SW,C],
         NumPy or tensor, host or device) -> the float32 device batch the network sees, sized on the
         device by the loaders' rule (util/device_cv.py; bit for bit the host's util/cv.py):
         ``'resize_img'`` (``max_size=240``), ``'standard_size'`` (``h=180, w=240``) or ``'none'``
-        (widened only)."""
+        (widened only).
+
+        ``bayer`` (a pattern of ``util/robotcar.py``: 'gbrg' for the RobotCar stereo cameras): the
+        frames are raw one-channel Bayer mosaics, [SH,SW] or [n,SH,SW]; they are demosaiced,
+        undistorted by the camera's table ``lut`` (``robotcar.load_distortion_lut``; None: not at all)
+        and sized in one launch (``DeviceResizer.debayer``: ``robotcar.load_image_np`` then the rule,
+        bit for bit).  ``bayer=None``: ``lut`` and ``border`` are not read."""
         from ..util.device_cv import DeviceResizer
         if self._resizer is None:
             model = self.model
             device = self.device if model is None else next(model.parameters()).device
             self._resizer = DeviceResizer('cpu' if device is None else device)   # a CPU device raises
+        if bayer is not None:
+            return self._resizer.debayer(frames, bayer, lut, border, rule, torch.float32, **kw)
         return self._resizer.apply(frames, rule, torch.float32, **kw)
 
-    def locate_raw(self, frames, rule='resize_img', near=None, radius=None, **kw):
-        """``locate`` of ``prepare_raw(frames, rule, **kw)``."""
-        return self.locate(self.prepare_raw(frames, rule, **kw), near, radius)
+    def locate_raw(self, frames, rule='resize_img', near=None, radius=None, bayer=None, lut=None,
+                   border='reflect', **kw):
+        """``locate`` of ``prepare_raw(frames, rule, bayer, lut, border, **kw)``."""
+        return self.locate(self.prepare_raw(frames, rule, bayer, lut, border, **kw), near, radius)
 
     def explain(self, images, k=0, mode='gradcam', near=None, radius=None):
         """``locate(images, near, radius)`` plus WHY: -> (idx, feature_dist, xy, map [B, h, w] float32,
